@@ -13,13 +13,16 @@ itself when it is started as plain `python bench.py --gpus N`. Each rank owns B 
 collective in the data path); what crosses GPUs each frame is the fixed-size block of live-track records per stream,
 all-gathered over xGMI.
 
-Prints ONE JSON line (rank 0): the contract fields plus
+Prints ONE JSON line (rank 0). A plain run sets up, warms up, times --steps steps and prints the contract fields (metric, value,
+unit, higher_is_better, dtype, ms_per_step) with the run's configuration. --dump-outputs DIR also writes what the timed path
+computed in its last step as DIR/*.npy (dump_outputs). --full adds every other leg of the line:
   roofline           dominant kernel: algorithmic HBM bytes per launch / its mean launch duration measured IN THE TIMED REGION
                      with HIP event pairs on the launching stream (mot_profile_kernel), vs 8 TB/s
   cpu_baseline       the reference's own sources (oracle/_ref) on this box's host cores: single thread (median / p95 per
                      stage), frame-parallel over all cores, and the -O0 build the reference's CMakeLists produces by default
   tracker_stress     tracker kernel at 8 / 32 / 64 live tracks per stream
   host_boundary_pipelined   PCIe-inclusive rate through mot_frames_host (pinned, double-buffered, several contexts)
+  all_outputs, single_stream, dense_scene, point_order, parity_check   the other workloads and the comparison with the reference
 """
 from __future__ import annotations
 
@@ -122,6 +125,60 @@ def gpu_sequence_results(mot, device, seq_dev, n_seq, stride, ego_v, ego_yaw, st
                             grid=dig(cl["grid"]), num_cluster=cl["num_cluster"], boxes=bx["boxes"], boxes_global=gb[: len(bx["boxes"])].copy(),
                             tracks=tr, states={int(i): c.track_state(int(i)) for i in live}))
     return out
+
+
+DUMP_SAMPLE = 32   # streams whose label grids and track records --dump-outputs writes
+DUMP_CLOUDS = 8    # of those, streams whose elevated cloud and ground mask it writes too
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(out_dir, ctxs, n_last):
+    """--dump-outputs DIR: what the timed path computed in its last step, as a caller of mot_frames_dev receives it through the
+    getters, from the frame every context processed last: per stream the counts and the boxes; for a fixed, seeded sample of
+    streams the label grid and the track records, and for the first DUMP_CLOUDS of them the elevated cloud and the ground mask.
+    float32 where the library hands out float32, float64 for its fp64 values and for counts and integer fields; every value finite.
+    n_last[ci][b]: input points of the frame context ci processed last in slot b. Returns {name: shape}."""
+    Bc = len(n_last[0]); S = len(ctxs) * Bc
+    sample = np.sort(np.random.default_rng(0).choice(S, size=min(DUMP_SAMPLE, S), replace=False))
+    counts = {k: np.zeros(S, np.float64) for k in ("n_elevated", "n_ground", "n_boxes", "n_tracks")}
+    boxes, grids, ncl, elev, mask = [], [], [], [], []
+    tracks = {k: [] for k in ("track_manage", "is_static", "is_vis", "lifetime", "p", "v_yaw", "vis_box")}
+    for s in range(S):
+        cx, b = ctxs[s // Bc], s % Bc
+        g = cx.get_ground(b, want_clouds=False)
+        bx = cx.get_boxes(b)["boxes"]
+        tr = cx.get_tracks(b)
+        counts["n_elevated"][s], counts["n_ground"][s], counts["n_boxes"][s], counts["n_tracks"][s] = g["n_elevated"], g["n_ground"], len(bx), tr["n"]
+        boxes.append(bx)
+        if s not in sample:
+            continue
+        cl = cx.get_clusters(b)
+        grids.append(cl["grid"].astype(np.float32)); ncl.append(cl["num_cluster"])
+        for k in tracks:
+            tracks[k].append(tr[k])
+        if len(grids) <= DUMP_CLOUDS:
+            gc = cx.get_ground(b, n_hint=int(n_last[s // Bc][b]))
+            elev.append(gc["elevated"]); mask.append(gc["mask"].astype(np.float32))
+    arrays = dict(counts, boxes=np.concatenate(boxes).astype(np.float32), sample_streams=sample.astype(np.float64),
+                  sample_num_cluster=np.array(ncl, np.float64), sample_label_grid=np.stack(grids),
+                  sample_elevated=np.concatenate(elev).astype(np.float32), sample_ground_mask=np.concatenate(mask))
+    tracks = {k: np.concatenate(v) for k, v in tracks.items()}
+    # a filter that diverged (the reference's own arithmetic does too, and its guards then kill the track) keeps NaN in its
+    # continuous fields: those are written for the records whose fields are all finite, whose indices are written beside them
+    cont = ("p", "v_yaw", "vis_box")
+    finite = np.all([np.isfinite(tracks[k]).all(axis=1) for k in cont], axis=0)   # p [n, 3], v_yaw [n, 2], vis_box [n, 24]
+    arrays["sample_track_finite_index"] = np.flatnonzero(finite).astype(np.float64)
+    for k, v in tracks.items():
+        v = v[finite] if k in cont else v
+        arrays["sample_" + (k if k.startswith("track") else "track_" + k)] = v if v.dtype in (np.float32, np.float64) else v.astype(np.float64)
+    bad = [k for k, v in arrays.items() if not np.isfinite(v).all()]
+    assert not bad, f"--dump-outputs: non-finite values in {bad}"
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, f"--dump-outputs would write {total} bytes"
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    return {k: list(v.shape) for k, v in arrays.items()}
 
 
 def cpu_baseline(frames: np.ndarray, ego_v, ego_yaw, n_points: int, budget_s: float = 10.0, gpu_results=None, n_per_frame=None, lib=None, quick=False):
@@ -790,6 +847,8 @@ def selftest_cpu(args, rank, world):
     if tg:   # every rank holds every rank's packed block of every context
         blocks = tg.blocks_as_numpy()
         assert len(blocks) == world and all(len(per) == NC and all(int(c.min()) >= 0 and not trunc for c, _, trunc in per) for per in blocks)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, ctxs, [[N] * Bc] * NC)
     if rank == 0:
         frames = B * F * args.steps * world
         _JSON_OUT.write(json.dumps({"metric": "LiDAR frames/sec (120k-pt 64-beam cloud) end-to-end ground->cluster->track", "value": round(frames / dt, 2),
@@ -815,13 +874,13 @@ def main():
                     "kernels of one (CCL, polygon, tracker: one workgroup per stream) overlap the streaming kernels of the others")
     ap.add_argument("--density", type=float, default=1.0, help="scene density (cars / pedestrians) of the synthetic street")
     ap.add_argument("--scene", choices=("street", "plaza"), default="street",
-                    help="street: the default workload (~17 live tracks per stream); plaza: the tracker-load scene, 50-65 live tracks per stream (the default run reports it as the dense_scene leg)")
+                    help="street: the default workload (~17 live tracks per stream); plaza: the tracker-load scene, 50-65 live tracks per stream (a --full run reports it as the dense_scene leg)")
     ap.add_argument("--point-order", choices=("beam", "firing", "random"), default="beam",
                     help="order of a frame's points in memory: beam = beam-major (KITTI .bin files; the default workload), firing = azimuth-major (the 64 lasers of a firing "
                          "together: the velodyne driver's `velodyne_points`, OT/src/groundremove/main.cpp:146), random = a seeded permutation per frame. Same point SETS per frame")
-    ap.add_argument("--no-dense-scene", action="store_true", help="skip the dense_scene leg (plaza scene, the headline's shape) of the default run")
-    ap.add_argument("--no-point-order", action="store_true", help="skip the point_order leg (the headline's workload in firing and in random point order) of the default run")
-    ap.add_argument("--issue-threads", type=int, default=1, help="1 (default since round 5): a host thread per context issues its launches (the library calls release the GIL): +1.6 % over one "
+    ap.add_argument("--no-dense-scene", action="store_true", help="skip the dense_scene leg (plaza scene, the headline's shape) of a --full run")
+    ap.add_argument("--no-point-order", action="store_true", help="skip the point_order leg (the headline's workload in firing and in random point order) of a --full run")
+    ap.add_argument("--issue-threads", type=int, default=1, help="1 (default since round 5): a host thread per context issues its launches (the library calls release the GIL): +1.6 %% over one "
                     "thread in an interleaved A/B, profiles/r05_contexts_sweep.txt — equal in round 2, when a launch sequence took a third longer; 0: one host thread issues every context's "
                     "launches, frame by frame, in a fixed order — what a run with the per-frame collective (N > 1, --force-gather) always does: the collectives' order on every rank")
     ap.add_argument("--phase", type=int, default=38, help="frames by which context c runs ahead of context c-1 within the (shared) sequences: at any instant the contexts' launches "
@@ -834,7 +893,7 @@ def main():
     ap.add_argument("--shared-gpu-dryrun", action="store_true", help="every rank on device 0, collectives over gloo: drives the N > 1 code path of this script (spawn, stream "
                     "sharding, packed gather, max over ranks, the JSON line) on a 1-GPU box. Not a measurement; the line says so")
     ap.add_argument("--outputs", choices=["headline", "all"], default="headline", help="all: the HEADLINE itself runs with every by-product of the reference written "
-                    "(mot_set_fused_outputs GROUND | MASK | LABELS); default: the headline writes what the next stage reads, and the all-outputs rate is measured in a second, "
+                    "(mot_set_fused_outputs GROUND | MASK | LABELS); default: the headline writes what the next stage reads, and the all-outputs rate is measured by --full in a second, "
                     "shorter timed region of the same run and reported beside it as `all_outputs`")
     ap.add_argument("--no-all-outputs", action="store_true", help="skip the second timed region (every output written): profiling runs, whose per-kernel averages it would mix into")
     ap.add_argument("--kitti-dir", default=os.environ.get("MOT_KITTI_DIR"), help="a KITTI raw drive directory (…/2011_09_26_drive_0005_sync: velodyne_points/data/*.bin, oxts/data/*.txt): "
@@ -843,6 +902,9 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-aux", action="store_true", help="skip tracker_stress / host_boundary / per-kernel isolated timings")
     ap.add_argument("--selftest-cpu", action="store_true", help="launch-logic self-test on CPU (gloo + emulated kernels); not a measurement")
+    ap.add_argument("--full", action="store_true", help="every leg of the line: roofline and per-kernel timings, the all-outputs region, CPU baseline and "
+                    "parity check, tracker stress, single stream, host boundary, dense scene, point orders. Default: the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what their last step computed as DIR/<name>.npy (dump_outputs)")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -1093,9 +1155,13 @@ def main():
     # (ground_removal.cpp:226-247; the `ground` node publishes it, groundremove/main.cpp:125-132), the per-point mask and the per-point
     # cluster labels (getClusteredPoints, box_fitting.cpp:46-72). A second timed region of the same process, same streams, same phases.
     all_out = None
-    prof = [cx.profile_read() for cx in ctxs] if rank == 0 else None   # the dominant kernel's event pairs of the timed region (read before anything else is launched)
+    prof = [cx.profile_read() for cx in ctxs] if rank == 0 and args.full else None   # the dominant kernel's event pairs of the timed region (read before anything else is launched)
     host_timed = (host_issue[0], host_cpu[0])   # (run_frames overwrites them)
-    if rank == 0 and world == 1 and args.outputs == "headline" and not variant and not args.no_all_outputs:
+    if rank == 0 and args.dump_outputs:   # the timed steps' results, before any other leg touches the contexts
+        for cx in ctxs:
+            cx.profile_kernel(0, 1)
+        dump_outputs(args.dump_outputs, ctxs, [n_seq[(pos[ci] - 1) % F] for ci in range(NC)])
+    if rank == 0 and args.full and world == 1 and args.outputs == "headline" and not variant and not args.no_all_outputs:
         try:
             k_all = max(2, min(4, args.steps))
             for cx in ctxs:
@@ -1114,7 +1180,36 @@ def main():
             print(f"all-outputs leg failed: {e}", file=sys.stderr)
             all_out = None
     host_issue[0], host_cpu[0] = host_timed
+    BL = Bc  # frames per launch (one context)
+    frames = B * F * args.steps * world
     if rank == 0:
+        out = {
+            "metric": "LiDAR frames/sec (120k-pt 64-beam cloud) end-to-end ground->cluster->track",
+            "value": round(frames / dt, 1), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32/f64 (fp32 grid indices with fp64 intermediates, int32 grids/labels, fp64 tracker — the reference's types)",
+            "data": (("kitti" if kitti else "synthetic") + ("; DRY RUN: every rank on ONE device, gloo collectives — not a measurement" if args.shared_gpu_dryrun else "" if not variant else f"; EXPERIMENT BUILD {variant} — not the product library") + (f"; EXPERIMENT: launches skipped (mask {skip}) — not a measurement of the product" if skip else "")), "inputs": "hbm-resident (rendered into HBM before the timed region; see host_boundary_pipelined for the PCIe-inclusive rate)",
+            "timed_region_s": round(dt, 3), "host_issue_ms_per_step": round(host_issue[0] / args.steps * 1e3, 3),
+            "host_cpu_ms_per_step": round(host_cpu[0] / args.steps * 1e3, 3) if not (args.issue_threads and NC > 1) else None,
+            "host_unblocked_us_per_launch_sequence": round(host_unblocked_us, 1),
+            "host_note": "host_issue = wall time the issuing thread spent inside the asynchronous launch calls (includes waiting for room in the hardware queues); host_cpu = CPU time of "
+                         "that thread (time.thread_time) over the timed region; host_unblocked = one launch sequence issued right after a synchronise (nothing to wait for): the host's own cost",
+            "issue_threads": (NC if args.issue_threads and NC > 1 else 1),
+            "config": {"workload": f"configs[3]: ground removal -> CCL -> box fit -> batched IMM-UKF-PDA tracker on one MI355X per rank; one step = {F}-frame "
+                                   + (f"sequence (ego motion of KITTI drive_0005) of every stream, {N}-pt synthetic HDL-64E clouds, no frame repeated within a sequence" if not kitti else
+                                    f"drive {kitti['dir']} (its own velodyne scans, ~{N} pts, and oxts ego motion), every stream replaying the drive from its own copy in HBM")
+                                   + ("" if world == 1 else f"; sharded as configs[4] (every stream pinned to one GPU, RCCL all-gather of the live-track blocks per frame) "
+                                      f"with the SAME per-GPU work as the 1-GPU line (weak scaling); configs[4]'s 200 k-point frames: --points 200000"),
+                       "points_per_frame": N, "frames_per_stream_per_step": F, "streams_per_gpu": B, "streams": B * world, "distinct_scenes_per_gpu": 1 if kitti else Bc,
+                       "frames_per_step_per_gpu": B * F, "contexts_per_gpu": NC, "frames_per_launch": BL, "context_phase_frames": args.phase,
+                       "render_s": round(render_s, 1), "scene": args.scene, "scene_density": args.density, "point_order": "as recorded" if kitti else args.point_order, "kitti": kitti,
+                       "parallelism": f"stream-sharded x{world}" + (", all_gather of live-track records per frame (RCCL)" if world > 1 else ""), "gather": gather_kind},
+        }
+        if args.outputs == "all":
+            out["config"]["outputs"] = "all (ground cloud, mask, per-point labels written in the fused path)"
+    if rank == 0 and not args.full:   # the headline alone
+        _JSON_OUT.write(json.dumps(out) + "\n"); _JSON_OUT.flush()
+    elif rank == 0:
         nsamp = sum(p["samples"] for p in prof)
         shared_ms = sum(p["mean_ms"] * p["samples"] for p in prof) / max(nsamp, 1)
         # ---- the dominant kernel with the GPU to itself: the same pipeline, same data, ONE context (in the timed region the NC
@@ -1135,7 +1230,6 @@ def main():
         cl0 = ctx.get_clusters(0); bx0 = ctx.get_boxes(0); tr0 = ctx.get_tracks(0)
         live = [int((ctx.get_tracks(b)["track_manage"] > 0).sum()) for b in range(min(Bc, 16))]
         G = ctx.params.num_grid
-        BL = Bc  # frames per launch (one context)
         # algorithmic HBM bytes per launch (what a kernel must read and write once), at the last frame's counts
         EB = 12.0 if args.outputs == "headline" else 16.0   # bytes of an elevated point between the stages: packed x, y, z unless the ground cloud is written too (mot_internal.h PackedXyz)
         alg_bytes = {"polar_minz_kernel": 16.0 * n_tot,
@@ -1150,7 +1244,6 @@ def main():
                      "track_step_kernel": (2 * 1624.0 + 144.0) * max(int(np.mean(live)), 1) * BL}
         achieved = alg_bytes[dom] / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
         frame_bytes = sum(alg_bytes.values()) / BL
-        frames = B * F * args.steps * world
         # HBM bytes per launch from the committed PMC passes of this command (FETCH_SIZE x2 on gfx950 + WRITE_SIZE, KB), same launch size only
         traffic, traffic_src = None, None
         import glob
@@ -1163,47 +1256,23 @@ def main():
                 traffic = int((2.0 * pmc["FETCH_SIZE"] + pmc["WRITE_SIZE"]) * 1024 / 512 * BL)
                 traffic_src = (f"profiles/{RND}_pmc_B512.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this pipeline at 512 frames per launch (FETCH_SIZE x 2: the gfx950 "
                                f"correction for wide coalesced reads)" + ("" if BL == 512 else f", scaled to the {BL} frames of a launch here"))
-        out = {
-            "metric": "LiDAR frames/sec (120k-pt 64-beam cloud) end-to-end ground->cluster->track",
-            "value": round(frames / dt, 1), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32/f64 (fp32 grid indices with fp64 intermediates, int32 grids/labels, fp64 tracker — the reference's types)",
-            "data": (("kitti" if kitti else "synthetic") + ("; DRY RUN: every rank on ONE device, gloo collectives — not a measurement" if args.shared_gpu_dryrun else "" if not variant else f"; EXPERIMENT BUILD {variant} — not the product library") + (f"; EXPERIMENT: launches skipped (mask {skip}) — not a measurement of the product" if skip else "")), "inputs": "hbm-resident (rendered into HBM before the timed region; see host_boundary_pipelined for the PCIe-inclusive rate)",
-            "timed_region_s": round(dt, 3), "host_issue_ms_per_step": round(host_issue[0] / args.steps * 1e3, 3),
-            "host_cpu_ms_per_step": round(host_cpu[0] / args.steps * 1e3, 3) if not (args.issue_threads and NC > 1) else None,
-            "host_unblocked_us_per_launch_sequence": round(host_unblocked_us, 1),
-            "host_note": "host_issue = wall time the issuing thread spent inside the asynchronous launch calls (includes waiting for room in the hardware queues); host_cpu = CPU time of "
-                         "that thread (time.thread_time) over the timed region; host_unblocked = one launch sequence issued right after a synchronise (nothing to wait for): the host's own cost",
-            "issue_threads": (NC if args.issue_threads and NC > 1 else 1),
-            "config": {"workload": f"configs[3]: ground removal -> CCL -> box fit -> batched IMM-UKF-PDA tracker on one MI355X per rank; one step = {F}-frame "
-                                   + (f"sequence (ego motion of KITTI drive_0005) of every stream, {N}-pt synthetic HDL-64E clouds, no frame repeated within a sequence" if not kitti else
-                                    f"drive {kitti['dir']} (its own velodyne scans, ~{N} pts, and oxts ego motion), every stream replaying the drive from its own copy in HBM")
-                                   + ("" if world == 1 else f"; sharded as configs[4] (every stream pinned to one GPU, RCCL all-gather of the live-track blocks per frame) "
-                                      f"with the SAME per-GPU work as the 1-GPU line (weak scaling); configs[4]'s 200 k-point frames: --points 200000"),
-                       "points_per_frame": N, "frames_per_stream_per_step": F, "streams_per_gpu": B, "streams": B * world, "distinct_scenes_per_gpu": 1 if kitti else Bc,
-                       "frames_per_step_per_gpu": B * F, "contexts_per_gpu": NC, "frames_per_launch": BL, "context_phase_frames": args.phase,
-                       "elevated_pts_per_frame": ne_tot // BL, "clusters_last_frame_stream0": cl0["num_cluster"], "boxes_last_frame_stream0": len(bx0["boxes"]),
-                       "tracks_ever_stream0": int(tr0["n"]), "live_tracks_per_stream": {"mean": round(float(np.mean(live)), 1), "max": int(np.max(live)), "streams_sampled": len(live)},
-                       "render_s": round(render_s, 1), "scene": args.scene, "scene_density": args.density, "point_order": "as recorded" if kitti else args.point_order, "kitti": kitti,
-                       "parallelism": f"stream-sharded x{world}" + (", all_gather of live-track records per frame (RCCL)" if world > 1 else ""), "gather": gather_kind},
-            "roofline": {"bound": "hbm", "kernel": dom_kernel, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
-                         "frac_of_achievable": round(achieved / HBM_ACHIEVABLE_GBS, 4), "achievable_peak": HBM_ACHIEVABLE_GBS,
-                         "traffic_ratio": round(traffic / alg_bytes[dom], 4) if traffic else None,
-                         "moved_GBps": round(traffic / (dom_ms * 1e-3) / 1e9, 1) if traffic and dom_ms > 0 else None,
-                         "kernel_ms": {"mean": round(dom_ms, 5), "min": round(solo["min_ms"], 5), "max": round(solo["max_ms"], 5), "samples": solo["samples"],
-                                       "how": "HIP event pairs around the kernel's launch on its own stream (mot_profile_kernel), the whole pipeline running on ONE context, "
-                                              f"nothing else on the GPU; rocprofv3 summary of the same schedule: profiles/{RND}_kernel_trace_B512_1ctx.txt"},
-                         "kernel_ms_in_timed_region": {"mean": round(shared_ms, 5), "min": round(min(p["min_ms"] for p in prof), 5), "max": round(max(p["max_ms"] for p in prof), 5), "samples": nsamp,
-                                       "frac_if_taken_alone": round(alg_bytes[dom] / (shared_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if shared_ms > 0 else None,
-                                       "how": f"the same event pairs inside the timed region, where {NC} contexts' kernels run concurrently and share HBM and CUs: a launch's duration there is its "
-                                              f"share of the machine (see pipeline_frac for the whole); rocprofv3 summary: profiles/{RND}_kernel_trace_B2048_4ctx.txt"},
-                         "algorithmic_bytes_per_launch": {k: int(v) for k, v in alg_bytes.items()},
-                         "pipeline_bytes_per_frame": int(frame_bytes),
-                         "pipeline_frac": round(frame_bytes * B * F / (dt / args.steps) / 1e9 / HBM_PEAK_GBS, 4)},
-        }
-        if args.outputs == "all":
-            out["config"]["outputs"] = "all (ground cloud, mask, per-point labels written in the fused path)"
+        out["config"].update({"elevated_pts_per_frame": ne_tot // BL, "clusters_last_frame_stream0": cl0["num_cluster"], "boxes_last_frame_stream0": len(bx0["boxes"]),
+                              "tracks_ever_stream0": int(tr0["n"]), "live_tracks_per_stream": {"mean": round(float(np.mean(live)), 1), "max": int(np.max(live)), "streams_sampled": len(live)}})
+        out["roofline"] = {"bound": "hbm", "kernel": dom_kernel, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
+                           "frac_of_achievable": round(achieved / HBM_ACHIEVABLE_GBS, 4), "achievable_peak": HBM_ACHIEVABLE_GBS,
+                           "traffic_ratio": round(traffic / alg_bytes[dom], 4) if traffic else None,
+                           "moved_GBps": round(traffic / (dom_ms * 1e-3) / 1e9, 1) if traffic and dom_ms > 0 else None,
+                           "kernel_ms": {"mean": round(dom_ms, 5), "min": round(solo["min_ms"], 5), "max": round(solo["max_ms"], 5), "samples": solo["samples"],
+                                         "how": "HIP event pairs around the kernel's launch on its own stream (mot_profile_kernel), the whole pipeline running on ONE context, "
+                                                f"nothing else on the GPU; rocprofv3 summary of the same schedule: profiles/{RND}_kernel_trace_B512_1ctx.txt"},
+                           "kernel_ms_in_timed_region": {"mean": round(shared_ms, 5), "min": round(min(p["min_ms"] for p in prof), 5), "max": round(max(p["max_ms"] for p in prof), 5), "samples": nsamp,
+                                         "frac_if_taken_alone": round(alg_bytes[dom] / (shared_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if shared_ms > 0 else None,
+                                         "how": f"the same event pairs inside the timed region, where {NC} contexts' kernels run concurrently and share HBM and CUs: a launch's duration there is its "
+                                                f"share of the machine (see pipeline_frac for the whole); rocprofv3 summary: profiles/{RND}_kernel_trace_B2048_4ctx.txt"},
+                           "algorithmic_bytes_per_launch": {k: int(v) for k, v in alg_bytes.items()},
+                           "pipeline_bytes_per_frame": int(frame_bytes),
+                           "pipeline_frac": round(frame_bytes * B * F / (dt / args.steps) / 1e9 / HBM_PEAK_GBS, 4)}
         if all_out is not None:
             # algorithmic bytes with every output written: SURVEY.md 8(d)'s own accounting — ground 16 N + 16 N + 16 (N_e + N_g), cluster 16 N_e + 16 N_e
             # + 4 N_e + 0.5 MB of grid, box (16 + 4) N_e, 0.1 MB of polar grid = 48 N + 56 N_e + 0.6 MB — at this run's measured N, N_e

@@ -1,7 +1,7 @@
 """rocprofv3 (ROCm 7.2) writes a rocpd SQLite database; this prints the per-kernel summary (the `--stats` view)
 as a text table so that it can be committed under profiles/.
    python profiles/summarize_rocpd.py kt_results.db [--tail=N]
---tail=N adds a second table over the LAST N launches of every kernel. bench.py ends (with --no-aux --no-cpu-baseline) with its
+--tail=N adds a second table over the LAST N launches of every kernel. bench.py --full ends (with --no-aux --no-cpu-baseline) with its
 single-context pass — 60 frames on one context, nothing else on the GPU, in the SAME process and memory layout as the timed
 region — so `--tail=60` of a trace of the default command is the rocprofv3 view of the launches `roofline.kernel_ms` times."""
 import sqlite3

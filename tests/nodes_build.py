@@ -20,7 +20,8 @@ REF = "/root/reference/object_tracking"
 SHIM = os.path.join(ROOT, "oracle", "ref_shim")
 REF_BIN = os.path.join(ROOT, "oracle", "_ref", "bin")
 OWN_BIN = os.path.join(HERE, "emu", "bin")
-HIP_BIN = os.path.join(ROOT, "ros", "bin")     # the same node sources linked against libmot_hip.so: prebuilt here, run on the GPU box
+HIP_BIN = os.path.join(ROOT, "oracle", "_ref", "ros_bin")   # the same node sources linked against libmot_hip.so: built with oracle/_ref (they need the
+                                                           # reference's vendored Eigen) and run on the GPU box, where oracle/_ref travels
 HIP_LIB = os.path.join(ROOT, "3d-lidar-multi-object-tracking_amd", "libmot_hip.so")
 NODES = {"ground": "src/groundremove/main.cpp", "cluster": "src/cluster/main.cpp", "tracking": "tracking/main.cpp"}
 ALGO_HEADERS = ("ground_removal.h", "component_clustering.h", "box_fitting.h", "imm_ukf_jpda.h")
@@ -123,7 +124,7 @@ def _hip_link_extra():
 
 
 def hip_recipe_nodes() -> dict:
-    """the reference's UNMODIFIED node sources + the adapter header (recipe_nodes) linked against the real library: ros/bin/recipe_*,
+    """the reference's UNMODIFIED node sources + the adapter header (recipe_nodes) linked against the real library: oracle/_ref/ros_bin/recipe_*,
     built where /root/reference exists, run on the GPU box (tests/test_nodes_gpu.py). Plus the adapter's tracker driver."""
     os.makedirs(HIP_BIN, exist_ok=True)
     out = recipe_nodes(HIP_LIB, HIP_BIN, _hip_link_extra())

@@ -105,3 +105,24 @@ def test_stage_wise_leg_on_the_emulator(mot, synth):
     assert r["tracks_ever"] >= 1
     cb = r["call_by_call"]   # both forms ran the same frames: same boxes, same tracks
     assert cb["boxes_last_frame"] == r["boxes_last_frame"] and cb["tracks_ever"] == r["tracks_ever"] and cb["ms_per_frame"]["median"] > 0
+
+
+def test_bench_dump_outputs_are_the_same_run_to_run(tmp_path):
+    """`--dump-outputs DIR` (the --selftest-cpu run: the emulator build standing in for the GPU): what the timed steps computed last, as
+    finite float32 / float64 .npy files within 64 MB, equal between two runs of the same arguments"""
+    pytest.importorskip("torch")
+    import numpy as np
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d, n in zip(dirs, (1, 2)):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(n), "--warmup", "1", "--selftest-cpu",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+    names = sorted(os.listdir(dirs[0]))
+    assert names == sorted(os.listdir(dirs[1])) and "boxes.npy" in names and "sample_label_grid.npy" in names
+    total = 0
+    for name in names:
+        a, b = (np.load(d / name) for d in dirs)
+        assert a.dtype in (np.float32, np.float64) and a.dtype == b.dtype and np.isfinite(a).all(), name
+        assert np.array_equal(a, b, equal_nan=True), name
+        total += a.nbytes
+    assert 0 < total <= 64 << 20

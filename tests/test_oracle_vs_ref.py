@@ -219,10 +219,9 @@ def test_tracker_ot0_vs_ref0(oracle, synth, tmp_path):
     _need_ref(oracle)
     p0, p1 = oracle.params(0), oracle.params(1)
     nf = 40
-    # the package's own fixtures (ego motion of KITTI drive_0005, one value per frame)
-    if not os.path.isfile("/root/reference/object_tracking0/src/ego_velo.txt"):
-        pytest.skip("the reference's ego-motion fixtures are not on this box")
-    velo = np.loadtxt("/root/reference/object_tracking0/src/ego_velo.txt")[:nf]; yaw = np.loadtxt("/root/reference/object_tracking0/src/ego_yaw.txt")[:nf]
+    # the package's own fixtures (ego motion of KITTI drive_0005, one value per frame: ego_velo.txt / ego_yaw.txt, kept in golden/)
+    ego = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ego_drive0005.npz"))
+    velo = ego["ego_v"][:nf]; yaw = ego["ego_yaw"][:nf]
     T = oracle.Tracker(p1); R = oracle.Ref0Tracker(); R.reset(tmp_path, velo, yaw)
     try:
         seen = 0

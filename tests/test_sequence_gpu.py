@@ -78,11 +78,32 @@ def test_bench_on_a_kitti_shaped_drive(hip_lib, tmp_path):
             synth.make_cloud(60000 - 501 * f, 3, f).tofile(os.path.join(d, "velodyne_points", "data", f"{f:010d}.bin"))
             ox = np.zeros(30); ox[8] = 3.0 + 0.1 * f; ox[5] = 0.004 * f
             np.savetxt(os.path.join(d, "oxts", "data", f"{f:010d}.txt"), ox[None])
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--kitti-dir", d, "--batch", "8", "--contexts", "2", "--steps", "2", "--warmup", "1", "--no-aux",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--kitti-dir", d, "--batch", "8", "--contexts", "2", "--steps", "2", "--warmup", "1", "--full", "--no-aux",
                         "--no-cpu-baseline", "--phase", "2"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["data"] == "kitti" and line["value"] > 0 and line["config"]["kitti"]["frames"] >= 6 and line["all_outputs"]["value"] > 0
+
+
+def test_bench_plain_line_and_dumped_outputs(hip_lib, tmp_path):
+    """a plain `bench.py` run prints the headline alone, timed over --steps steps; `--dump-outputs DIR` writes what the last timed step
+    computed, the same for two runs of the same workload (seeded inputs; one and two timed steps)"""
+    import numpy as np
+    root = os.path.dirname(HERE)
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d, steps in zip(dirs, (1, 2)):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--batch", "8", "--contexts", "2", "--frames", "6", "--steps", str(steps), "--warmup", "1",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert line["steps"] == steps and line["value"] > 0 and line["ms_per_step"] > 0 and line["unit"] == "frames/s" and line["higher_is_better"]
+        assert "roofline" not in line and "cpu_baseline" not in line and "all_outputs" not in line
+    names = sorted(os.listdir(dirs[0]))
+    assert names == sorted(os.listdir(dirs[1])) and "boxes.npy" in names
+    for name in names:
+        a, b = (np.load(d / name) for d in dirs)
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all() and np.array_equal(a, b), name
+    assert np.load(dirs[0] / "n_boxes.npy").sum() > 0
 
 
 def test_sequence_mode_on_the_device(hip_lib):

@@ -1,6 +1,7 @@
 # bench.py (short, no auxiliary lines) on the product library and on every prebuilt variant in variants/ (tools/prebuild.py):
 #   bash tools/bench_variants.sh [steps] [extra bench args...]        -> gpurun_out/variants.txt
 cd ${GRAFT_REPO_ROOT:-.}; S=${1:-5}; shift; mkdir -p gpurun_out
+set -- --full "$@"   # the roofline leg the lines below print is part of bench.py --full
 run() { # name, lib ('' = product)
   MOT_BENCH_LIB=$2 timeout 300 python bench.py --steps $S --warmup 1 --no-aux --no-cpu-baseline "${@:3}" 2> gpurun_out/variant_$1.err | python -c "
 import sys, json

@@ -1,7 +1,7 @@
 # GPU session: mot_ring parity + bench with stage rings + prebuilt block-size variants + the default bench line
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp; O=gpurun_out/s1; mkdir -p $O
 timeout 600 python -m pytest tests/test_ring_gpu.py tests/test_abi.py -q 2>&1 | tail -4 | tee $O/pytest_ring.txt
-b() { n=$1; shift; timeout 300 python bench.py --steps 5 --warmup 1 --no-aux --no-cpu-baseline "$@" 2> $O/$n.err | python -c "
+b() { n=$1; shift; timeout 300 python bench.py --full --steps 5 --warmup 1 --no-aux --no-cpu-baseline "$@" 2> $O/$n.err | python -c "
 import sys, json
 try:
     d = json.loads(sys.stdin.readline())
@@ -17,5 +17,5 @@ except Exception as e:
   b ring3_b1536c3 --ring 3 --contexts 3 --batch 1536
   b free_b1024c2 --contexts 2 --batch 1024; } | tee $O/ring.txt
 bash tools/bench_variants.sh 5 > /dev/null; cp gpurun_out/variants.txt $O/
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err; tail -c 300 $O/bench_default.err; python -c "
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; tail -c 300 $O/bench_default.err; python -c "
 import json; d = json.load(open('$O/bench_default.json')); print(d['value'], d['roofline']['frac'], d['roofline']['pipeline_frac']); print(json.dumps(d.get('single_stream'))); print(json.dumps(d.get('tracker_stress')))"

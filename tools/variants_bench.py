@@ -10,7 +10,7 @@ batch, ctxs = sys.argv[1], sys.argv[2]
 for spec in sys.argv[3:]:
     name, _, fl = spec.partition("=")
     build.build(extra_flags=[f for f in fl.split(",") if f], force=True)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--batch", batch, "--contexts", ctxs], capture_output=True, text=True)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--batch", batch, "--contexts", ctxs], capture_output=True, text=True)
     try:
         d = json.loads(r.stdout.strip().splitlines()[-1])
         print(name, d["value"], d["ms_per_step"], {k: round(v, 4) for k, v in d["roofline"]["kernel_ms"].items() if k in ("track_step_kernel", "cluster_index_kernel")}, flush=True)
