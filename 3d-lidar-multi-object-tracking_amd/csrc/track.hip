@@ -888,9 +888,12 @@ __device__ void update_group(const TrackBuffers& tb, UpdateScratch* G, int b, in
 // Two instantiations of the same code, chosen ON THE DEVICE by the launch's number of live tracks (both are launched; the one whose range does not hold
 // n_items leaves at once — an empty launch costs the sequence nothing, profiles/r06_launch_boundaries.md):
 //   track_update_kernel        2 waves per SIMD (234 VGPRs, no scratch): 4 workgroups = 32 tracks per CU — the faster code while one round holds the launch
-//   track_update_dense_kernel  3 waves per SIMD (168 VGPRs, 200 bytes of scratch per lane): 6 workgroups = 48 tracks per CU — slower per track, fewer rounds:
-//                              512 streams x 64 live tracks 275 -> 245 us, 512 x 32 127 -> 134 us (profiles/r06_tracker_occupancy_variants.txt)
-// Same arithmetic, same results (-ffp-contract=off: a spill changes no rounding).
+//   track_update_dense_kernel  3 waves per SIMD (168 VGPRs, 200 bytes of scratch per lane): 6 workgroups = 48 tracks per CU — slower per track, fewer rounds.
+//                              Its effect on the step is UNMEASURED: the figures of profiles/r06_tracker_occupancy_variants.txt (512 streams x 64 live tracks
+//                              275 -> 245 us, 512 x 32 127 -> 134 us) come from whole-kernel occupancy variants and predate this kernel being reachable — until the
+//                              launch predicate in mot_launch_track was corrected, the dense launch was never issued by the default build.
+// Same arithmetic, same results (-ffp-contract=off: a spill changes no rounding) — held on the MI355X by tests/test_tracker_gpu.py
+// (test_dense_threshold_crossings, test_dense_variant_library_equals_the_default_bit_for_bit).
 #ifndef MOT_UPDATE_DENSE_TRACKS
 #define MOT_UPDATE_DENSE_TRACKS 24576   // live tracks of a launch from which the dense instantiation runs
 #endif
@@ -1296,7 +1299,7 @@ void mot_launch_track(const TrackBuffers& t, int batch, hipStream_t stream, bool
   int item_groups = batch * 8;   // 2 waves x 4 tracks each: one round covers 64 live tracks per stream; the chip holds 1536 such workgroups of the prediction and of the
   item_groups = item_groups < 16 ? 16 : (item_groups > 1536 ? 1536 : item_groups);   // dense update (6 per CU: 3 waves per SIMD), 1024 of the plain update (4 per CU)
 #endif
-  const bool two_updates = item_groups * 8 > MOT_UPDATE_DENSE_TRACKS / 2;   // (a launch this small never reaches the dense range: one update launch)
+  const bool two_updates = (long)batch * t.T >= MOT_UPDATE_DENSE_TRACKS;   // (a call whose streams cannot hold that many live tracks never reaches the dense range: one update launch)
 #ifndef MOT_STREAM_KERNEL_MAX_BATCH
 #define MOT_STREAM_KERNEL_MAX_BATCH 32
 #endif

@@ -24,8 +24,17 @@ SAN_FLAGS = (["-fsanitize=address", "-fno-omit-frame-pointer"] if ASAN else
 PERTURB = bool(os.environ.get("MOT_EMU_PERTURB"))
 # MOT_EMU_DEFINES="-DMOT_X=1 -DMOT_Y=2": a variant build of the kernels (the knobs tools/prebuild.py gives hipcc), in a library of its own
 DEFINES = os.environ.get("MOT_EMU_DEFINES", "").split()
-_TAG = ("_" + "".join(ch if ch.isalnum() else "_" for ch in "".join(DEFINES))) if DEFINES else ""
-LIB = os.path.join(HERE, ("libmot_emu_asan" if ASAN else "libmot_emu_ubsan" if SANITIZE else "libmot_emu_ulp" if PERTURB else "libmot_emu") + _TAG + ".so")
+
+
+def _tag(defines):
+    return ("_" + "".join(ch if ch.isalnum() else "_" for ch in "".join(defines))) if defines else ""
+
+
+def lib_path(defines=None):
+    return os.path.join(HERE, ("libmot_emu_asan" if ASAN else "libmot_emu_ubsan" if SANITIZE else "libmot_emu_ulp" if PERTURB else "libmot_emu") + _tag(DEFINES if defines is None else list(defines)) + ".so")
+
+
+LIB = lib_path()
 
 
 def sources():
@@ -35,7 +44,10 @@ def sources():
     return m.SOURCES, m.HEADERS
 
 
-def build(force: bool = False) -> str:
+def build(force: bool = False, defines=None) -> str:
+    """defines: a variant build of its own beside the default one, as MOT_EMU_DEFINES gives (e.g. ("-DMOT_UPDATE_DENSE_TRACKS=4",)): two libraries in one process"""
+    DEFINES = globals()["DEFINES"] if defines is None else list(defines)
+    LIB = lib_path(DEFINES); _TAG = _tag(DEFINES)
     srcs, hdrs = sources()
     deps = [os.path.join(CSRC, s) for s in srcs + hdrs] + [os.path.join(HERE, "hipemu.h"), os.path.abspath(__file__)]
     if not force and os.path.exists(LIB) and all(os.path.getmtime(d) <= os.path.getmtime(LIB) for d in deps):

@@ -51,6 +51,9 @@ __asm__(
 #include <cstring>
 #include <algorithm>
 #include <functional>
+#include <map>
+#include <mutex>
+#include <string>
 #include <vector>
 
 #define __global__
@@ -285,8 +288,22 @@ inline void launch(dim3 grid, dim3 block, F&& f) {
 #define gridDim (hipemu::S().grid)
 #define warpSize 64
 
+// launches per kernel NAME since the library was loaded (the macro sees the name): lets a CPU test tell which kernels a call issued — e.g.
+// that a context able to hold MOT_UPDATE_DENSE_TRACKS live tracks gets track_update_dense_kernel launched and a smaller one does not
+// (tests/test_emu_tracker.py). Emulator-only accessor; the product library has no such symbol.
+namespace hipemu {
+inline std::map<std::string, long>& launch_counts() { static std::map<std::string, long> m; return m; }
+inline std::mutex& launch_counts_mu() { static std::mutex mu; return mu; }   // (contexts of the gather tests launch from several host threads)
+inline void count_launch(const char* name) { std::lock_guard<std::mutex> g(launch_counts_mu()); ++launch_counts()[name]; }
+}  // namespace hipemu
+extern "C" __attribute__((weak, used, visibility("default"))) long hipemu_launch_count(const char* kernel_name) {
+  std::lock_guard<std::mutex> g(hipemu::launch_counts_mu());
+  auto& m = hipemu::launch_counts();
+  auto it = m.find(kernel_name);
+  return it == m.end() ? 0 : it->second;
+}
 #define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...) \
-  hipemu::launch((grid), (block), [=]() { kernel(__VA_ARGS__); })
+  (hipemu::count_launch(#kernel), hipemu::launch((grid), (block), [=]() { kernel(__VA_ARGS__); }))
 
 static inline void __syncthreads() { hipemu::syncthreads(); }
 static inline unsigned long long __ballot(int p) { return hipemu::ballot(p != 0); }

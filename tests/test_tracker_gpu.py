@@ -260,3 +260,64 @@ def _report_head(st):
     print("long run, head vs the reference builds:", st["reference_builds_stepped"], "frames", st.get("reference_frames"), "retired at",
           st.get("reference_builds_retired_at"), st.get("head_vs_reference_builds"))
     assert st.get("reference_frames", 0) >= 40 and st["head_vs_reference_builds"]["state_compares"] > 50
+
+
+# ---- the many-stream path: four launches, one work list over all streams (what 512-stream contexts run); tests/tracker_cases.py has the bodies
+
+def _timed(fn, *a, **kw):
+    import time
+    t0 = time.time()
+    st = fn(*a, **kw)
+    st["wall_s"] = round(time.time() - t0, 1)
+    return st
+
+
+def test_wide_batch_four_launch_path_vs_oracle(mot, hip_lib, oracle):
+    """256 streams in one context under AUTO (batch * 8 reaches the 1536-workgroup clamp, the plain update its 1024: every workgroup takes several rounds of the
+    work list): empty, 1-box, ~8-box, crowded (2 m), late and 64-box streams side by side, every stream its own sequence, a partial reset, a repeated timestamp,
+    a call that leaves streams out; > 14 000 live tracks at the peak. Every stream on every frame against its own reference tracker."""
+    import tracker_cases as TC
+    st = _timed(TC.wide_batch, mot, oracle, _to_dev, size="gpu")
+    print("wide_batch:", {k: v for k, v in st.items() if k != "live_by_kind"}, st["live_by_kind"])
+    assert st["streams"] >= 224 and max(st["live_total"]) >= 12000
+
+
+def test_dense_threshold_crossings(mot, hip_lib, oracle):
+    """512 streams x 64 track slots, default library, AUTO: the live-track count of the step crosses MOT_UPDATE_DENSE_TRACKS = 24576 back and forth, with one
+    step at exactly 24576 and one at 24575 — track_update_dense_kernel (3 waves per SIMD, spills) and track_update_kernel take turns on the device. Every stream
+    on every frame against its own reference tracker; the planned sequence of n_items is asserted from the oracles' live counts."""
+    import tracker_cases as TC
+    st = _timed(TC.dense_threshold, mot, oracle, _to_dev)
+    print("dense_threshold:", {k: v for k, v in st.items() if k != "live_by_kind"}, st["live_by_kind"])
+
+
+def test_tracker_launch_modes_give_identical_results_on_the_device(mot, hip_lib, oracle):
+    """MOT_TRACKER_SPLIT against MOT_TRACKER_STREAM on the MI355X: outputs and every state key bit for bit, NaNs included (random, hostile and 40-live-track sequences)"""
+    import tracker_cases as TC
+    st = _timed(TC.launch_modes_identical, mot, oracle, _to_dev)
+    print("launch modes:", st)
+
+
+@pytest.fixture(scope="session")
+def dense4_lib(hip_lib):
+    """test-variant library with the dense threshold pulled down to 4 live tracks (variants/ is not in git; built once when missing)"""
+    import os
+    import conftest
+    build = conftest.load_sub("build")
+    out = os.path.join(conftest.ROOT, "variants", "libmot_dense4.so")
+    deps = [os.path.join(build.CSRC, s) for s in build.SOURCES + build.HEADERS]
+    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        build.build(extra_flags=("-DMOT_UPDATE_DENSE_TRACKS=4",), out=out)
+    return out
+
+
+def test_dense_variant_library_equals_the_default_bit_for_bit(mot, hip_lib, dense4_lib, oracle):
+    """-DMOT_UPDATE_DENSE_TRACKS=4 against the default library, both in SPLIT mode: the golden sequences cross the threshold back and forth, the 64-live-track
+    case sits above it — the spilled instantiation held against the unspilled one directly: bit-identical; and both within the bar of the reference."""
+    import conftest
+    import tracker_cases as TC
+    build = conftest.load_sub("build")
+    st = _timed(TC.dense_variant_identical, mot, oracle, _to_dev, build.LIB, dense4_lib, G.TRACKERS)
+    print("dense variant:", st)
+    assert st["threshold_crossings"] >= 2, st

@@ -237,3 +237,392 @@ def long_run_bounded_slots(mot, oracle, lib_path=None, frames=1500, slots=16, sp
     assert ever_total >= min_ever_factor * slots and stats["live_peak"] <= slots, (ever_total, stats)
     stats["tracks_ever"] = ever_total
     return stats
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Many streams in ONE context: the step as four launches (track_prep -> track_predict -> track_update [+ track_update_dense] -> track_finish,
+# csrc/track.hip mot_launch_track), the live tracks of all streams dealt over the chip through one work list. Contexts of more than
+# MOT_STREAM_KERNEL_MAX_BATCH = 32 streams take that path under AUTO; the bodies below never set a mode.
+
+DENSE_TRACKS = 24576   # MOT_UPDATE_DENSE_TRACKS of the default build (csrc/track.hip): n_items >= this -> the dense update instantiation works
+
+
+class StreamPlan:
+    """what ONE stream of a many-stream run is fed: `nbox` boxes of grid_boxes(spacing) from frame `start` on (none before), drawn from
+    default_rng(seed) the way many_live_tracks draws them; `resets`: frames before whose step the stream's tracks are forgotten
+    (mot_reset_tracks_slot / the oracle's reset); `dup`: the frame that repeats its predecessor's timestamp (dt = 0); `skips`: frames on
+    which the stream is not part of the call at all (neither side is stepped, its clock stands still)"""
+
+    def __init__(self, kind, nbox, spacing=9.0, seed=0, start=0, resets=(), dup=None, skips=()):
+        self.kind, self.nbox, self.spacing, self.seed, self.start = kind, int(nbox), float(spacing), int(seed), int(start)
+        self.resets, self.dup, self.skips = frozenset(resets), dup, frozenset(skips)
+
+    def key(self):
+        """the schedule without the seed: what a seed is selected FOR (tools: tests/golden/make_stream_seeds.py)"""
+        return (self.nbox, self.spacing, self.start, tuple(sorted(self.resets)), self.dup, tuple(sorted(self.skips)))
+
+    def boxes(self, frames):
+        rng = np.random.default_rng(self.seed)
+        n = max(self.nbox, 1)
+        vel = rng.uniform(-1.0, 1.0, size=(1, n, 2))
+        out = [grid_boxes(1, n, f, vel, rng, self.spacing)[0] for f in range(frames)]   # (drawn for every frame: a late start does not shift the sequence)
+        return [b[: self.nbox if f >= self.start else 0] for f, b in enumerate(out)]
+
+    def timestamps(self, frames):
+        ts = [1.0e9 + f * 1.0e5 for f in range(frames)]
+        if self.dup is not None:
+            ts[self.dup] = ts[self.dup - 1]
+        return ts
+
+
+def replay_on_oracle(plan, frames, tracker, on_frame=None):
+    """the stream's exact schedule on one oracle tracker; -> live count after every frame (None where the stream did not run)"""
+    bx, ts = plan.boxes(frames), plan.timestamps(frames)
+    live = []
+    for f in range(frames):
+        if f in plan.skips:
+            live.append(None); continue
+        if f in plan.resets:
+            tracker.reset()
+        tracker.ego_update(ts[f], 0.0, 0.0)
+        o = tracker.step(bx[f], ts[f], max_tracks=1024)
+        live.append(int((o["track_manage"] != 0).sum()))
+        if on_frame is not None:
+            on_frame(f, o)
+    return live
+
+
+def _compare_records(a, o, where, rtol=SP.RTOL):
+    """discrete outputs exact, NaN patterns equal, the records of the live tracks (position, speed / yaw, visible box) within rtol of the
+    vector they belong to — seq_parity.compare_tracks's output checks for a whole stream at once, without the per-track state fetch"""
+    assert a["n"] == o["n"], (where, a["n"], o["n"])
+    for k in ("track_manage", "is_static", "is_vis"):
+        assert np.array_equal(a[k], o[k]), (where, k, np.nonzero(a[k] != o[k])[0][:8])
+    if "lifetime" in o:
+        assert np.array_equal(a["lifetime"], o["lifetime"]), (where, "lifetime")
+    live = o["track_manage"] > 0
+    for key, atol in (("p", 1e-6), ("v_yaw", 1e-7), ("vis_box", 1e-5)):
+        av, ov = np.asarray(a[key], np.float64)[live], np.asarray(o[key], np.float64)[live]
+        nan = np.isnan(ov)
+        assert np.array_equal(nan, np.isnan(av)), (where, key, "NaN pattern")
+        if av.size:
+            scale = np.nanmax(np.where(nan, 0.0, np.abs(ov)), axis=1, keepdims=True)
+            bad = np.where(nan, 0.0, np.abs(av - ov)) > rtol * scale + atol
+            assert not bad.any(), (where, key, np.nonzero(bad.any(axis=1))[0][:8])
+    return int(live.sum())
+
+
+def run_stream_plans(mot, oracle, to_dev, plans, frames, lib_path=None, slots=64, full_every=5, always=(), mode=None, short_call=None):
+    """`plans[s]` on slot s of ONE context through mot_track_steps_dev, one oracle tracker per stream, stepped ONE AFTER ANOTHER while the device works: the
+    reference build is not re-entrant even across its private library copies (oracle/ref_capi.cpp's Quiet swaps the process-wide std::cout buffer for a
+    stack-local sink; stepping copies from a thread pool crashed the host in exactly that, on the first run of this body) — 4 ms a step, 37 s for the largest case. Every stream on every frame: discrete outputs exact and the track records within the bar
+    (_compare_records); the full filter state of every live track (seq_parity.compare_tracks, every STATE_KEY) on every `full_every`-th
+    frame and the last, and on every frame for the streams in `always`. Streams of spacing < 6 m (shared gates) are compared with
+    skip_ill_conditioned exactly as many_live_tracks does, and always in full; no other stream has anything set aside — asserted by the callers
+    through stats["ill_conditioned_9m"]. short_call = (frame, k): on that frame the call covers all but the last k streams (their plans
+    must list the frame in `skips`).
+    -> stats: n_items[f] (the work-list length of step f, from the oracles' live counts: a stream contributes what it held after its
+    previous step, nothing on a first frame or when it does not run), live_total[f], live_by_kind, resets, state_compares, ..."""
+    B = len(plans)
+    p = oracle.params(0)
+    kw = dict(lib_path=lib_path) if lib_path else {}
+    boxes = [pl.boxes(frames) for pl in plans]
+    tss = [pl.timestamps(frames) for pl in plans]
+    maxbox = max(max(pl.nbox for pl in plans), 1)
+    stride = maxbox * 24
+    always = set(always) | {s for s, pl in enumerate(plans) if pl.spacing < 6}
+    stats, stats2m = {}, {}
+    n_items, live_total, resets = [], [], 0
+    held = [0] * B            # live-list length each stream holds (what its next step contributes to the work list)
+    fresh = [True] * B        # the next step of the stream is a first frame
+    live_by_kind, peak_by_stream = {}, [0] * B
+    records_compared = 0
+    with mot.Context(max_points=1024, max_batch=B, max_tracks_total=slots, **kw) as c:
+        if mode is not None:
+            c.set_tracker_mode(mode)
+        Ts = [oracle.Tracker(p) for _ in range(B)]
+        try:
+            for f in range(frames):
+                nb = B - short_call[1] if short_call and short_call[0] == f else B
+                run = [s < nb for s in range(B)]
+                for s, pl in enumerate(plans):
+                    assert (f in pl.skips) == (not run[s]), (f, s, "plan and call disagree about who runs")
+                    if f in pl.resets:
+                        c.reset_tracks_slot(s); Ts[s].reset(); fresh[s] = True; held[s] = 0; resets += 1
+                n_items.append(sum(held[s] for s in range(B) if run[s] and not fresh[s]))
+                host = np.zeros((B, stride), np.float32)
+                m = [len(boxes[s][f]) for s in range(B)]
+                for s in range(B):
+                    host[s, : m[s] * 24] = boxes[s][f].reshape(-1)
+                ptr, free = to_dev(host)
+                egos = [c.ego_update(tss[s][f], 0.0, 0.0, s) for s in range(nb)]
+                c.track_steps_dev(ptr, stride, m[:nb], [tss[s][f] for s in range(nb)])
+
+                def orc_step(s):
+                    e = Ts[s].ego_update(tss[s][f], 0.0, 0.0)
+                    return e, Ts[s].step(boxes[s][f], tss[s][f], max_tracks=1024)
+                outs = [orc_step(s) for s in range(nb)]
+                full_frame = f % full_every == 0 or f == frames - 1
+                tot = 0
+                for s in range(nb):
+                    e, o = outs[s]
+                    # (the oracle has no tracks-only reset: its reset() also starts the ego dead reckoning over, and getOriginPoints' first call reports the
+                    # first-frame yaw offset. The ego stands still here (v = 0, yaw = 0), so the origin of the global frame is the same on both sides, and
+                    # the one record a first frame writes — the seed track's — does not depend on the ego yaw. From the next frame on the poses must be equal again.)
+                    assert np.array_equal(e, egos[s]) or f in plans[s].resets, (f, s, "ego pose", e, egos[s])
+                    a = c.get_tracks(s)
+                    assert not a["capacity_exceeded"], (f, s)
+                    if full_frame or s in always:
+                        two_m = plans[s].spacing < 6
+                        SP.compare_tracks(a, o, lambda i: c.track_state(i, slot=s), Ts[s].state, (f, s, plans[s].kind), stats=stats2m if two_m else stats, skip_ill_conditioned=two_m)
+                    else:
+                        _compare_records(a, o, (f, s, plans[s].kind))
+                    records_compared += int((o["track_manage"] > 0).sum())
+                    held[s] = int((o["track_manage"] != 0).sum()); fresh[s] = False
+                    peak_by_stream[s] = max(peak_by_stream[s], held[s])
+                    tot += held[s]
+                tot += sum(held[s] for s in range(nb, B))
+                live_total.append(tot)
+                free()
+        finally:
+            for T_ in Ts:
+                T_.close()
+    for s, pl in enumerate(plans):
+        k = live_by_kind.setdefault(pl.kind, dict(streams=0, peak_min=1 << 30, peak_max=0))
+        k["streams"] += 1; k["peak_min"] = min(k["peak_min"], peak_by_stream[s]); k["peak_max"] = max(k["peak_max"], peak_by_stream[s])
+    return dict(n_items=n_items, live_total=live_total, resets=resets, live_by_kind=live_by_kind, records_compared=records_compared,
+                state_compares=stats.get("state_compares", 0) + stats2m.get("state_compares", 0), ill_conditioned_9m=stats.get("ill_conditioned", 0),
+                ill_conditioned_2m=stats2m.get("ill_conditioned", 0), max_rel_state_err=stats.get("max_rel_state_err", 0.0),
+                max_rel_state_err_2m=stats2m.get("max_rel_state_err", 0.0), streams=B, frames=frames)
+
+
+STREAM_SEEDS = "stream_seeds.json"   # tests/golden: the selected seeds of the 9 m streams, per case and schedule (tests/golden/make_stream_seeds.py)
+
+
+def fixture_seeds(case):
+    """-> next_seed(plan_key): the committed seeds for the streams of `case`, in order; running out of them is an error (a plan that
+    changed needs its seeds selected again: the seed list changes, never the bar)"""
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", STREAM_SEEDS)) as fh:
+        table = json.load(fh)[case]
+    taken = {}
+
+    def next_seed(key):
+        k = repr(key)
+        i = taken.get(k, 0); taken[k] = i + 1
+        assert k in table and i < len(table[k]), ("no selected seed left for schedule", k, "of", case, ": run tests/golden/make_stream_seeds.py")
+        return table[k][i]
+    return next_seed
+
+
+def _seeded(plans, next_seed):
+    """the 9 m streams get selected seeds (per schedule); the 2 m and the empty streams keep the fixed ones they were planned with"""
+    for pl in plans:
+        if pl.spacing >= 6 and pl.nbox > 0:
+            pl.seed = next_seed(pl.key())
+    return plans
+
+
+WIDE_SIZES = {
+    # streams of each kind; boxes of a "full" stream; frames; the frame of the partial reset, of the repeated timestamp, of the short call
+    "gpu": dict(empty=6, one=6, eight=10, crowded=6, late=40, full=188, nbox=64, frames=16, reset_at=9, dup_at=6, short_at=12, short_k=5, late_start=3, slots=128),
+    "emu": dict(empty=2, one=2, eight=4, crowded=2, late=6, full=24, nbox=16, frames=12, reset_at=7, dup_at=5, short_at=9, short_k=3, late_start=3, slots=32),
+}
+
+
+def wide_batch_plans(size, next_seed):
+    """streams of very different sizes side by side, interleaved over the slots (kinds alternate, so one wave's four work items regularly
+    belong to different streams and kinds), ragged in time: `late` streams get their first boxes `late_start` frames after the others; at
+    `reset_at` every 6th full stream, one one-box, one eight-box and one crowded stream are reset while the rest carry on; one full stream
+    repeats a timestamp at `dup_at`; at `short_at` the call leaves the last `short_k` streams (full ones) out."""
+    z = WIDE_SIZES[size]
+    kinds = ["empty"] * z["empty"] + ["one"] * z["one"] + ["eight"] * z["eight"] + ["crowded"] * z["crowded"] + ["late"] * z["late"] + ["full"] * (z["full"] - z["short_k"])
+    order = np.random.default_rng(2024).permutation(len(kinds))
+    kinds = [kinds[i] for i in order] + ["full"] * z["short_k"]
+    plans, seen = [], {}
+    for s, kind in enumerate(kinds):
+        j = seen.get(kind, 0); seen[kind] = j + 1
+        last = s >= len(kinds) - z["short_k"]
+        resets = (z["reset_at"],) if (kind == "full" and j % 6 == 1 and not last) or (kind in ("one", "eight", "crowded") and j == 1) else ()
+        nbox = dict(empty=0, one=1, eight=(7, 9, 8)[j % 3], crowded=z["nbox"], late=z["nbox"], full=z["nbox"])[kind]
+        plans.append(StreamPlan(kind, nbox, spacing=2.0 if kind == "crowded" else 9.0, seed=500 + s, start=z["late_start"] if kind == "late" else 0, resets=resets,
+                                dup=z["dup_at"] if kind == "full" and j == 0 else None, skips=(z["short_at"],) if last else ()))
+    return _seeded(plans, next_seed)
+
+
+def wide_batch(mot, oracle, to_dev, lib_path=None, size="gpu", next_seed=None):
+    """The four-launch tracker step against one oracle tracker per stream, AUTO mode (more than 32 streams: the product's own switch picks the
+    launches). See wide_batch_plans for what runs side by side and run_stream_plans for what is compared. Asserts what the run exercised."""
+    z = WIDE_SIZES[size]
+    plans = wide_batch_plans(size, next_seed or fixture_seeds("wide_" + size))
+    B, nbox, frames = len(plans), z["nbox"], z["frames"]
+    assert B > 32
+    always = [next(s for s, pl in enumerate(plans) if pl.kind == k) for k in ("empty", "one", "eight", "crowded", "late", "full")]
+    always += [s for s, pl in enumerate(plans) if pl.resets or pl.dup is not None or pl.skips][:8]
+    always += [s for s in range(B) if s not in always][: max(0, 16 - len(set(always)))]
+    st = run_stream_plans(mot, oracle, to_dev, plans, frames, lib_path=lib_path, slots=z["slots"], full_every=5, always=always, short_call=(z["short_at"], z["short_k"]))
+    st["always"] = len(set(always))
+    k = st["live_by_kind"]
+    # what the run exercised — a comparison that silently went empty fails here
+    assert k["empty"]["streams"] == z["empty"] and k["empty"]["peak_max"] == 0, k            # the empty streams stayed empty
+    assert k["one"]["peak_min"] == 1 and k["one"]["peak_max"] == 1, k
+    assert 7 <= k["eight"]["peak_min"] and k["eight"]["peak_max"] <= 9, k
+    assert k["full"]["peak_min"] == nbox and k["late"]["peak_min"] == nbox, k
+    assert k["crowded"]["peak_min"] >= nbox // 4, k
+    n_full = z["full"] + z["late"]
+    assert max(st["live_total"]) >= n_full * nbox and max(st["n_items"]) >= n_full * nbox, st["live_total"]
+    n_reset = sum(1 for pl in plans if pl.resets)
+    assert st["resets"] == n_reset and n_reset >= 4, st["resets"]
+    odd = sum(1 for n in st["n_items"] if n % 8 and n % 64)
+    assert odd > frames // 2, st["n_items"]                                                    # a ragged tail in the last wave on most frames
+    assert st["ill_conditioned_9m"] == 0, st                                                     # selected seeds: nothing of a 9 m stream is set aside
+    assert st["max_rel_state_err"] <= SP.RTOL
+    always_min = sum(1 for f in range(frames) for s in set(always) if f not in plans[s].skips and plans[s].nbox and f > plans[s].start + 1) * 1
+    assert st["state_compares"] >= 4 * (n_full - z["short_k"]) * nbox + always_min, st["state_compares"]   # >= 4 full frames of every full stream + the always-streams
+    assert st["records_compared"] >= (frames - 6) * (n_full - z["short_k"]) * nbox, st["records_compared"]
+    return st
+
+
+DENSE_PLAN = dict(streams=512, nbox=64, frames=18, odd_stream=350, odd_nbox=63,
+                  # frame -> the streams whose tracks are forgotten before it
+                  resets={4: range(0, 200), 8: range(200, 350), 11: range(350, 478), 14: range(0, 128)})
+# n_items of every step with the canonical live counts (a stream holds 1 track after a first frame, its box count after that — the seeds are
+# selected for exactly that, make_stream_seeds.py): 511 x 64 + 63 = 32767 when everything runs at full size
+DENSE_N_ITEMS = [0, 512, 32767, 32767,
+                 312 * 64 - 1, 312 * 64 - 1 + 200, 32767, 32767,        # 200 streams reset: below, below, above again
+                 362 * 64 - 1, 362 * 64 - 1 + 150, 32767,                # another 150: below (23167, 23317), above
+                 384 * 64, 384 * 64 + 128, 32767,                        # 128 reset, the 63-box stream among them: EXACTLY 24576 -> the dense kernel's first count
+                 383 * 64 + 63, 383 * 64 + 63 + 128, 32767, 32767]       # 128 others: 24575 -> the plain kernel's last count
+
+
+def dense_threshold_plans(next_seed):
+    d = DENSE_PLAN
+    plans = []
+    for s in range(d["streams"]):
+        resets = [f for f, who in d["resets"].items() if s in who]
+        plans.append(StreamPlan("odd" if s == d["odd_stream"] else "full", d["odd_nbox"] if s == d["odd_stream"] else d["nbox"], seed=s, resets=resets))
+    return _seeded(plans, next_seed)
+
+
+def dense_threshold(mot, oracle, to_dev, lib_path=None, next_seed=None):
+    """The default build's switch between track_update_kernel and track_update_dense_kernel (n_items < / >= MOT_UPDATE_DENSE_TRACKS = 24576, decided
+    on the device), crossed back and forth in one run of 512 streams x 64 track slots under AUTO: above, below, above, below, above, EXACTLY
+    24576 (the dense kernel's first count), above, 24575 (the plain kernel's last). An off-by-one in `n < lo || n >= hi` leaves every track of
+    such a frame without its update, or updates it twice. The planned n_items sequence is asserted from the oracles' own live counts."""
+    plans = dense_threshold_plans(next_seed or fixture_seeds("dense"))
+    d = DENSE_PLAN
+    always = [0, 127, 128, 199, 200, 349, 350, 351, 477, 478, 500, 511, 64, 300, 400, 490]
+    st = run_stream_plans(mot, oracle, to_dev, plans, d["frames"], lib_path=lib_path, slots=64, full_every=5, always=always)
+    assert st["n_items"] == DENSE_N_ITEMS, st["n_items"]
+    sides = [n >= DENSE_TRACKS for n in st["n_items"]]
+    assert sides == [False, False, True, True, False, False, True, True, False, False, True, True, True, True, False, True, True, True]
+    assert DENSE_TRACKS in st["n_items"] and DENSE_TRACKS - 1 in st["n_items"]
+    assert st["resets"] == 200 + 150 + 128 + 128
+    assert st["ill_conditioned_9m"] == 0 and st["ill_conditioned_2m"] == 0, st
+    assert st["max_rel_state_err"] <= SP.RTOL
+    assert st["state_compares"] >= 4 * 300 * 64 + 16 * 14 * 60, st["state_compares"]
+    assert st["records_compared"] >= 12 * 32767, st["records_compared"]
+    return st
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The same bits from the three instantiations of the step: the stream kernel (one launch), the four launches with the plain update, and the four
+# launches with the dense update. The source promises it ("Same arithmetic, same results (-ffp-contract=off: a spill changes no rounding)").
+
+class RecordingPkg:
+    """the package with every new Context put into one tracker launch mode (and, optionally, one library), every track_step / get_tracks / track_state
+    result appended to `log`: for bodies that create their own contexts"""
+
+    def __init__(self, mot, mode, log=None, lib_path=None):
+        self._mot, self._mode, self._log, self._lib = mot, mode, log, lib_path
+
+    def __getattr__(self, k):
+        return getattr(self._mot, k)
+
+    def Context(self, *a, **kw):
+        if self._lib:
+            kw["lib_path"] = self._lib
+        c = self._mot.Context(*a, **kw); c.set_tracker_mode(self._mode)
+        if self._log is not None:
+            for name in ("track_step", "get_tracks", "track_state"):
+                def wrap(fn):
+                    def call(*aa, **kk):
+                        r = fn(*aa, **kk); self._log.append(r); return r
+                    return call
+                setattr(c, name, wrap(getattr(c, name)))
+        return c
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint8)   # (NaN outputs of a diverged track must be the same NaNs)
+
+
+def assert_logs_bit_identical(la, lb, what):
+    """two RecordingPkg logs of the same calls: every output and every state key bit for bit, NaNs included"""
+    assert len(la) == len(lb) and len(la) > 0, (what, len(la), len(lb))
+    n_state = 0
+    for i, (ra, rb) in enumerate(zip(la, lb)):
+        assert ra.keys() == rb.keys(), (what, i)
+        for k in ra:
+            if k in ("capacity_exceeded",):
+                assert ra[k] == rb[k], (what, i, k)
+            else:
+                assert np.array_equal(_bits(np.asarray(ra[k])), _bits(np.asarray(rb[k]))), (what, i, k)
+        n_state += "x_merge" in ra
+    return n_state
+
+
+def launch_modes_identical(mot, oracle, to_dev, lib_path=None):
+    """mot_set_tracker_mode: the step as four launches (MOT_TRACKER_SPLIT: tracks of all streams dealt over the chip — what the 512-stream contexts run) and as
+    ONE launch with a workgroup per stream (MOT_TRACKER_STREAM: what contexts of few streams run) must give the same bits: same phases, same order per track,
+    kernel boundaries replaced by workgroup barriers. Random and degenerate sequences on three streams at once, then 40 live tracks per stream through the
+    batched device entry point (more than one round of 32 groups in the stream kernel) — that part also against the oracle, in both modes."""
+    import test_emu_tracker_random as TR
+    logs, many = {}, {}
+    for mode in (mot.MOT_TRACKER_SPLIT, mot.MOT_TRACKER_STREAM):
+        log = logs[mode] = []
+        pkg = RecordingPkg(mot, mode, log, lib_path)
+        with pkg.Context(max_points=1024, max_batch=3, max_tracks_total=256) as c:
+            seqs = [TR.sequence(70 + k, frames=20) if k < 2 else TR.hostile_sequence(5, frames=20) for k in range(3)]
+            for f in range(20):
+                for s in range(3):
+                    boxes, ts, v, yaw = seqs[s][f]
+                    c.ego_update(ts, v, yaw, s)
+                    tr = c.track_step(boxes, ts, s)
+                    for i in np.nonzero(tr["track_manage"] > 0)[0]:
+                        c.track_state(int(i), slot=s)
+        many[mode] = many_live_tracks(pkg, oracle, to_dev, streams=2, T=40, frames=14, spacing=9.0, min_live=40)
+    n_state = assert_logs_bit_identical(logs[mot.MOT_TRACKER_SPLIT], logs[mot.MOT_TRACKER_STREAM], "split vs stream")
+    assert n_state >= 2 * 12 * 40 + 100, n_state
+    assert many[mot.MOT_TRACKER_SPLIT]["max_rel_state_err"] == many[mot.MOT_TRACKER_STREAM]["max_rel_state_err"]
+    return dict(states_compared=n_state, calls=len(logs[mot.MOT_TRACKER_SPLIT]))
+
+
+def dense_variant_identical(mot, oracle, to_dev, lib_default, lib_dense4, golden, frames=30):
+    """A library built with -DMOT_UPDATE_DENSE_TRACKS=4 against the default one, both in MOT_TRACKER_SPLIT mode on the same inputs: in the variant every step with
+    >= 4 live tracks goes through track_update_dense_kernel (on the MI355X: the instantiation held to 3 waves per SIMD, which spills), in the default library
+    the plain kernel does all the work. The golden tracker sequences cross the threshold back and forth (checked against the fixtures' reference values at the bar),
+    the 64-live-track case sits far above it (checked against the oracle at the bar); all outputs and all states of the two libraries bit for bit."""
+    import golden_util as G
+    logs = {}
+    crossings = 0
+    for tag, lib in (("default", lib_default), ("dense4", lib_dense4)):
+        log = logs[tag] = []
+        pkg = RecordingPkg(mot, mot.MOT_TRACKER_SPLIT, log, lib)
+        for name in golden:
+            fx = G.load(name)
+            side = []
+            with pkg.Context(max_points=4096, max_tracks_total=256) as c:
+                for f in range(len(fx["n_boxes"])):
+                    ts = 1.0e9 + f * float(fx["unit"])
+                    c.ego_update(ts, *G.ego_of(fx, f))
+                    side.append(int((c.get_tracks(0)["track_manage"] != 0).sum()) >= 4 if f else False)   # the live list this step starts from
+                    out = c.track_step(fx["boxes"][f][: fx["n_boxes"][f]], ts)
+                    G.check_tracker_frame(fx, f, out, lambda i: c.track_state(i), rtol=SP.RTOL)
+            crossings += sum(1 for x, y in zip(side, side[1:]) if x != y) if tag == "dense4" else 0
+            assert tag != "dense4" or (True in side and False in side), (name, side)
+        many_live_tracks(pkg, oracle, to_dev, streams=4, T=64, frames=frames, spacing=9.0, min_live=64)   # (test_64_live_tracks_vs_oracle[9.0-64]'s case: streams and seed as there)
+    n_state = assert_logs_bit_identical(logs["default"], logs["dense4"], "default vs -DMOT_UPDATE_DENSE_TRACKS=4")
+    assert n_state >= 4 * 64 * (frames - 2), n_state
+    return dict(states_compared=n_state, calls=len(logs["default"]), threshold_crossings=crossings)
