@@ -18,6 +18,68 @@
 #include <string>
 #include <vector>
 
+// ---------------------------------------------------------------------------------------- what each slot holds
+// The one record of slot residency, and the only code that writes it: per slot the four facts of SlotState, per context the input description of the last batch
+// ("its compaction can be re-run"). What include/mot.h promises of mot_get_ground, mot_box_markers and mot_get_clusters is this table; tests/test_emu_slot_residency.py walks it.
+//   transition (callers)                                                          slots       packed       labels                        boxes  ground                        last_fused
+//   fused_batch (mot_frames_*, mot_sequence_dev)                                   0..batch-1  !OUT_GROUND  OUT_LABELS ? Ready : FromCells  yes    GROUND & MASK ? Resident : None  yes
+//   ground_stage (mot_ground_remove*, mot_ground_node_frame)                       0           no           FromPoints                    no     mask ? Resident : None        no
+//   slot0_taken (mot_cluster, _box_fit, _cluster_products_host, _cluster_node_frame)  0        no           FromPoints                    no     Foreign                       no
+//   labels_written (mot_get_clusters on demand, mot_cluster with labels)           one         -            Ready                         -      -                             -
+//   box_stage (mot_box_fit, _box_fit_resident, _cluster_node_frame once it fit)    one         -            Ready                         yes    -                             -
+//   compaction_rerun (mot_get_ground on demand, mot_time_stage)                    0..batch-1  as run       -                             -      as run, unless Foreign        -
+//   describe_batch (set_batch): the last_* input description. Nothing is vouched for in a slot at or beyond last_batch that needs the batch's input.
+// per-point labels: not computed, the cloud was uploaded by a stage-wise call (no cell codes: mot_get_clusters computes them from the points) / not computed, cloud and cell
+// codes come from the fused compaction kernel (... from the cells) / in d_label
+enum LabelState : char { kLabelsFromPoints, kLabelsFromCells, kLabelsReady };
+// d_ground / d_mask of the slot: not (both) resident, a fused batch's can be rebuilt (can_rebuild_ground) / hold the ground cloud and the mask that go with the slot's elevated cloud /
+// belong to ANOTHER cloud: a stage-wise cluster / box call has put its own elevated cloud into the slot since the ground stage ran
+enum GroundState : char { kGroundNone, kGroundResident, kGroundForeign };
+struct SlotState {
+  bool packed = false;                    // the elevated cloud is 12-byte points (the elevated-only compaction: mot_internal.h PackedXyz), not float4 records
+  LabelState labels = kLabelsFromPoints;
+  bool boxes = false;                     // the box stage's products (boxes, cluster order, groups) belong to the cloud now resident in the slot
+  GroundState ground = kGroundNone;
+};
+struct Residency {
+  std::vector<SlotState> slots;
+  bool last_fused = false;                // the last ground launch was a fused one (input, cells and thresholds of the batch still resident)
+  int last_batch = 0, last_max_n = 0;     // the last ground launch's geometry and input: what a re-run of its compaction needs
+  const float4* last_in = nullptr; long last_in_stride = 0;
+  void reset(int batch) { slots.assign(batch, SlotState()); }
+  void describe_batch(int batch, int max_n, const float4* in, long stride) { last_batch = batch; last_max_n = max_n; last_in = in; last_in_stride = stride; }
+  static bool fused_packs(int outputs) { return MOT_PACKED_ELEVATED && !(outputs & MOT_OUT_GROUND); }   // the elevated-only compaction leaves 12-byte points
+  static bool fused_keeps_ground(int outputs) { return (outputs & (MOT_OUT_GROUND | MOT_OUT_MASK)) == (MOT_OUT_GROUND | MOT_OUT_MASK); }
+  // a fused call over slots 0..batch-1 was issued: what those slots hold from now on (the slots beyond keep what an earlier, larger batch left). Host
+  // state, so it also holds when a captured graph is replayed: every reader built from cluster_buffers afterwards is told the layout
+  void fused_batch(int batch, int outputs) {
+    last_fused = true;
+    for (int b = 0; b < batch; b++) slots[b] = {fused_packs(outputs), (outputs & MOT_OUT_LABELS) ? kLabelsReady : kLabelsFromCells, true, fused_keeps_ground(outputs) ? kGroundResident : kGroundNone};
+  }
+  // a stage-wise ground stage ran on slot 0 (float4 records); without a mask a later mot_get_ground that asks for one answers MOT_E_STATE
+  void ground_stage(bool with_mask) { last_fused = false; slots[0] = {false, kLabelsFromPoints, false, with_mask ? kGroundResident : kGroundNone}; }
+  // slot 0 now holds a stage-wise cluster / box call's cloud, as float4 records: mot_get_ground must not re-run a fused batch's compaction over it, slot 0's ground cloud / mask (if any) are another
+  // cloud's (mot_get_ground(0) answers MOT_E_STATE, as include/mot.h promises), what an earlier label kernel or box stage left is stale (mot_box_markers: MOT_E_STATE). The caller then states what it produced.
+  void slot0_taken() { last_fused = false; slots[0] = {false, kLabelsFromPoints, false, kGroundForeign}; }
+  // the label kernel ran on the slot's cloud; written = false: in the fused geometry without per-point labels (mot_time_stage)
+  void labels_written(int slot, bool written = true) { slots[slot].labels = written ? kLabelsReady : kLabelsFromCells; }
+  // the box stage (label kernel included) ran on the slot's cloud: mot_box_markers / mot_get_boxes / mot_get_clusters may read its products
+  void box_stage(int slot) { slots[slot].labels = kLabelsReady; slots[slot].boxes = true; }
+  // the compaction of the last batch was run again: same points in the same order (what the later stages hold stays valid), in the layout and with the outputs
+  // of this run. (A slot a stage-wise call has taken since stays refused: only mot_time_stage gets here in that state.)
+  void compaction_rerun(int batch, bool packed, bool ground_and_mask) {
+    for (int b = 0; b < batch; b++) { slots[b].packed = packed; if (slots[b].ground != kGroundForeign) slots[b].ground = ground_and_mask ? kGroundResident : kGroundNone; }
+  }
+  bool elev_packed_at(int slot) const { return slots[slot].packed; }
+  bool labels_ready(int slot) const { return slots[slot].labels == kLabelsReady; }
+  bool cells_usable(int slot) const { return slots[slot].labels == kLabelsFromCells; }
+  bool boxes_valid(int slot) const { return slots[slot].boxes; }
+  bool ground_foreign(int slot) const { return slots[slot].ground == kGroundForeign; }
+  // (a slot beyond the last batch: whatever an earlier batch left is not vouched for)
+  bool ground_readable(int slot) const { return slots[slot].ground == kGroundResident && slot < last_batch; }
+  bool can_rebuild_ground(int slot) const { return last_fused && last_in && last_batch >= 1 && slot < last_batch; }
+};
+
 struct mot_ctx {
   mot_params params;
   MotDevParams dp;
@@ -134,21 +196,9 @@ struct mot_ctx {
   std::vector<int> h_n;
   unsigned short* d_ecell = nullptr;   // Cartesian cell of every elevated point (fused path: compaction kernel -> label kernel)
   int fused_outputs = 0;               // MOT_OUT_* the fused entry points materialise besides what the next stage needs
-  // per-point cluster labels of a slot: 1 = in d_label; 0 = not computed, the slot's cloud and cells come from the fused compaction kernel;
-  // 2 = not computed, the slot's cloud was uploaded by a stage-wise call (no cells). mot_get_clusters computes them on demand.
-  std::vector<char> label_state;
-  bool elev_packed = false;           // the last fused batch left its elevated clouds as 12-byte points (the elevated-only compaction: mot_internal.h PackedXyz) ...
-  std::vector<char> slot_packed;      // ... and what each SLOT holds now: a fused call writes the slots of its batch, a stage-wise call float4 records into slot 0 only
-  std::vector<char> box_valid;        // per slot: the box stage's products (boxes, cluster order, groups) belong to the cloud now resident in the slot
-  bool ground_resident = false;        // d_ground / d_mask hold the last batch's ground cloud and mask
-  bool ground_all = false;             // ... of every slot of the last fused batch; false: of slot 0 only (a stage-wise mot_ground_remove* since)
+  Residency res;                       // what each slot holds (above)
   int dbg_skip = 0;                    // mot_debug_skip_kernels: MEASUREMENT ONLY (upper bounds of launch-fusion experiments); the results of a frame are then stale
-  bool ground_foreign0 = false;        // a stage-wise cluster / box call has replaced slot 0's elevated cloud since the ground stage ran: d_ground / d_mask of slot 0 belong to ANOTHER cloud
-  bool last_fused = false;             // the last ground launch was a fused one (input, cells and thresholds of the batch still resident)
   int* h_counts = nullptr;  // pinned [batch][4]
-  int last_batch = 0, last_max_n = 0;
-  const float4* last_in = nullptr;
-  long last_in_stride = 0;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   // pipelined host ingest (mot_frames_host): a copy stream and two staging copies of the input batch
   hipStream_t copy_stream = nullptr;
@@ -341,20 +391,10 @@ static int arg_block_commit(mot_ctx* c, size_t off, size_t bytes) {
   return MOT_OK;
 }
 
-// layout of the elevated cloud resident in `slot`
-static bool elev_packed_at(const mot_ctx* c, int slot) { return c->slot_packed[slot] != 0; }
-// a fused call over slots 0..batch-1 was issued: what those slots hold from now on (the slots beyond keep what an earlier, larger batch left)
-static void mark_fused_slots(mot_ctx* c, int batch, bool want_ground, bool want_mask) {
-  c->ground_resident = want_ground && want_mask; c->ground_all = true; c->last_fused = true; c->ground_foreign0 = false;
-  c->elev_packed = MOT_PACKED_ELEVATED && !want_ground;   // how this call's compaction kernel leaves the elevated clouds (host state: also on a graph replay)
-  for (int b = 0; b < batch; b++) {
-    c->label_state[b] = (c->fused_outputs & MOT_OUT_LABELS) ? 1 : 0; c->box_valid[b] = 1; c->slot_packed[b] = c->elev_packed ? 1 : 0;
-  }
-}
-// slot < 0: a launch over the whole fused batch just issued; otherwise the slot a single-frame launch works on
+// slot < 0: a launch over the whole fused batch just issued (every slot of it has slot 0's layout); otherwise the slot a single-frame launch works on
 static ClusterBuffers cluster_buffers(mot_ctx* c, int slot = -1) {
   ClusterBuffers b;
-  b.elevated = c->d_elev; b.elevated_packed = (slot < 0 ? c->elev_packed : elev_packed_at(c, slot)) ? 1 : 0; b.cap = c->cap; b.counts = c->d_counts; b.plane_a = c->d_plane_a; b.plane_b = c->d_plane_b; b.ccl_parent = c->d_ccl_parent;
+  b.elevated = c->d_elev; b.elevated_packed = c->res.elev_packed_at(slot < 0 ? 0 : slot) ? 1 : 0; b.cap = c->cap; b.counts = c->d_counts; b.plane_a = c->d_plane_a; b.plane_b = c->d_plane_b; b.ccl_parent = c->d_ccl_parent;
   b.occ_list = nullptr; b.occ_count = nullptr; b.n_in = c->d_n; b.occ_chunks = c->occ_chunks;   // the fused path points these at the compaction kernel's lists
   b.grid = c->d_grid; b.label = c->d_label; b.stats = c->d_stats; b.cand = c->d_cand; b.boxes = c->d_boxes;
   b.box_cluster = c->d_box_cluster; b.rng = c->d_rng; b.poly = c->d_poly; b.groups = c->d_groups; b.group_cap = c->cap / 2; b.cluster_start = c->d_cluster_start; b.cluster_gstart = c->d_cluster_gstart; b.order = c->d_order; b.gsorted = c->d_gsorted;
@@ -368,6 +408,7 @@ static int create_impl(mot_ctx* c) {
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(c, MOT_E_HIP, "no HIP device: this library has no CPU fallback");
   if (c->device < 0 || c->device >= ndev) return fail(c, MOT_E_ARG, "device ordinal out of range");
   MOT_HIP(c, hipSetDevice(c->device));   // mot_create restores the caller's device (DevGuard)
+  c->res.reset(c->batch);
   {
     hipDeviceProp_t prop;
     MOT_HIP(c, hipGetDeviceProperties(&prop, c->device));
@@ -480,9 +521,6 @@ static int create_impl(mot_ctx* c) {
   MOT_HIP(c, hipMemsetAsync(c->d_desc, 0, B * c->max_chunks * sizeof(unsigned long long), c->stream));
   MOT_HIP(c, hipStreamSynchronize(c->stream));
   c->h_n.assign(B, 0);
-  c->label_state.assign(B, 2);
-  c->box_valid.assign(B, 0);
-  c->slot_packed.assign(B, 0);
   return MOT_OK;
 }
 
@@ -581,7 +619,7 @@ static int set_batch(mot_ctx* c, const int* n_points, int batch, const float4* i
     memcpy(blk, c->h_n.data(), batch * sizeof(int));
     if ((rc = arg_block_commit(c, 0, batch * sizeof(int)))) return rc;
   }
-  c->last_batch = batch; c->last_max_n = max_n; c->last_in = in; c->last_in_stride = stride;
+  c->res.describe_batch(batch, max_n, in, stride);
   return MOT_OK;
 }
 
@@ -709,12 +747,21 @@ RangeScope::RangeScope(const mot_ctx* c, const char* name) : on(false) {
   if (g_roctx.push) { (void)g_roctx.push(name); on = true; }
 }
 
-static void issue_frame_kernels(mot_ctx* c, int batch, int max_n, int run_tracker, bool want_ground, bool want_mask, bool from_block) {
-  GroundBuffers g = ground_buffers(c, c->last_in, c->last_in_stride, want_mask, true);
-  if (!want_ground) g.ground = nullptr;   // the ground cloud on demand (mot_get_ground re-runs the compaction)
-  // (the elevated-only compaction leaves 12-byte points; c->elev_packed was set by the CALLER — launch_frames / mot_sequence_dev, which also run
-  // when a captured graph is replayed and this function is not — so that every reader built from cluster_buffers below is told)
-  g.elevated_packed = (MOT_PACKED_ELEVATED && !want_ground) ? 1 : 0;
+// the buffer sets of a launch in the fused geometry: the compaction kernel leaves the occupancy as per-chunk lists and every elevated point's cell for the label kernel; the ground cloud, the mask and the
+// per-point labels only where mot_set_fused_outputs asks for them (on demand otherwise: mot_get_ground, mot_get_clusters). The readers' layout (cluster_buffers) comes from the residency record, which the
+// CALLERS of issue_frame_kernels set: they also run when a captured graph is replayed and issue_frame_kernels is not.
+static void fused_buffers(mot_ctx* c, GroundBuffers* g, ClusterBuffers* cb) {
+  *g = ground_buffers(c, c->res.last_in, c->res.last_in_stride, (c->fused_outputs & MOT_OUT_MASK) != 0, true);
+  if (!(c->fused_outputs & MOT_OUT_GROUND)) g->ground = nullptr;
+  g->elevated_packed = Residency::fused_packs(c->fused_outputs) ? 1 : 0;
+  *cb = cluster_buffers(c);
+  cb->occ_list = c->d_occ_list; cb->occ_count = c->d_occ_count; cb->ecell = g->ecell;
+  if (!(c->fused_outputs & MOT_OUT_LABELS)) cb->label = nullptr;
+}
+
+static void issue_frame_kernels(mot_ctx* c, int batch, int max_n, int run_tracker, bool from_block) {
+  GroundBuffers g; ClusterBuffers cb;
+  fused_buffers(c, &g, &cb);
   if (from_block) g.launch = reinterpret_cast<const FrameLaunch*>(c->d_argblk + c->arg_off_launch);
   {
     RangeScope rs(c, "mot:ground");
@@ -722,10 +769,6 @@ static void issue_frame_kernels(mot_ctx* c, int batch, int max_n, int run_tracke
     if (!(c->dbg_skip & 1)) { ProfScope ps(c, kK2); mot_launch_ground_kernel(1, c->dp, g, batch, max_n, c->stream); }
     { ProfScope ps(c, kK3); mot_launch_ground_kernel(2, c->dp, g, batch, max_n, c->stream); }
   }
-  ClusterBuffers cb = cluster_buffers(c);
-  cb.occ_list = c->d_occ_list; cb.occ_count = c->d_occ_count;   // the occupancy comes as the compaction kernel's per-chunk lists
-  cb.ecell = g.ecell;                                            // ... and every elevated point's cell with it
-  if (!(c->fused_outputs & MOT_OUT_LABELS)) cb.label = nullptr;  // per-point labels on demand (mot_get_clusters)
   // MEASUREMENT ONLY (mot_debug_skip_kernels bits 8-11: a count): that many EXTRA launch boundaries — empty one-workgroup-per-frame kernels — in the middle of the
   // sequence. What k more boundaries cost is what fusing k of the sequence's one-workgroup-per-frame launches away could at most win (profiles/r06_launch_boundaries.md).
   for (int k = 0; k < ((c->dbg_skip >> 8) & 15); k++) mot_launch_noop(batch, c->stream);
@@ -745,31 +788,37 @@ static void issue_frame_kernels(mot_ctx* c, int batch, int max_n, int run_tracke
   }
 }
 
+// Every per-batch argument in ONE copy at the head of a fused sequence: n[], and for the tracker the tracking node's per-frame host work
+// (OT/tracking/main.cpp:72-166): ego pose, the tf chain's matrix, dt / first-frame flags. one_stream (mot_sequence_dev): entry k is FRAME k of
+// stream 0 — its ego pose advanced frame by frame on the host (slot 0's dead reckoning) — instead of stream k's frame.
+static int send_frame_args(mot_ctx* c, int batch, int run_tracker, bool one_stream, const double* timestamps, const double* ego_v, const double* ego_yaw) {
+  int rc; char* blk;
+  if ((rc = arg_block_acquire(c, &blk))) return rc;
+  memcpy(blk, c->h_n.data(), batch * sizeof(int));
+  TrackFrameArgs* targs = reinterpret_cast<TrackFrameArgs*>(blk + c->arg_off_targs);
+  EgoTf* ego = reinterpret_cast<EgoTf*>(blk + c->arg_off_ego);
+  for (int b = 0; b < c->batch; b++) targs[b].run = 0;
+  if (run_tracker)
+    for (int b = 0; b < batch; b++) {
+      const int s = one_stream ? 0 : b;   // the stream whose ego / tracker state entry b advances
+      if ((rc = mot_ego_update(c, s, timestamps[b], ego_v[b], ego_yaw[b], nullptr))) return rc;
+      tf_velodyne_to_global(c->ego[s].egoPoint[0], c->ego[s].egoPoint[1], c->ego[s].egoPoint[2], ego[b].m);
+      TrackFrameArgs one[1];
+      prepare_track_args(c, one_stream ? one : targs, s, 0, timestamps[b], true);   // (fills entry s of the array it is given)
+      if (one_stream) targs[b] = one[0];
+    }
+  FrameLaunch* fl = reinterpret_cast<FrameLaunch*>(blk + c->arg_off_launch);
+  fl->in = c->res.last_in; fl->in_stride = c->res.last_in_stride; fl->epoch = c->epoch; fl->pad = 0;
+  return arg_block_commit(c, 0, (run_tracker || c->graph_mode) ? c->arg_bytes : batch * sizeof(int));
+}
+
 // the fused launch sequence of one batch on the context stream; every argument has been validated
 static int launch_frames(mot_ctx* c, int batch, int run_tracker, const double* timestamps, const double* ego_v, const double* ego_yaw) {
   int rc;
   if ((rc = next_epoch(c))) return rc;
-  const int max_n = c->last_max_n;
-  {  // every per-batch argument in ONE copy at the head of the sequence: n[], and for the tracker the tracking node's per-frame
-     // host work (OT/tracking/main.cpp:72-166): ego pose, the tf chain's matrix, dt / first-frame flags
-    char* blk;
-    if ((rc = arg_block_acquire(c, &blk))) return rc;
-    memcpy(blk, c->h_n.data(), batch * sizeof(int));
-    TrackFrameArgs* targs = reinterpret_cast<TrackFrameArgs*>(blk + c->arg_off_targs);
-    EgoTf* ego = reinterpret_cast<EgoTf*>(blk + c->arg_off_ego);
-    for (int b = 0; b < c->batch; b++) targs[b].run = 0;
-    if (run_tracker)
-      for (int b = 0; b < batch; b++) {
-        if ((rc = mot_ego_update(c, b, timestamps[b], ego_v[b], ego_yaw[b], nullptr))) return rc;
-        tf_velodyne_to_global(c->ego[b].egoPoint[0], c->ego[b].egoPoint[1], c->ego[b].egoPoint[2], ego[b].m);
-        prepare_track_args(c, targs, b, 0, timestamps[b], true);
-      }
-    FrameLaunch* fl = reinterpret_cast<FrameLaunch*>(blk + c->arg_off_launch);
-    fl->in = c->last_in; fl->in_stride = c->last_in_stride; fl->epoch = c->epoch; fl->pad = 0;
-    if ((rc = arg_block_commit(c, 0, (run_tracker || c->graph_mode) ? c->arg_bytes : batch * sizeof(int)))) return rc;
-  }
-  const bool want_ground = (c->fused_outputs & MOT_OUT_GROUND) != 0, want_mask = (c->fused_outputs & MOT_OUT_MASK) != 0;
-  mark_fused_slots(c, batch, want_ground, want_mask);
+  const int max_n = c->res.last_max_n;
+  if ((rc = send_frame_args(c, batch, run_tracker, false, timestamps, ego_v, ego_yaw))) return rc;
+  c->res.fused_batch(batch, c->fused_outputs);
 #ifndef MOT_HIPEMU
   // Few streams per launch = somebody waits for every frame: the sequence's 10-13 launches go out as ONE hipGraph launch, captured
   // once per launch geometry. What differs from call to call without changing the geometry (the cloud's address, the look-back
@@ -784,7 +833,7 @@ static int launch_frames(mot_ctx* c, int batch, int run_tracker, const double* t
       hipGraphExec_t ge = nullptr;
       bool ok = hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
       if (ok) {
-        issue_frame_kernels(c, batch, key.chunks * kGroundChunk, run_tracker, want_ground, want_mask, true);   // (grids from the chunk count: any frame of this geometry)
+        issue_frame_kernels(c, batch, key.chunks * kGroundChunk, run_tracker, true);   // (grids from the chunk count: any frame of this geometry)
         ok = hipStreamEndCapture(c->stream, &graph) == hipSuccess && graph != nullptr;
       }
       if (ok) ok = hipGraphInstantiate(&ge, graph, nullptr, nullptr, 0) == hipSuccess;
@@ -799,7 +848,7 @@ static int launch_frames(mot_ctx* c, int batch, int run_tracker, const double* t
     }
   }
 #endif
-  issue_frame_kernels(c, batch, max_n, run_tracker, want_ground, want_mask, false);
+  issue_frame_kernels(c, batch, max_n, run_tracker, false);
   MOT_HIP(c, hipGetLastError());
   return MOT_OK;
 }
@@ -840,29 +889,10 @@ extern "C" int mot_sequence_dev(mot_ctx* c, const float* d_xyzw, long frame_stri
   if ((d_tracks != nullptr) != (d_counts != nullptr) || (d_tracks && max_per_frame < 1)) return fail(c, MOT_E_ARG, "mot_sequence_dev: d_tracks and d_counts go together, max_per_frame >= 1");
   if ((rc = set_batch(c, n_points, frames, (const float4*)d_xyzw, frame_stride / 4, false))) return rc;
   if ((rc = next_epoch(c))) return rc;
-  const int K = frames, max_n = c->last_max_n;
-  {  // one argument block for the whole sequence: n[k], and per FRAME what the tracking node computes per callback (main.cpp:72-166) —
-     // the ego pose advanced frame by frame on the host (slot 0's dead reckoning), its tf matrix, dt / first-frame flag
-    char* blk;
-    if ((rc = arg_block_acquire(c, &blk))) return rc;
-    memcpy(blk, c->h_n.data(), K * sizeof(int));
-    TrackFrameArgs* targs = reinterpret_cast<TrackFrameArgs*>(blk + c->arg_off_targs);
-    EgoTf* ego = reinterpret_cast<EgoTf*>(blk + c->arg_off_ego);
-    for (int b = 0; b < c->batch; b++) targs[b].run = 0;
-    TrackFrameArgs one[1];
-    for (int k = 0; k < K; k++) {
-      if ((rc = mot_ego_update(c, 0, timestamps[k], ego_v[k], ego_yaw[k], nullptr))) return rc;
-      tf_velodyne_to_global(c->ego[0].egoPoint[0], c->ego[0].egoPoint[1], c->ego[0].egoPoint[2], ego[k].m);
-      prepare_track_args(c, one, 0, 0, timestamps[k], true);
-      targs[k] = one[0];
-    }
-    FrameLaunch* fl = reinterpret_cast<FrameLaunch*>(blk + c->arg_off_launch);
-    fl->in = c->last_in; fl->in_stride = c->last_in_stride; fl->epoch = c->epoch; fl->pad = 0;
-    if ((rc = arg_block_commit(c, 0, c->arg_bytes))) return rc;
-  }
-  const bool want_ground = (c->fused_outputs & MOT_OUT_GROUND) != 0, want_mask = (c->fused_outputs & MOT_OUT_MASK) != 0;
-  mark_fused_slots(c, K, want_ground, want_mask);
-  issue_frame_kernels(c, K, max_n, 0, want_ground, want_mask, false);   // slots = frames; ends with the plain box_finalize_kernel
+  const int K = frames, max_n = c->res.last_max_n;
+  if ((rc = send_frame_args(c, K, 1, true, timestamps, ego_v, ego_yaw))) return rc;   // one argument block for the whole sequence
+  c->res.fused_batch(K, c->fused_outputs);
+  issue_frame_kernels(c, K, max_n, 0, false);   // slots = frames; ends with the plain box_finalize_kernel
   const TrackBuffers base = track_buffers(c, true);
   RangeScope rt(c, "mot:tracker (sequence)");
   for (int k = 0; k < K; k++) {   // the per-frame inputs of step k live in slot k, the track state in slot 0
@@ -890,6 +920,55 @@ static int ensure_copy_path(mot_ctx* c) {
   return MOT_OK;
 }
 
+// what the pipelined host-ingest calls with one strided host block check of batch and n_points[]; *max_n: the largest frame
+static int check_host_batch(mot_ctx* c, const int* n_points, int batch, long stride_points, int* max_n) {
+  if (batch < 1 || batch > c->batch) return fail(c, MOT_E_ARG, "batch out of range");
+  *max_n = 0;
+  for (int b = 0; b < batch; b++) {
+    if (n_points[b] < 0) return fail(c, MOT_E_ARG, "negative point count");
+    if (n_points[b] > c->max_points) return fail(c, MOT_E_CAPACITY, "frame has more points than max_points");
+    if (batch > 1 && stride_points < n_points[b]) return fail(c, MOT_E_ARG, "frame_stride is smaller than a frame");
+    if (n_points[b] > *max_n) *max_n = n_points[b];
+  }
+  return MOT_OK;
+}
+// the next staging parity; the copy stream waits for the last reader of where the copies go: d_stage[s]'s last compaction kernel, or a landing buffer's (12-byte / raw records) last unpacking kernel
+static int next_stage(mot_ctx* c, bool landing, int* s_out) {
+  const int s = *s_out = c->stage_next;
+  c->stage_next ^= 1;
+  if (landing ? c->stage12_used[s] : c->stage_used[s]) MOT_HIP(c, hipStreamWaitEvent(c->copy_stream, landing ? c->ev_expanded[s] : c->ev_consumed[s], 0));
+  return MOT_OK;
+}
+// the copies of parity s are queued: the compute stream waits for them
+static int stage_copied(mot_ctx* c, int s) {
+  MOT_HIP(c, hipEventRecord(c->ev_copied[s], c->copy_stream));
+  MOT_HIP(c, hipStreamWaitEvent(c->stream, c->ev_copied[s], 0));
+  return MOT_OK;
+}
+// host frames of w floats a point -> a staging buffer at its stride of cap points (frames already at that stride: one copy for the whole batch)
+static int copy_frames(mot_ctx* c, int s, float* dst, const float* src, long frame_stride, int w, const int* n_points, int batch) {
+  const size_t cap_w = (size_t)c->cap * w;
+  if ((size_t)frame_stride == cap_w) {
+    const size_t bytes = ((size_t)(batch - 1) * cap_w + (size_t)n_points[batch - 1] * w) * sizeof(float);
+    if (bytes) MOT_HIP(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->copy_stream));
+  } else {
+    for (int b = 0; b < batch; b++)
+      if (n_points[b] > 0)
+        MOT_HIP(c, hipMemcpyAsync(dst + (size_t)b * cap_w, src + (size_t)b * frame_stride, (size_t)n_points[b] * w * sizeof(float), hipMemcpyHostToDevice, c->copy_stream));
+  }
+  return stage_copied(c, s);
+}
+// the fused sequence on the batch staged in d_stage[s]
+static int launch_staged(mot_ctx* c, int s, const int* n_points, int batch, int run_tracker, const double* timestamps, const double* ego_v, const double* ego_yaw) {
+  int rc;
+  if ((rc = set_batch(c, n_points, batch, c->d_stage[s], c->cap, false))) return rc;
+  rc = launch_frames(c, batch, run_tracker, timestamps, ego_v, ego_yaw);
+  // (recorded after the whole sequence: the input is last read by the compaction kernel, but mot_time_stage may re-read it)
+  MOT_HIP(c, hipEventRecord(c->ev_consumed[s], c->stream));
+  c->stage_used[s] = true;
+  return rc;
+}
+
 // One sensor frame per slot from HOST memory (what the reference's nodes receive per message: OT/src/groundremove/main.cpp:91-136,
 // OT0/src/main.cpp:51-95), pipelined: the H2D copy of this batch runs on the context's copy stream into one of two staging
 // buffers while the kernels of the previous batch run on the compute stream. Returns as soon as everything is queued.
@@ -899,35 +978,12 @@ extern "C" int mot_frames_host(mot_ctx* c, const float* h_xyzw, long frame_strid
   MOT_GUARD(c);
   int rc = check_frames_args(c, h_xyzw, frame_stride, n_points, batch, run_tracker, timestamps, ego_v, ego_yaw);
   if (rc) return rc;
-  if (batch < 1 || batch > c->batch) return fail(c, MOT_E_ARG, "batch out of range");
-  for (int b = 0; b < batch; b++) {
-    if (n_points[b] < 0) return fail(c, MOT_E_ARG, "negative point count");
-    if (n_points[b] > c->max_points) return fail(c, MOT_E_CAPACITY, "frame has more points than max_points");
-    if (batch > 1 && frame_stride / 4 < n_points[b]) return fail(c, MOT_E_ARG, "frame_stride is smaller than a frame");
-  }
+  int max_n, s;
+  if ((rc = check_host_batch(c, n_points, batch, frame_stride / 4, &max_n))) return rc;
   if ((rc = ensure_copy_path(c))) return rc;
-  const int s = c->stage_next;
-  c->stage_next ^= 1;
-  // the staging buffer is free once the compaction kernel of the batch that used it last has run
-  if (c->stage_used[s]) MOT_HIP(c, hipStreamWaitEvent(c->copy_stream, c->ev_consumed[s], 0));
-  const bool dense = frame_stride / 4 == c->cap;   // host frames already at the staging stride: one copy for the whole batch
-  if (dense) {
-    size_t bytes = ((size_t)(batch - 1) * c->cap + (size_t)n_points[batch - 1]) * sizeof(float4);
-    if (bytes) MOT_HIP(c, hipMemcpyAsync(c->d_stage[s], h_xyzw, bytes, hipMemcpyHostToDevice, c->copy_stream));
-  } else {
-    for (int b = 0; b < batch; b++)
-      if (n_points[b] > 0)
-        MOT_HIP(c, hipMemcpyAsync(c->d_stage[s] + (size_t)b * c->cap, h_xyzw + (size_t)b * frame_stride, (size_t)n_points[b] * sizeof(float4),
-                                  hipMemcpyHostToDevice, c->copy_stream));
-  }
-  MOT_HIP(c, hipEventRecord(c->ev_copied[s], c->copy_stream));
-  MOT_HIP(c, hipStreamWaitEvent(c->stream, c->ev_copied[s], 0));
-  if ((rc = set_batch(c, n_points, batch, c->d_stage[s], c->cap, false))) return rc;
-  rc = launch_frames(c, batch, run_tracker, timestamps, ego_v, ego_yaw);
-  // (recorded after the whole sequence: the input is last read by the compaction kernel, but mot_time_stage may re-read it)
-  MOT_HIP(c, hipEventRecord(c->ev_consumed[s], c->stream));
-  c->stage_used[s] = true;
-  return rc;
+  if ((rc = next_stage(c, false, &s))) return rc;
+  if ((rc = copy_frames(c, s, reinterpret_cast<float*>(c->d_stage[s]), h_xyzw, frame_stride, 4, n_points, batch))) return rc;
+  return launch_staged(c, s, n_points, batch, run_tracker, timestamps, ego_v, ego_yaw);
 }
 
 // mot_frames_host for clouds WITHOUT a 4th value: packed {x, y, z} records, 12 bytes a point (include/mot.h). pcl::PointXYZ has no 4th value (its
@@ -942,45 +998,20 @@ extern "C" int mot_frames_host_xyz(mot_ctx* c, const float* h_xyz, long frame_st
   if (!h_xyz || !n_points) return fail(c, MOT_E_ARG, "null cloud or point-count pointer");
   if (frame_stride < 0 || ((size_t)h_xyz & 3) != 0) return fail(c, MOT_E_ARG, "mot_frames_host_xyz: frame_stride (floats) must be non-negative, the cloud 4-byte aligned");
   if (run_tracker && (!timestamps || !ego_v || !ego_yaw)) return fail(c, MOT_E_ARG, "run_tracker needs timestamps, ego_v and ego_yaw");
-  if (batch < 1 || batch > c->batch) return fail(c, MOT_E_ARG, "batch out of range");
-  int max_n = 0;
-  for (int b = 0; b < batch; b++) {
-    if (n_points[b] < 0) return fail(c, MOT_E_ARG, "negative point count");
-    if (n_points[b] > c->max_points) return fail(c, MOT_E_CAPACITY, "frame has more points than max_points");
-    if (batch > 1 && frame_stride / 3 < n_points[b]) return fail(c, MOT_E_ARG, "frame_stride is smaller than a frame");
-    if (n_points[b] > max_n) max_n = n_points[b];
-  }
-  int rc;
+  int rc, max_n, s;
+  if ((rc = check_host_batch(c, n_points, batch, frame_stride / 3, &max_n))) return rc;
   if ((rc = ensure_copy_path(c))) return rc;
   for (int i = 0; i < 2; i++) {
     if (!c->d_stage12[i]) MOT_HIP(c, hipMalloc(&c->d_stage12[i], (size_t)c->batch * c->cap * 3 * sizeof(float)));
     if (!c->ev_expanded[i]) MOT_HIP(c, hipEventCreateWithFlags(&c->ev_expanded[i], hipEventDisableTiming));
   }
-  const int s = c->stage_next;
-  c->stage_next ^= 1;
-  if (c->stage12_used[s]) MOT_HIP(c, hipStreamWaitEvent(c->copy_stream, c->ev_expanded[s], 0));   // the landing buffer is free once its last expansion has run
-  const size_t cap3 = (size_t)c->cap * 3;
-  if ((size_t)frame_stride == cap3) {   // host frames already at the staging stride: one copy for the whole batch
-    const size_t bytes = ((size_t)(batch - 1) * cap3 + (size_t)n_points[batch - 1] * 3) * sizeof(float);
-    if (bytes) MOT_HIP(c, hipMemcpyAsync(c->d_stage12[s], h_xyz, bytes, hipMemcpyHostToDevice, c->copy_stream));
-  } else {
-    for (int b = 0; b < batch; b++)
-      if (n_points[b] > 0)
-        MOT_HIP(c, hipMemcpyAsync(c->d_stage12[s] + (size_t)b * cap3, h_xyz + (size_t)b * frame_stride, (size_t)n_points[b] * 3 * sizeof(float),
-                                  hipMemcpyHostToDevice, c->copy_stream));
-  }
-  MOT_HIP(c, hipEventRecord(c->ev_copied[s], c->copy_stream));
-  MOT_HIP(c, hipStreamWaitEvent(c->stream, c->ev_copied[s], 0));
-  // (d_stage[s] was last read by the batch before the previous one, on this same stream: ordered)
-  mot_launch_expand_xyz12(c->d_stage12[s], (long)cap3, c->d_stage[s], c->cap, batch, max_n, c->stream);
-  MOT_HIP(c, hipGetLastError());
+  if ((rc = next_stage(c, true, &s))) return rc;
+  if ((rc = copy_frames(c, s, c->d_stage12[s], h_xyz, frame_stride, 3, n_points, batch))) return rc;
+  mot_launch_expand_xyz12(c->d_stage12[s], (long)c->cap * 3, c->d_stage[s], c->cap, batch, max_n, c->stream);
+  MOT_HIP(c, hipGetLastError());   // (d_stage[s] was last read two batches ago, on this same stream: ordered)
   MOT_HIP(c, hipEventRecord(c->ev_expanded[s], c->stream));
   c->stage12_used[s] = true;
-  if ((rc = set_batch(c, n_points, batch, c->d_stage[s], c->cap, false))) return rc;
-  rc = launch_frames(c, batch, run_tracker, timestamps, ego_v, ego_yaw);
-  MOT_HIP(c, hipEventRecord(c->ev_consumed[s], c->stream));
-  c->stage_used[s] = true;
-  return rc;
+  return launch_staged(c, s, n_points, batch, run_tracker, timestamps, ego_v, ego_yaw);
 }
 
 // mot_frames_host for sensor_msgs/PointCloud2 payloads as they arrive — one message per sensor stream, each in its own host buffer (include/mot.h): what a
@@ -1017,23 +1048,17 @@ extern "C" int mot_frames_host_pointcloud2(mot_ctx* c, const void* const* h_payl
     c->stage_raw_bytes = need;
   }
   for (int i = 0; i < 2; i++) if (!c->ev_expanded[i]) MOT_HIP(c, hipEventCreateWithFlags(&c->ev_expanded[i], hipEventDisableTiming));
-  const int s = c->stage_next;
-  c->stage_next ^= 1;
-  if (c->stage12_used[s]) MOT_HIP(c, hipStreamWaitEvent(c->copy_stream, c->ev_expanded[s], 0));   // (shared with the 12-byte path: "the landing buffer of parity s has been unpacked")
+  int s;
+  if ((rc = next_stage(c, true, &s))) return rc;   // (shared with the 12-byte path: "the landing buffer of parity s has been unpacked")
   for (int b = 0; b < batch; b++)
     if (n_points[b] > 0)
       MOT_HIP(c, hipMemcpyAsync(c->d_stage_raw[s] + (size_t)b * slot_bytes, h_payloads[b], (size_t)n_points[b] * (size_t)point_step, hipMemcpyHostToDevice, c->copy_stream));
-  MOT_HIP(c, hipEventRecord(c->ev_copied[s], c->copy_stream));
-  MOT_HIP(c, hipStreamWaitEvent(c->stream, c->ev_copied[s], 0));
+  if ((rc = stage_copied(c, s))) return rc;
   mot_launch_decode_pointcloud2_batch(c->d_stage_raw[s], (long)slot_bytes, batch, max_n, point_step, off_x, off_y, off_z, off_w, c->d_stage[s], c->cap, c->stream);
-  MOT_HIP(c, hipGetLastError());
+  MOT_HIP(c, hipGetLastError());   // (d_stage[s] was last read two batches ago, on this same stream: ordered)
   MOT_HIP(c, hipEventRecord(c->ev_expanded[s], c->stream));
   c->stage12_used[s] = true;
-  if ((rc = set_batch(c, n_points, batch, c->d_stage[s], c->cap, false))) return rc;
-  rc = launch_frames(c, batch, run_tracker, timestamps, ego_v, ego_yaw);
-  MOT_HIP(c, hipEventRecord(c->ev_consumed[s], c->stream));
-  c->stage_used[s] = true;
-  return rc;
+  return launch_staged(c, s, n_points, batch, run_tracker, timestamps, ego_v, ego_yaw);
 }
 
 // blocks until every H2D copy queued by mot_frames_host has completed: the caller's host buffers may be reused
@@ -1101,13 +1126,9 @@ extern "C" int mot_profile_read(mot_ctx* c, float* mean_ms, float* min_ms, float
   return MOT_OK;
 }
 
-// D2H of the per-frame counters (synchronises); device-side capacity flags become MOT_E_CAPACITY
-static int fetch_counts(mot_ctx* c, int slot) {
-  int* h = c->h_counts + slot * kCountsStride;
-  MOT_HIP(c, hipMemcpyAsync(h, c->d_counts + slot * kCountsStride, kCountsStride * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  MOT_HIP(c, hipStreamSynchronize(c->stream));
-  if (h[kCntFlags]) {
-    int f = h[kCntFlags];
+// a slot's device-side capacity flags (read back with its counters) become MOT_E_CAPACITY; the flags are cleared on the device
+static int capacity_error(mot_ctx* c, int slot, int f) {
+  if (f) {
     MOT_HIP(c, hipMemsetAsync(c->d_counts + slot * kCountsStride + kCntFlags, 0, sizeof(int), c->stream));
     if (f & kFlagClusterOverflow) return fail(c, MOT_E_CAPACITY, "more clusters in a frame than the library supports (4096)");
     if (f & kFlagBoxOverflow) return fail(c, MOT_E_CAPACITY, "more boxes in a frame than the library supports (1024)");
@@ -1117,12 +1138,36 @@ static int fetch_counts(mot_ctx* c, int slot) {
   }
   return MOT_OK;
 }
+// D2H of the per-frame counters (synchronises)
+static int fetch_counts(mot_ctx* c, int slot) {
+  int* h = c->h_counts + slot * kCountsStride;
+  MOT_HIP(c, hipMemcpyAsync(h, c->d_counts + slot * kCountsStride, kCountsStride * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  MOT_HIP(c, hipStreamSynchronize(c->stream));
+  return capacity_error(c, slot, h[kCntFlags]);
+}
 
 static int set_count(mot_ctx* c, int slot, int which, int value) {
   c->h_counts[slot * kCountsStride + which] = value;
   MOT_HIP(c, hipMemcpyAsync(c->d_counts + slot * kCountsStride + which, c->h_counts + slot * kCountsStride + which, sizeof(int),
                             hipMemcpyHostToDevice, c->stream));
   return MOT_OK;
+}
+
+// the argument checks the stage-wise cluster / box calls share (each with its own message)
+static int check_cloud(mot_ctx* c, const float* elev, int n, bool others_ok, const char* msg) {
+  if ((!elev && n > 0) || n < 0 || !others_ok) return fail(c, MOT_E_ARG, msg);
+  if (n > c->max_points) return fail(c, MOT_E_CAPACITY, "cloud has more points than max_points");
+  return MOT_OK;
+}
+// a stage-wise cluster / box call's own float4 cloud into slot 0, with_grid: and its label grid (already converted into h_grid16, each caller by its own rule)
+static int take_slot0(mot_ctx* c, const float* elev, int n, bool with_grid) {
+  if (n > 0) MOT_HIP(c, hipMemcpyAsync(c->d_elev, elev, (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
+  if (with_grid) {
+    MOT_HIP(c, hipMemcpyAsync(c->d_grid, c->h_grid16.data(), c->h_grid16.size() * sizeof(GridLabel), hipMemcpyHostToDevice, c->stream));
+    MOT_HIP(c, hipStreamSynchronize(c->stream));   // (h_grid16 is reused by the next call)
+  }
+  c->res.slot0_taken();
+  return set_count(c, 0, kCntElev, n);
 }
 
 extern "C" int mot_get_clusters(mot_ctx* c, int slot, int32_t* grid, int* num_cluster, int32_t* point_label, int label_capacity) {
@@ -1136,13 +1181,13 @@ extern "C" int mot_get_clusters(mot_ctx* c, int slot, int32_t* grid, int* num_cl
   int ne = c->h_counts[slot * kCountsStride + kCntElev];
   if (point_label && ne > label_capacity) return fail(c, MOT_E_CAPACITY, "more elevated points than the caller's label buffer holds");   // before any copy is queued: "nothing copied"
   if (grid) { c->h_grid16.resize((size_t)G * G); MOT_HIP(c, hipMemcpyAsync(c->h_grid16.data(), c->d_grid + (size_t)slot * MOT_MAX_GRID * MOT_MAX_GRID, (size_t)G * G * sizeof(GridLabel), hipMemcpyDeviceToHost, c->stream)); }
-  if (point_label && ne > 0 && c->label_state[slot] != 1) {
+  if (point_label && ne > 0 && !c->res.labels_ready(slot)) {
     // the fused path left the per-point labels out (mot_set_fused_outputs): this slot's, from its cells and label grid
     ClusterBuffers cb = cluster_buffers(c, slot);
-    cb.ecell = (c->label_state[slot] == 0 && c->params.num_grid < MOT_MAX_GRID) ? c->d_ecell : nullptr;
+    cb.ecell = (c->res.cells_usable(slot) && c->params.num_grid < MOT_MAX_GRID) ? c->d_ecell : nullptr;
     mot_launch_point_labels(c->dp, cb, slot, ne, c->stream);
     MOT_HIP(c, hipGetLastError());
-    c->label_state[slot] = 1;
+    c->res.labels_written(slot);
   }
   if (point_label && ne > 0) MOT_HIP(c, hipMemcpyAsync(point_label, c->d_label + (size_t)slot * c->cap, (size_t)ne * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   MOT_HIP(c, hipStreamSynchronize(c->stream));
@@ -1169,14 +1214,9 @@ extern "C" int mot_get_boxes(mot_ctx* c, int slot, float* boxes, int max_boxes, 
 extern "C" int mot_cluster(mot_ctx* c, const float* elev, int n, int32_t* grid, int* num_cluster, int32_t* point_label) {
   if (!c) return MOT_E_ARG;
   MOT_GUARD(c);
-  if ((!elev && n > 0) || n < 0 || !num_cluster) return fail(c, MOT_E_ARG, "mot_cluster: null cloud / negative n / null num_cluster");   // grid may be NULL: nothing but the count is read back
-  if (n > c->max_points) return fail(c, MOT_E_CAPACITY, "cloud has more points than max_points");
-  int rc;
-  if (n > 0) MOT_HIP(c, hipMemcpyAsync(c->d_elev, elev, (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
-  c->last_fused = false;   // slot 0 now holds this call's cloud: mot_get_ground must not re-run a fused batch's compaction over it
-  c->ground_foreign0 = true;   // ... and slot 0's ground cloud / mask (if any) are another cloud's: mot_get_ground(0) answers MOT_E_STATE, as include/mot.h promises
-  c->slot_packed[0] = 0;  // ... as float4 records
-  if ((rc = set_count(c, 0, kCntElev, n))) return rc;
+  int rc = check_cloud(c, elev, n, num_cluster != nullptr, "mot_cluster: null cloud / negative n / null num_cluster");   // grid may be NULL: nothing but the count is read back
+  if (rc) return rc;
+  if ((rc = take_slot0(c, elev, n, false))) return rc;
   ClusterBuffers cb = cluster_buffers(c, 0);
   mot_launch_cluster(c->dp, cb, 1, n, c->stream);
   if (point_label) {  // getClusteredPoints' per-point lookup; the statistics it also gathers are discarded
@@ -1184,8 +1224,7 @@ extern "C" int mot_cluster(mot_ctx* c, const float* elev, int n, int32_t* grid, 
     mot_launch_stats_init(cb, 1, c->stream);
     MOT_HIP(c, hipMemsetAsync(c->d_counts + kCntGroups, 0, 2 * sizeof(int), c->stream));   // kCntGroups, kCntIrregular
   }
-  c->label_state[0] = point_label ? 1 : 2;
-  c->box_valid[0] = 0;   // a new cloud in slot 0: what an earlier box stage left there is stale (mot_box_markers answers MOT_E_STATE)
+  if (point_label) c->res.labels_written(0);
   MOT_HIP(c, hipGetLastError());
   return mot_get_clusters(c, 0, grid, num_cluster, point_label, n);
 }
@@ -1194,26 +1233,19 @@ extern "C" int mot_box_fit(mot_ctx* c, const float* elev, int n, const int32_t* 
                            int* n_boxes, int32_t* box_cluster, int* n_undefined) {
   if (!c) return MOT_E_ARG;
   MOT_GUARD(c);
-  if ((!elev && n > 0) || n < 0 || !grid || num_cluster < 0 || !n_boxes) return fail(c, MOT_E_ARG, "mot_box_fit: null cloud / grid / n_boxes or a negative count");
-  if (n > c->max_points) return fail(c, MOT_E_CAPACITY, "cloud has more points than max_points");
+  int rc = check_cloud(c, elev, n, grid && num_cluster >= 0 && n_boxes, "mot_box_fit: null cloud / grid / n_boxes or a negative count");
+  if (rc) return rc;
   if (num_cluster > kMaxClusters) return fail(c, MOT_E_CAPACITY, "more clusters than the library supports (4096)");
-  int rc;
   const int G = c->params.num_grid;
-  if (n > 0) MOT_HIP(c, hipMemcpyAsync(c->d_elev, elev, (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
   // the caller's int32 grid onto the device's 16-bit one: a value outside 0 .. num_cluster names no cluster (getClusteredPoints indexes
   // its per-cluster vectors with it, box_fitting.cpp:59-66; the kernels treat it as "no label") and becomes 0
   c->h_grid16.resize((size_t)G * G);
   for (size_t i = 0, ng = (size_t)G * G; i < ng; i++) { const int32_t v = grid[i]; c->h_grid16[i] = (v < 0 || v > num_cluster) ? (GridLabel)0 : (GridLabel)v; }
-  MOT_HIP(c, hipMemcpyAsync(c->d_grid, c->h_grid16.data(), (size_t)G * G * sizeof(GridLabel), hipMemcpyHostToDevice, c->stream));
-  MOT_HIP(c, hipStreamSynchronize(c->stream));   // (h_grid16 is reused by the next call)
-  c->last_fused = false;   // slot 0 now holds this call's cloud: mot_get_ground must not re-run a fused batch's compaction over it
-  c->ground_foreign0 = true;   // ... and slot 0's ground cloud / mask (if any) are another cloud's: mot_get_ground(0) answers MOT_E_STATE, as include/mot.h promises
-  c->slot_packed[0] = 0;
-  if ((rc = set_count(c, 0, kCntElev, n))) return rc;
+  if ((rc = take_slot0(c, elev, n, true))) return rc;
   if ((rc = set_count(c, 0, kCntClusters, num_cluster))) return rc;
   ClusterBuffers cb = cluster_buffers(c, 0);
   mot_launch_box(c->dp, cb, 1, n, c->stream);
-  c->label_state[0] = 1; c->box_valid[0] = 1;
+  c->res.box_stage(0);
   MOT_HIP(c, hipGetLastError());
   return mot_get_boxes(c, 0, boxes, max_boxes, n_boxes, box_cluster, n_undefined);
 }
@@ -1230,7 +1262,7 @@ extern "C" int mot_box_fit_resident(mot_ctx* c, float* boxes, int max_boxes, int
   if (n < 0 || n > c->cap) return fail(c, MOT_E_STATE, "mot_box_fit_resident: no cloud resident in slot 0");
   if (c->h_counts[kCntClusters] > kMaxClusters) return fail(c, MOT_E_CAPACITY, "more clusters than the library supports (4096)");
   mot_launch_box(c->dp, cluster_buffers(c, 0), 1, n, c->stream);
-  c->label_state[0] = 1; c->box_valid[0] = 1;
+  c->res.box_stage(0);
   MOT_HIP(c, hipGetLastError());
   return mot_get_boxes(c, 0, boxes, max_boxes, n_boxes, box_cluster, n_undefined);
 }
@@ -1263,6 +1295,11 @@ extern "C" int mot_side_params_default(mot_side_params* o) {
 }
 
 constexpr int kMaxCostCells = 65536;
+static int check_cost_map(mot_ctx* c, const mot_side_params* sp) {
+  const bool ok = sp->cost_width >= 1 && sp->cost_height >= 1 && (long)sp->cost_width * sp->cost_height <= kMaxCostCells && sp->cost_resolution > 0;
+  return ok ? MOT_OK : fail(c, MOT_E_ARG, "cost map must have 1..65536 cells and a positive resolution");
+}
+static int ensure_markers(mot_ctx* c) { if (!c->d_markers) MOT_HIP(c, hipMalloc(&c->d_markers, (size_t)kMaxBoxesPerFrame * 6 * sizeof(float))); return MOT_OK; }
 
 static int side_setup(mot_ctx* c, int slot, const mot_side_params* sp, SideDevParams* dout, SideBuffers* sout) {
   // (a failure half-way — out of memory is plausible — leaves what exists for mot_destroy; the next call tries again from there)
@@ -1278,7 +1315,7 @@ static int side_setup(mot_ctx* c, int slot, const mot_side_params* sp, SideDevPa
   d.center_y = (sp->cost_height / 2.0) * sp->cost_resolution - sp->cost_offset_y;   // map_center_y, :429
   d.height_limit = sp->height_limit; d.car_length = sp->car_length; d.car_width = sp->car_width;
   SideBuffers s;
-  s.elevated = c->d_elev + (size_t)slot * c->cap; s.elevated_packed = elev_packed_at(c, slot) ? 1 : 0; s.grid = c->d_grid + (size_t)slot * MOT_MAX_GRID * MOT_MAX_GRID;
+  s.elevated = c->d_elev + (size_t)slot * c->cap; s.elevated_packed = c->res.elev_packed_at(slot) ? 1 : 0; s.grid = c->d_grid + (size_t)slot * MOT_MAX_GRID * MOT_MAX_GRID;
   s.counts = c->d_counts + (size_t)slot * kCountsStride; s.cell_first = c->d_side_cell; s.clustered = c->d_side_cloud;
   s.obstacles = c->d_side_obs; s.cost = c->d_side_cost; s.out_counts = c->d_side_counts; s.chunk_counts = c->d_side_chunks;
   s.max_clustered = c->cap; s.max_obstacles = MOT_MAX_GRID * MOT_MAX_GRID;
@@ -1293,18 +1330,14 @@ extern "C" int mot_cluster_products(mot_ctx* c, int slot, const mot_side_params*
   MOT_GUARD(c);
   if (!sp || slot < 0 || slot >= c->batch || max_clustered < 0 || max_obstacles < 0) return fail(c, MOT_E_ARG, "mot_cluster_products: null parameters, slot or a capacity out of range");
   if ((clustered_xyzw && !n_clustered) || (obstacles_xyzc && !n_obstacles)) return fail(c, MOT_E_ARG, "mot_cluster_products: an output list needs its count pointer");
-  if (sp->cost_width < 1 || sp->cost_height < 1 || (long)sp->cost_width * sp->cost_height > kMaxCostCells || !(sp->cost_resolution > 0))
-    return fail(c, MOT_E_ARG, "cost map must have 1..65536 cells and a positive resolution");
+  int rc = check_cost_map(c, sp);
+  if (rc) return rc;
   SideDevParams d; SideBuffers s;
-  {
-    const int rc0 = side_setup(c, slot, sp, &d, &s);
-    if (rc0) return rc0;
-  }
+  if ((rc = side_setup(c, slot, sp, &d, &s))) return rc;
   mot_launch_side_products(c->dp, d, s, c->cap, c->stream);
   MOT_HIP(c, hipGetLastError());
   char* pin;
-  int rc = pinned_scratch(c, 64, &pin);
-  if (rc) return rc;
+  if ((rc = pinned_scratch(c, 64, &pin))) return rc;
   int* h = reinterpret_cast<int*>(pin);
   MOT_HIP(c, hipMemcpyAsync(h, c->d_side_counts, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   MOT_HIP(c, hipStreamSynchronize(c->stream));
@@ -1324,8 +1357,8 @@ extern "C" int mot_cluster_products_host(mot_ctx* c, const float* elev, int n, c
                                          int max_obstacles, int* n_obstacles, int32_t* cost_map) {
   if (!c) return MOT_E_ARG;
   MOT_GUARD(c);
-  if ((!elev && n > 0) || n < 0 || !grid) return fail(c, MOT_E_ARG, "mot_cluster_products_host: null cloud / grid or negative n");
-  if (n > c->max_points) return fail(c, MOT_E_CAPACITY, "cloud has more points than max_points");
+  int rc = check_cloud(c, elev, n, grid != nullptr, "mot_cluster_products_host: null cloud / grid or negative n");
+  if (rc) return rc;
   const int G = c->params.num_grid;
   // the caller's int32 grid onto the device's 16-bit one. componentClustering's labels are 0 .. numCluster <= 32 768; the three functions replaced
   // here use a label only as "!= 0" and as the obstacle's cluster id, so anything outside 0 .. 65 535 is not a label grid (checked before anything
@@ -1335,15 +1368,7 @@ extern "C" int mot_cluster_products_host(mot_ctx* c, const float* elev, int n, c
     if (grid[i] < 0 || grid[i] > 65535) return fail(c, MOT_E_ARG, "mot_cluster_products_host: grid labels must lie in 0 .. 65535");
     c->h_grid16[i] = (GridLabel)grid[i];
   }
-  if (n > 0) MOT_HIP(c, hipMemcpyAsync(c->d_elev, elev, (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
-  MOT_HIP(c, hipMemcpyAsync(c->d_grid, c->h_grid16.data(), (size_t)G * G * sizeof(GridLabel), hipMemcpyHostToDevice, c->stream));
-  MOT_HIP(c, hipStreamSynchronize(c->stream));
-  c->last_fused = false;   // slot 0 now holds this call's cloud: mot_get_ground must not re-run a fused batch's compaction over it
-  c->ground_foreign0 = true;   // ... and slot 0's ground cloud / mask (if any) are another cloud's: mot_get_ground(0) answers MOT_E_STATE, as include/mot.h promises
-  c->slot_packed[0] = 0;
-  c->box_valid[0] = 0;
-  int rc = set_count(c, 0, kCntElev, n);
-  if (rc) return rc;
+  if ((rc = take_slot0(c, elev, n, true))) return rc;   // (the labels of the slot's previous cloud go with it: mot_get_clusters recomputes them from this cloud and this grid)
   return mot_cluster_products(c, 0, sp, clustered_xyzw, max_clustered, n_clustered, obstacles_xyzc, max_obstacles, n_obstacles, cost_map);
 }
 
@@ -1353,14 +1378,14 @@ extern "C" int mot_box_markers(mot_ctx* c, int slot, float* centroid_extent, int
   if (!c) return MOT_E_ARG;
   MOT_GUARD(c);
   if (slot < 0 || slot >= c->batch || max_boxes < 0 || !n_boxes) return fail(c, MOT_E_ARG, "mot_box_markers: slot or max_boxes out of range, or null n_boxes");
-  if (!c->box_valid[slot]) return fail(c, MOT_E_STATE, "mot_box_markers: no box stage has run on the cloud now resident in this slot (a stage-wise call replaced it since)");
+  if (!c->res.boxes_valid(slot)) return fail(c, MOT_E_STATE, "mot_box_markers: no box stage has run on the cloud now resident in this slot (a stage-wise call replaced it since)");
   int rc = fetch_counts(c, slot);   // (also reports a frame whose groups overflowed: its cluster order is incomplete)
   if (rc) return rc;
   const int nb = c->h_counts[slot * kCountsStride + kCntBoxes];
   *n_boxes = nb;
   if (nb > max_boxes) return fail(c, MOT_E_CAPACITY, "more boxes than the caller's buffer holds");
   if (nb == 0 || !centroid_extent) return MOT_OK;
-  if (!c->d_markers) MOT_HIP(c, hipMalloc(&c->d_markers, (size_t)kMaxBoxesPerFrame * 6 * sizeof(float)));
+  if ((rc = ensure_markers(c))) return rc;
   mot_launch_box_markers(cluster_buffers(c, slot), slot, nb < kMaxBoxesPerFrame ? nb : kMaxBoxesPerFrame, c->d_markers, c->stream);
   MOT_HIP(c, hipGetLastError());
   MOT_HIP(c, hipMemcpyAsync(centroid_extent, c->d_markers, (size_t)nb * 6 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
@@ -1374,15 +1399,13 @@ extern "C" int mot_box_markers(mot_ctx* c, int slot, float* centroid_extent, int
 extern "C" int mot_cluster_node_frame(mot_ctx* c, const float* elev, int n, const mot_side_params* sp, mot_cluster_frame* out) {
   if (!c) return MOT_E_ARG;
   MOT_GUARD(c);
-  if ((!elev && n > 0) || n < 0 || !sp || !out) return fail(c, MOT_E_ARG, "mot_cluster_node_frame: null cloud / parameters / result, or negative n");
-  if (n > c->max_points) return fail(c, MOT_E_CAPACITY, "cloud has more points than max_points");
-  if (sp->cost_width < 1 || sp->cost_height < 1 || (long)sp->cost_width * sp->cost_height > kMaxCostCells || !(sp->cost_resolution > 0))
-    return fail(c, MOT_E_ARG, "cost map must have 1..65536 cells and a positive resolution");
+  int rc = check_cloud(c, elev, n, sp && out, "mot_cluster_node_frame: null cloud / parameters / result, or negative n");
+  if (rc) return rc;
+  if ((rc = check_cost_map(c, sp))) return rc;
   memset(out, 0, sizeof *out);
   SideDevParams d; SideBuffers s;
-  int rc = side_setup(c, 0, sp, &d, &s);
-  if (rc) return rc;
-  if (!c->d_markers) MOT_HIP(c, hipMalloc(&c->d_markers, (size_t)kMaxBoxesPerFrame * 6 * sizeof(float)));
+  if ((rc = side_setup(c, 0, sp, &d, &s))) return rc;
+  if ((rc = ensure_markers(c))) return rc;
   const size_t cost_cells = (size_t)sp->cost_width * sp->cost_height;
   // the page-locked block: [counts 64 B][clustered n x 16][obstacles min(n, G^2) x 16][cost map][boxes][box clusters][cubes]
   const size_t G2 = (size_t)c->params.num_grid * c->params.num_grid, max_obs = (size_t)n < G2 ? (size_t)n : G2;
@@ -1391,36 +1414,23 @@ extern "C" int mot_cluster_node_frame(mot_ctx* c, const float* elev, int n, cons
                total = o_mk + (size_t)kMaxBoxesPerFrame * 6 * sizeof(float);
   char* pin;
   if ((rc = pinned_scratch(c, total, &pin))) return rc;
-  if (n > 0) MOT_HIP(c, hipMemcpyAsync(c->d_elev, elev, (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
-  c->last_fused = false;   // slot 0 now holds this call's cloud
-  c->ground_foreign0 = true;   // ... and slot 0's ground cloud / mask (if any) are another cloud's: mot_get_ground(0) answers MOT_E_STATE, as include/mot.h promises
-  c->slot_packed[0] = 0;
+  if ((rc = take_slot0(c, elev, n, false))) return rc;   // (nothing of this frame is vouched for until the device's flags say that it fit: below)
   s.elevated_packed = 0;   // (side_setup looked at slot 0 BEFORE the upload: after a fused batch on this context it saw 12-byte points there)
-  if ((rc = set_count(c, 0, kCntElev, n))) return rc;
   ClusterBuffers cb = cluster_buffers(c, 0);
   mot_launch_cluster(c->dp, cb, 1, n, c->stream);
   mot_launch_side_products(c->dp, d, s, n > 0 ? n : 1, c->stream);
   mot_launch_box(c->dp, cb, 1, n, c->stream);
   mot_launch_box_markers(cb, 0, kMaxBoxesPerFrame, c->d_markers, c->stream);   // (the box count is still on the device: workgroups beyond it leave at once)
-  c->label_state[0] = 2; c->box_valid[0] = 0;   // until the device's flags say that the frame fit (set below); 2: no per-point labels vouched for, no cell codes either
   MOT_HIP(c, hipGetLastError());
   int* h = reinterpret_cast<int*>(pin);
   MOT_HIP(c, hipMemcpyAsync(h, c->d_counts, kCountsStride * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   MOT_HIP(c, hipMemcpyAsync(h + kCountsStride, c->d_side_counts, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   MOT_HIP(c, hipStreamSynchronize(c->stream));
   memcpy(c->h_counts, h, kCountsStride * sizeof(int));
-  if (h[kCntFlags]) {
-    const int f = h[kCntFlags];
-    MOT_HIP(c, hipMemsetAsync(c->d_counts + kCntFlags, 0, sizeof(int), c->stream));
-    if (f & kFlagClusterOverflow) return fail(c, MOT_E_CAPACITY, "more clusters in a frame than the library supports (4096)");
-    if (f & kFlagBoxOverflow) return fail(c, MOT_E_CAPACITY, "more boxes in a frame than the library supports (1024)");
-    if (f & kFlagHullOverflow) return fail(c, MOT_E_CAPACITY, "convex hull larger than 384 vertices");
-    if (f & kFlagGroupOverflow) return fail(c, MOT_E_CAPACITY, "cloud too fragmented: more than max_points/2 (tile, cluster) groups in a frame");
-    if (f & kFlagRngExhausted) return fail(c, MOT_E_CAPACITY, "L-shape sampling ran out of pre-generated random draws");
-  }
+  if ((rc = capacity_error(c, 0, h[kCntFlags]))) return rc;
   const int ncc = h[kCountsStride], nob = h[kCountsStride + 1], nb = h[kCntBoxes];
   if (ncc < 0 || ncc > n || nob < 0 || (size_t)nob > max_obs || nb < 0 || nb > kMaxBoxesPerFrame) return fail(c, MOT_E_STATE, "mot_cluster_node_frame: inconsistent counts");
-  c->label_state[0] = 1; c->box_valid[0] = 1;   // no overflow: slot 0 holds this cloud's labels and boxes (mot_box_markers / mot_get_boxes / mot_get_clusters may read them)
+  c->res.box_stage(0);   // no overflow: slot 0 holds this cloud's labels and boxes
   if (ncc > 0) MOT_HIP(c, hipMemcpyAsync(pin + o_cc, c->d_side_cloud, (size_t)ncc * 16, hipMemcpyDeviceToHost, c->stream));
   if (nob > 0) MOT_HIP(c, hipMemcpyAsync(pin + o_ob, c->d_side_obs, (size_t)nob * 16, hipMemcpyDeviceToHost, c->stream));
   MOT_HIP(c, hipMemcpyAsync(pin + o_cm, c->d_side_cost, cost_cells * sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -1450,26 +1460,37 @@ extern "C" int mot_get_ground(mot_ctx* c, int slot, float* elev, int* n_elev, fl
   if (n_ground) *n_ground = ng;
   if ((elev && ne > capacity_points) || (ground && ng > capacity_points) || (mask && c->h_n[slot] > capacity_points))
     return fail(c, MOT_E_CAPACITY, "more points resident than the caller's buffers hold (capacity_points)");
-  if (slot == 0 && c->ground_foreign0 && (elev || ground || mask))
+  // (known, kept as it is: the counts above are written and the capacity tested before this refusal)
+  if (c->res.ground_foreign(slot) && (elev || ground || mask))
     return fail(c, MOT_E_STATE, "mot_get_ground: a stage-wise cluster / box call has put its own cloud into slot 0 since the ground stage ran: no ground result of that cloud is resident");
-  const bool have_ground = c->ground_resident && (c->ground_all ? slot < c->last_batch : slot == 0);   // (a slot beyond the last batch: whatever an earlier batch left is not vouched for)
-  if (((ground || mask) && !have_ground) || (elev && elev_packed_at(c, slot))) {   // (packed: the fused path left 12-byte points; the ABI's records are float4 with the input's 4th value)
+  if (((ground || mask) && !c->res.ground_readable(slot)) || (elev && c->res.elev_packed_at(slot))) {   // (packed: the fused path left 12-byte points; the ABI's records are float4 with the input's 4th value)
     // The fused path left the ground cloud / mask out (mot_set_fused_outputs): materialise them for the whole last batch by
     // re-running the compaction with every output, from the batch's input, polar cells and thresholds — all still resident.
     // (No occupancy this time: the cluster stage has consumed it. The elevated cloud and the counts are rewritten with the
     // same values.)
-    if (!c->last_fused || !c->last_in || c->last_batch < 1 || slot >= c->last_batch) return fail(c, MOT_E_STATE, "mot_get_ground: no ground result resident");
+    if (!c->res.can_rebuild_ground(slot)) return fail(c, MOT_E_STATE, "mot_get_ground: no ground result resident");
     if ((rc = next_epoch(c))) return rc;
-    GroundBuffers g = ground_buffers(c, c->last_in, c->last_in_stride, true, false);
-    mot_launch_ground_kernel(2, c->dp, g, c->last_batch, c->last_max_n, c->stream);
+    GroundBuffers g = ground_buffers(c, c->res.last_in, c->res.last_in_stride, true, false);
+    mot_launch_ground_kernel(2, c->dp, g, c->res.last_batch, c->res.last_max_n, c->stream);
     MOT_HIP(c, hipGetLastError());
-    c->ground_resident = true; c->ground_all = true; c->elev_packed = false;
-    for (int b = 0; b < c->last_batch; b++) c->slot_packed[b] = 0;   // every slot's elevated cloud is float4 again (same points, same order: what the later stages hold stays valid)
+    c->res.compaction_rerun(c->res.last_batch, false, true);   // every slot's elevated cloud is float4 again
   }
   if (elev && ne > 0) MOT_HIP(c, hipMemcpyAsync(elev, c->d_elev + (size_t)slot * c->cap, (size_t)ne * 16, hipMemcpyDeviceToHost, c->stream));
   if (ground && ng > 0) MOT_HIP(c, hipMemcpyAsync(ground, c->d_ground + (size_t)slot * c->cap, (size_t)ng * 16, hipMemcpyDeviceToHost, c->stream));
   if (mask && c->h_n[slot] > 0) MOT_HIP(c, hipMemcpyAsync(mask, c->d_mask + (size_t)slot * c->cap, (size_t)c->h_n[slot], hipMemcpyDeviceToHost, c->stream));
   MOT_HIP(c, hipStreamSynchronize(c->stream));
+  return MOT_OK;
+}
+
+// the stage-wise ground stage on the cloud a caller has put into d_in (slot 0)
+static int ground_stage_slot0(mot_ctx* c, int n, bool want_mask) {
+  int rc = set_batch(c, &n, 1, c->d_in, c->cap);
+  if (rc) return rc;
+  if ((rc = next_epoch(c))) return rc;
+  GroundBuffers g = ground_buffers(c, c->d_in, c->cap, want_mask);
+  mot_launch_ground(c->dp, g, 1, n, c->stream);
+  MOT_HIP(c, hipGetLastError());
+  c->res.ground_stage(want_mask);
   return MOT_OK;
 }
 
@@ -1480,13 +1501,8 @@ extern "C" int mot_ground_remove(mot_ctx* c, const float* xyzw, int n, float* el
   if ((!xyzw && n > 0) || n < 0) return fail(c, MOT_E_ARG, "mot_ground_remove: null cloud or negative n");
   if (n > c->max_points) return fail(c, MOT_E_CAPACITY, "frame has more points than max_points");
   if (n > 0) MOT_HIP(c, hipMemcpyAsync(c->d_in, xyzw, (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
-  int rc = set_batch(c, &n, 1, c->d_in, c->cap);
+  int rc = ground_stage_slot0(c, n, true);
   if (rc) return rc;
-  if ((rc = next_epoch(c))) return rc;
-  GroundBuffers g = ground_buffers(c, c->d_in, c->cap, true);
-  mot_launch_ground(c->dp, g, 1, n, c->stream);
-  MOT_HIP(c, hipGetLastError());
-  c->ground_resident = true; c->ground_all = false; c->last_fused = false; c->ground_foreign0 = false; c->slot_packed[0] = 0; c->label_state[0] = 2; c->box_valid[0] = 0;
   return mot_get_ground(c, 0, elev, n_elev, ground, n_ground, mask, n);
 }
 
@@ -1500,14 +1516,7 @@ extern "C" int mot_ground_node_frame(mot_ctx* c, const float* xyzw, int n, const
   int rc = pinned_scratch(c, 64 + 2 * (size_t)n * 16, &pin);
   if (rc) return rc;
   if (n > 0) MOT_HIP(c, hipMemcpyAsync(c->d_in, xyzw, (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
-  if ((rc = set_batch(c, &n, 1, c->d_in, c->cap))) return rc;
-  if ((rc = next_epoch(c))) return rc;
-  GroundBuffers g = ground_buffers(c, c->d_in, c->cap, false);
-  mot_launch_ground(c->dp, g, 1, n, c->stream);
-  MOT_HIP(c, hipGetLastError());
-  c->ground_resident = false;   // (no mask: a later mot_get_ground that asks for one answers MOT_E_STATE)
-  c->slot_packed[0] = 0;
-  c->last_fused = false; c->ground_foreign0 = false; c->label_state[0] = 2; c->box_valid[0] = 0;
+  if ((rc = ground_stage_slot0(c, n, false))) return rc;
   if ((rc = fetch_counts(c, 0))) return rc;
   const int ne = c->h_counts[kCntElev], ng = c->h_counts[kCntGround];
   if (ne < 0 || ng < 0 || ne + ng > n) return fail(c, MOT_E_STATE, "mot_ground_node_frame: inconsistent counts");
@@ -1547,13 +1556,7 @@ extern "C" int mot_ground_remove_pointcloud2(mot_ctx* c, const void* data, int n
   MOT_GUARD(c);
   int rc = upload_pointcloud2(c, data, n, point_step, off_x, off_y, off_z);
   if (rc) return rc;
-  rc = set_batch(c, &n, 1, c->d_in, c->cap);
-  if (rc) return rc;
-  if ((rc = next_epoch(c))) return rc;
-  GroundBuffers g = ground_buffers(c, c->d_in, c->cap, true);
-  mot_launch_ground(c->dp, g, 1, n, c->stream);
-  MOT_HIP(c, hipGetLastError());
-  c->ground_resident = true; c->ground_all = false; c->last_fused = false; c->ground_foreign0 = false; c->slot_packed[0] = 0; c->label_state[0] = 2; c->box_valid[0] = 0;
+  if ((rc = ground_stage_slot0(c, n, true))) return rc;
   return mot_get_ground(c, 0, elev, n_elev, ground, n_ground, mask, n);
 }
 
@@ -1569,22 +1572,17 @@ extern "C" int mot_frame_pointcloud2(mot_ctx* c, const void* data, int n, int po
 
 static int launch_one(mot_ctx* c, int id, int batch) {
   int rc;
-  const int max_n = c->last_max_n;
+  const int max_n = c->res.last_max_n;
   if (id == kK3 && (rc = next_epoch(c))) return rc;
-  GroundBuffers g = ground_buffers(c, c->last_in, c->last_in_stride, (c->fused_outputs & MOT_OUT_MASK) != 0, true);   // as in the fused path: the compaction kernel leaves the occupancy lists
-  if (!(c->fused_outputs & MOT_OUT_GROUND)) g.ground = nullptr;
-  g.elevated_packed = (MOT_PACKED_ELEVATED && !g.ground) ? 1 : 0;
-  if (id == kK3) { c->elev_packed = g.elevated_packed != 0; for (int b = 0; b < batch; b++) c->slot_packed[b] = c->elev_packed ? 1 : 0; }
-  if (id == kK3) { c->ground_resident = (c->fused_outputs & (MOT_OUT_GROUND | MOT_OUT_MASK)) == (MOT_OUT_GROUND | MOT_OUT_MASK); c->ground_all = true; }
-  ClusterBuffers cb = cluster_buffers(c);
-  cb.occ_list = c->d_occ_list; cb.occ_count = c->d_occ_count; cb.ecell = g.ecell;
-  if (!(c->fused_outputs & MOT_OUT_LABELS)) cb.label = nullptr;   // as in the fused path
+  if (id == kK3) c->res.compaction_rerun(batch, Residency::fused_packs(c->fused_outputs), Residency::fused_keeps_ground(c->fused_outputs));
+  GroundBuffers g; ClusterBuffers cb;
+  fused_buffers(c, &g, &cb);   // as in the fused path
   switch (id) {
     case kK1: mot_launch_ground_kernel(0, c->dp, g, batch, max_n, c->stream); break;
     case kK2: mot_launch_ground_kernel(1, c->dp, g, batch, max_n, c->stream); break;
     case kK3: mot_launch_ground_kernel(2, c->dp, g, batch, max_n, c->stream); break;
     case kC2: mot_launch_cluster_kernel(1, c->dp, cb, batch, max_n, c->stream); break;
-    case kB1: mot_launch_box_kernel(0, c->dp, cb, batch, max_n, c->stream); for (int b = 0; b < batch; b++) c->label_state[b] = cb.label ? 1 : 0; break;
+    case kB1: mot_launch_box_kernel(0, c->dp, cb, batch, max_n, c->stream); for (int b = 0; b < batch; b++) c->res.labels_written(b, cb.label != nullptr); break;
     case kB2: mot_launch_box_kernel(1, c->dp, cb, batch, max_n, c->stream); break;
     case kB3: mot_launch_box_kernel(2, c->dp, cb, batch, max_n, c->stream); break;
     case kB2b: mot_launch_box_kernel(3, c->dp, cb, batch, max_n, c->stream); break;
@@ -1604,7 +1602,7 @@ extern "C" int mot_time_stage(mot_ctx* c, int stage, int batch, int iters, float
   if (!c) return MOT_E_ARG;
   MOT_GUARD(c);
   if (!ms_per_iter || iters < 1) return fail(c, MOT_E_ARG, "mot_time_stage: null result pointer or iters < 1");
-  if (!c->last_in || batch != c->last_batch) return fail(c, MOT_E_STATE, "call mot_frames_dev with the same batch first");
+  if (!c->res.last_in || batch != c->res.last_batch) return fail(c, MOT_E_STATE, "call mot_frames_dev with the same batch first");
   struct Seq { int pre[4], timed[12], post[3]; };
   Seq s = {{0, 0, 0, 0}, {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, {0, 0, 0}};
   switch (stage) {
