@@ -127,6 +127,9 @@ label_stats_kernel(MotDevParams p, ClusterBuffers c) {
   // workgroups per frame, profiles/r03_box_stage_experiments.txt: many independent workgroups hide the three dependent round
   // trips at a chunk's start better than any one workgroup's prefetch)
   const long base = (long)blockIdx.x * kLabelChunk;
+  // the box stage starts here: the frame's capacity flags are re-armed inside the launch sequence (a captured graph replays it), so that a refusal
+  // stays with the frame that caused it — the getters no longer clear what they report. The kernels that raise a flag all run behind this one.
+  if (blockIdx.x == 0 && threadIdx.x == 0) c.counts[b * kCountsStride + kCntFlags] = 0;
   if (base >= n) return;
   if (threadIdx.x < kWgClusters) {
     s_tab_label[threadIdx.x] = 0; s_tab_count[threadIdx.x] = 0; s_tab_first[threadIdx.x] = 0x7fffffff;
@@ -342,8 +345,7 @@ cluster_index_kernel(ClusterBuffers c) {
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int num_cluster = min(c.counts[b * kCountsStride + kCntClusters], kMaxClusters);
   const int n = c.counts[b * kCountsStride + kCntElev];
-  int E = c.counts[b * kCountsStride + kCntGroups];
-  if (E > c.group_cap) { E = c.group_cap; if (tid == 0) atomicOr(&c.counts[b * kCountsStride + kCntFlags], (int)kFlagGroupOverflow); }
+  const int E = c.counts[b * kCountsStride + kCntGroups];
   const int nwg = (n + kLabelChunk - 1) / kLabelChunk;
   const bool fast = c.counts[b * kCountsStride + kCntIrregular] == 0 && nwg <= kIndexWgLds && nwg <= c.max_wg && n <= (1 << kIndexPointBits) - 64;   // (fewer than 2^13 tiles: a cluster's groups fit the 13 bits above its 19 bits of points)
   const PointGroup* __restrict__ groups = c.groups + (long)b * c.group_cap;
@@ -351,6 +353,19 @@ cluster_index_kernel(ClusterBuffers c) {
   int* cstart = c.cluster_start + (long)b * (kMaxClusters + 1);
   int* cgstart = c.cluster_gstart + (long)b * (kMaxClusters + 1);   // (read back below by other threads of this workgroup: no __restrict__)
   SortedGroup* __restrict__ gsorted = c.gsorted + (long)b * c.group_cap;
+  if (E > c.group_cap) {
+    // A REFUSED frame (uniform over the workgroup). The label kernel stored the first group_cap groups only, but counted every group into the
+    // clusters' statistics: buckets sized by those counts would hold records nobody wrote, and the per-cluster kernels would follow their tile
+    // numbers out of the frame's buffers. Nothing of such a frame is delivered (every getter answers MOT_E_CAPACITY), so nothing of it is put in
+    // order here — cluster starts, group starts and the processing order keep whatever an earlier frame left, or what hipMalloc left — and the
+    // whole per-cluster stage SKIPS the frame: the gather and rectangle kernels leave at once when they see this flag, and box_finalize_body
+    // delivers no box without reading a candidate record (it still re-arms the statistics).
+    if (tid == 0) {
+      atomicOr(&c.counts[b * kCountsStride + kCntFlags], (int)kFlagGroupOverflow);
+      c.counts[b * kCountsStride + kCntGroups] = 0; c.counts[b * kCountsStride + kCntIrregular] = 0;  // re-arm
+    }
+    return;
+  }
   B1B_T_BEGIN(c, b);
   // exclusive scans of the cluster sizes in points and in groups (kMaxClusters / kIndexBlock clusters per thread)
   {
@@ -612,6 +627,7 @@ cluster_gather_kernel(MotDevParams p, ClusterBuffers c) {
   const int b = blockIdx.y;
   const int n = c.counts[b * kCountsStride + kCntElev];
   const int num_cluster = min(c.counts[b * kCountsStride + kCntClusters], kMaxClusters);
+  if (c.counts[b * kCountsStride + kCntFlags] & (int)kFlagGroupOverflow) return;   // a refused frame (cluster_index_kernel, the launch before this one): its cluster starts and cluster-ordered groups were never written
   const float4* __restrict__ pts = c.elevated + (long)b * c.cap;
   const SortedGroup* __restrict__ gsorted = c.gsorted + (long)b * c.group_cap;
   const int* __restrict__ cstart = c.cluster_start + (long)b * (kMaxClusters + 1);
@@ -1011,6 +1027,9 @@ __device__ __forceinline__ void cluster_rect_body(const MotDevParams& p, const C
   // the large-hull instantiation finds no work in almost every frame: the gather kernel leaves a per-frame flag, and without it
   // this kernel is one load (walking the frame's clusters to discover that cost 24 us per 512 frames)
   if (kLarge && c.counts[b * kCountsStride + kCntPoly] == 0) return;
+  // a frame the index kernel refused has no processing order and no candidate records (the gather kernel skipped it): order[] and cand[] hold
+  // an earlier frame's values or none at all
+  if (c.counts[b * kCountsStride + kCntFlags] & (int)kFlagGroupOverflow) return;
   // clusters by falling size, dealt to the frame's workgroups forwards, then backwards, ...: whoever got a large one in a round
   // gets a small one in the next (45 -> 41 us)
   for (int round = 0; round * (int)gridDim.x < num_cluster; round++) {
@@ -1242,6 +1261,9 @@ static __device__ void box_finalize_body(const MotDevParams& p, const ClusterBuf
   const int b = blockIdx.x;
   const int num_cluster = min(c.counts[b * kCountsStride + kCntClusters], kMaxClusters);
   const int lane = lane_id(), wave = threadIdx.x >> 6;
+  // a frame the index kernel refused: the per-cluster kernels skipped it, its candidate records are not this frame's. No box, nothing undefined.
+  // (Read by every thread before thread 0 raises a flag of its own below: another bit of the same word.)
+  const bool skipped = (c.counts[b * kCountsStride + kCntFlags] & (int)kFlagGroupOverflow) != 0;
   if (threadIdx.x == 0) {
     s_base = 0; s_undef = 0;
     if (c.counts[b * kCountsStride + kCntClusters] > kMaxClusters) atomicOr(&c.counts[b * kCountsStride + kCntFlags], (int)kFlagClusterOverflow);
@@ -1250,7 +1272,7 @@ static __device__ void box_finalize_body(const MotDevParams& p, const ClusterBuf
   for (int base = 0; base < num_cluster; base += kFinalBlock) {
     int ci = base + threadIdx.x;
     BoxCandidate cand; cand.accepted = 0; cand.undefined = 0;
-    if (ci < num_cluster) cand = c.cand[(long)b * kMaxClusters + ci];
+    if (ci < num_cluster && !skipped) cand = c.cand[(long)b * kMaxClusters + ci];
     unsigned long long acc = __ballot(cand.accepted != 0);
     unsigned long long und = __ballot(cand.undefined != 0);
     if (lane == 0) { s_wave[wave] = __popcll(acc); if (und) atomicAdd(&s_undef, __popcll(und)); }

@@ -1126,11 +1126,14 @@ extern "C" int mot_profile_read(mot_ctx* c, float* mean_ms, float* min_ms, float
   return MOT_OK;
 }
 
-// a slot's device-side capacity flags (read back with its counters) become MOT_E_CAPACITY; the flags are cleared on the device
-static int capacity_error(mot_ctx* c, int slot, int f) {
+// a slot's device-side capacity flags (read back with its counters) become MOT_E_CAPACITY. Reading does NOT clear them: the refusal belongs to the
+// frame, and every getter answers it, however often, until a new stage call writes the slot — the flags are re-armed where a stage starts on
+// it (the label kernel at the head of the box stage, inside the launch sequence and any graph captured from it; take_slot0 and
+// ground_stage_slot0 for the stage-wise calls that put a new cloud into slot 0 without running the box stage).
+static const char kMsgClusterOverflow[] = "more clusters in a frame than the library supports (4096)";
+static int capacity_error(mot_ctx* c, int f) {
   if (f) {
-    MOT_HIP(c, hipMemsetAsync(c->d_counts + slot * kCountsStride + kCntFlags, 0, sizeof(int), c->stream));
-    if (f & kFlagClusterOverflow) return fail(c, MOT_E_CAPACITY, "more clusters in a frame than the library supports (4096)");
+    if (f & kFlagClusterOverflow) return fail(c, MOT_E_CAPACITY, kMsgClusterOverflow);
     if (f & kFlagBoxOverflow) return fail(c, MOT_E_CAPACITY, "more boxes in a frame than the library supports (1024)");
     if (f & kFlagHullOverflow) return fail(c, MOT_E_CAPACITY, "convex hull larger than 384 vertices");
     if (f & kFlagGroupOverflow) return fail(c, MOT_E_CAPACITY, "cloud too fragmented: more than max_points/2 (tile, cluster) groups in a frame");
@@ -1143,7 +1146,7 @@ static int fetch_counts(mot_ctx* c, int slot) {
   int* h = c->h_counts + slot * kCountsStride;
   MOT_HIP(c, hipMemcpyAsync(h, c->d_counts + slot * kCountsStride, kCountsStride * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   MOT_HIP(c, hipStreamSynchronize(c->stream));
-  return capacity_error(c, slot, h[kCntFlags]);
+  return capacity_error(c, h[kCntFlags]);
 }
 
 static int set_count(mot_ctx* c, int slot, int which, int value) {
@@ -1167,6 +1170,8 @@ static int take_slot0(mot_ctx* c, const float* elev, int n, bool with_grid) {
     MOT_HIP(c, hipStreamSynchronize(c->stream));   // (h_grid16 is reused by the next call)
   }
   c->res.slot0_taken();
+  int rc = set_count(c, 0, kCntFlags, 0);   // a new cloud: the flags of the frame it replaces go with that frame
+  if (rc) return rc;
   return set_count(c, 0, kCntElev, n);
 }
 
@@ -1235,7 +1240,7 @@ extern "C" int mot_box_fit(mot_ctx* c, const float* elev, int n, const int32_t* 
   MOT_GUARD(c);
   int rc = check_cloud(c, elev, n, grid && num_cluster >= 0 && n_boxes, "mot_box_fit: null cloud / grid / n_boxes or a negative count");
   if (rc) return rc;
-  if (num_cluster > kMaxClusters) return fail(c, MOT_E_CAPACITY, "more clusters than the library supports (4096)");
+  if (num_cluster > kMaxClusters) return fail(c, MOT_E_CAPACITY, kMsgClusterOverflow);
   const int G = c->params.num_grid;
   // the caller's int32 grid onto the device's 16-bit one: a value outside 0 .. num_cluster names no cluster (getClusteredPoints indexes
   // its per-cluster vectors with it, box_fitting.cpp:59-66; the kernels treat it as "no label") and becomes 0
@@ -1260,7 +1265,12 @@ extern "C" int mot_box_fit_resident(mot_ctx* c, float* boxes, int max_boxes, int
   if (rc) return rc;
   const int n = c->h_counts[kCntElev];
   if (n < 0 || n > c->cap) return fail(c, MOT_E_STATE, "mot_box_fit_resident: no cloud resident in slot 0");
-  if (c->h_counts[kCntClusters] > kMaxClusters) return fail(c, MOT_E_CAPACITY, "more clusters than the library supports (4096)");
+  if (c->h_counts[kCntClusters] > kMaxClusters) {
+    // turned down before a kernel runs — and the refusal is left on the resident frame, as the kernels would have left it: every getter of slot 0
+    // answers it from now on (fetch_counts), until a stage call puts a new cloud there
+    if ((rc = set_count(c, 0, kCntFlags, kFlagClusterOverflow))) return rc;
+    return fail(c, MOT_E_CAPACITY, kMsgClusterOverflow);
+  }
   mot_launch_box(c->dp, cluster_buffers(c, 0), 1, n, c->stream);
   c->res.box_stage(0);
   MOT_HIP(c, hipGetLastError());
@@ -1332,6 +1342,7 @@ extern "C" int mot_cluster_products(mot_ctx* c, int slot, const mot_side_params*
   if ((clustered_xyzw && !n_clustered) || (obstacles_xyzc && !n_obstacles)) return fail(c, MOT_E_ARG, "mot_cluster_products: an output list needs its count pointer");
   int rc = check_cost_map(c, sp);
   if (rc) return rc;
+  if ((rc = fetch_counts(c, slot))) return rc;   // a frame the box stage refused is refused here as well: nothing of it is delivered
   SideDevParams d; SideBuffers s;
   if ((rc = side_setup(c, slot, sp, &d, &s))) return rc;
   mot_launch_side_products(c->dp, d, s, c->cap, c->stream);
@@ -1378,9 +1389,9 @@ extern "C" int mot_box_markers(mot_ctx* c, int slot, float* centroid_extent, int
   if (!c) return MOT_E_ARG;
   MOT_GUARD(c);
   if (slot < 0 || slot >= c->batch || max_boxes < 0 || !n_boxes) return fail(c, MOT_E_ARG, "mot_box_markers: slot or max_boxes out of range, or null n_boxes");
-  if (!c->res.boxes_valid(slot)) return fail(c, MOT_E_STATE, "mot_box_markers: no box stage has run on the cloud now resident in this slot (a stage-wise call replaced it since)");
-  int rc = fetch_counts(c, slot);   // (also reports a frame whose groups overflowed: its cluster order is incomplete)
+  int rc = fetch_counts(c, slot);   // (a refused frame first, with the limit's message like every other getter: its cluster order is incomplete or absent)
   if (rc) return rc;
+  if (!c->res.boxes_valid(slot)) return fail(c, MOT_E_STATE, "mot_box_markers: no box stage has run on the cloud now resident in this slot (a stage-wise call replaced it since)");
   const int nb = c->h_counts[slot * kCountsStride + kCntBoxes];
   *n_boxes = nb;
   if (nb > max_boxes) return fail(c, MOT_E_CAPACITY, "more boxes than the caller's buffer holds");
@@ -1427,7 +1438,7 @@ extern "C" int mot_cluster_node_frame(mot_ctx* c, const float* elev, int n, cons
   MOT_HIP(c, hipMemcpyAsync(h + kCountsStride, c->d_side_counts, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   MOT_HIP(c, hipStreamSynchronize(c->stream));
   memcpy(c->h_counts, h, kCountsStride * sizeof(int));
-  if ((rc = capacity_error(c, 0, h[kCntFlags]))) return rc;
+  if ((rc = capacity_error(c, h[kCntFlags]))) return rc;
   const int ncc = h[kCountsStride], nob = h[kCountsStride + 1], nb = h[kCntBoxes];
   if (ncc < 0 || ncc > n || nob < 0 || (size_t)nob > max_obs || nb < 0 || nb > kMaxBoxesPerFrame) return fail(c, MOT_E_STATE, "mot_cluster_node_frame: inconsistent counts");
   c->res.box_stage(0);   // no overflow: slot 0 holds this cloud's labels and boxes
@@ -1487,6 +1498,7 @@ static int ground_stage_slot0(mot_ctx* c, int n, bool want_mask) {
   int rc = set_batch(c, &n, 1, c->d_in, c->cap);
   if (rc) return rc;
   if ((rc = next_epoch(c))) return rc;
+  if ((rc = set_count(c, 0, kCntFlags, 0))) return rc;   // a new cloud in slot 0: the flags of the frame it replaces go with that frame
   GroundBuffers g = ground_buffers(c, c->d_in, c->cap, want_mask);
   mot_launch_ground(c->dp, g, 1, n, c->stream);
   MOT_HIP(c, hipGetLastError());
@@ -1781,7 +1793,8 @@ extern "C" int mot_get_tracks(mot_ctx* c, int slot, mot_track* tracks, int max_t
   // ignores one error is told again on every call, not only at the next dropped birth.
   if (sticky)
     return fail(c, MOT_E_CAPACITY, "a stream ran out of track slots (more than max_tracks_total tracks alive or just dead) or of its lifetime track budget "
-                                   "(mot_params.max_tracks_ever): births are being dropped; mot_reset_tracks_slot() starts its tracks over");
+                                   "(mot_params.max_tracks_ever): births are being dropped; or a fused frame of the stream was refused for capacity "
+                                   "(see mot_get_boxes) and the tracker stepped on an incomplete box list; mot_reset_tracks_slot() starts its tracks over");
   return MOT_OK;
 }
 
@@ -2302,6 +2315,7 @@ extern "C" int mot_debug_copy(mot_ctx* c, int which, int slot, void* dst, size_t
   else if (which == 10) src = c->d_hg + (size_t)slot * MOT_POLAR_CELLS;
   else if (which == 11) src = c->d_tboxes + (size_t)slot * kMaxBoxesPerFrame * 24;
   else if (which == 12) src = reinterpret_cast<const long long*>(c->d_items) + (size_t)slot * 32;   // -DMOT_DBG_STREAM_TIMING builds: phase clocks of track_step_stream_kernel
+  else if (which == 13) src = c->d_cluster_gstart + (size_t)slot * (kMaxClusters + 1);
   else return MOT_E_ARG;
   MOT_HIP(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
   MOT_HIP(c, hipStreamSynchronize(c->stream));

@@ -10,7 +10,8 @@ extern "C" {
 #endif
 /* raw copy of a per-slot device array to the host (which: 0 box candidates, 1 cluster statistics,
  * 3 polygon pool, 5 cluster-sorted index, 7 cluster starts, 8 pixels, 9 (tile, cluster) groups, 10 polar thresholds hGround,
- * 11 the fused path's boxes in the global frame (the tracker's input)) */
+ * 11 the fused path's boxes in the global frame (the tracker's input), 13 first (tile, cluster) group of every cluster: entry [num_cluster] is the
+ * frame's group count as the label kernel counted it) */
 int mot_debug_copy(mot_ctx* ctx, int which, int slot, void* dst, size_t bytes);
 /* the context's device-side parameter block (MotDevParams, mot_internal.h; bytes >= 512 is enough): what the on-device sweeps of the guarded
  * fast paths (tests/devcheck/sweep.hip -> libmot_sweep.so: test infrastructure, not in this library) are run with */

@@ -321,7 +321,7 @@ struct TrackBuffers {
   int step_mode;                // host only: MOT_TRACKER_AUTO / _SPLIT / _STREAM (mot_set_tracker_mode) — how mot_launch_track launches the step
   MotTrackParams tp;
 };
-enum { kTrackFlagCapacity = 1 };   // a birth was dropped: no free slot (more than T tracks alive or just dead) or E tracks ever created
+enum { kTrackFlagCapacity = 1 };   // a birth was dropped: no free slot (more than T tracks alive or just dead) or E tracks ever created; or (fused path) the box stage refused a frame of the stream (kFlag*): track_prep_body
 
 void mot_launch_track(const TrackBuffers& t, int batch, hipStream_t stream, bool prep_done = false);
 void mot_launch_box_finalize_prep(const MotDevParams& p, const ClusterBuffers& c, const TrackBuffers& tb, int batch, hipStream_t stream);

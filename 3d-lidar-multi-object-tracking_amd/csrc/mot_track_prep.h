@@ -64,6 +64,9 @@ static __device__ void track_prep_body_t(const TrackBuffers& tb, const int b) {
   if (!args.run) return;
   const MotTrackParams tp = tb.tp;
   const int M = tb.m_dev ? min(tb.m_dev[b * kCountsStride + kCntBoxes], kMaxBoxesPerFrame) : args.m;
+  // fused path: a frame the box stage refused (its capacity flags: too many clusters / boxes / groups / hull vertices) hands the tracker a cut or
+  // empty box list. The stream says so the way it reports a dropped birth: sticky MOT_E_CAPACITY from mot_get_tracks until it is reset.
+  if (tb.m_dev && tid == 0 && tb.m_dev[b * kCountsStride + kCntFlags] != 0) atomicOr(&tb.flags[b], (int)kTrackFlagCapacity);
   const float* boxes = tb.boxes + (long)b * tb.box_stride;   // (fused path: the same memory as `dst` below — no __restrict__ on either)
   if (tb.boxes_sensor) {
     // the tf step of the tracking node (OT/tracking/main.cpp:143-158: pcl_ros::transformPointCloud("/global", box, ...)): the host

@@ -385,7 +385,31 @@ int mot_fetch_tracks_async(mot_ctx* ctx, int batch, void* h_tracks, int max_per_
 
 /* read back results of the last mot_frames_dev / stage call for `slot` (host buffers; any may be NULL).
  * capacity_points: points each of elevated_xyzw / ground_xyzw / mask can hold; label_capacity: ints point_label can hold.
- * The counts are always delivered; MOT_E_CAPACITY (nothing copied) when a requested buffer is too small. */
+ * The counts are always delivered; MOT_E_CAPACITY (nothing copied) when a requested buffer is too small.
+ *
+ * PER-FRAME LIMITS OF THE CLUSTER AND BOX STAGE. A frame beyond one of them is REFUSED: the kernels stay inside their buffers, nothing outside
+ * the frame's slot is touched, and mot_get_ground / mot_get_clusters / mot_get_boxes / mot_box_markers / mot_cluster_products (and the stage calls
+ * that end in one of them: mot_box_fit, mot_box_fit_resident, mot_cluster_node_frame) answer MOT_E_CAPACITY with the limit's message for that
+ * slot — on every call, not only the first — until a new stage call or fused batch writes the slot; the next frame is judged on its own.
+ * With the tracker on (mot_frames_*, mot_sequence_dev) the tracker steps on the cut (possibly empty) box list of a refused frame and the
+ * stream's mot_get_tracks reports MOT_E_CAPACITY like a dropped birth: sticky until mot_reset / mot_reset_slot / mot_reset_tracks_slot.
+ *   - (tile, cluster) groups: at most max_points / 2 per frame, a group = the points of one cluster among 64 consecutive elevated points.
+ *     REACHABLE: a cloud in no order at all whose clusters are tiny (n elevated points in random order over >> 64 clusters give ~n groups:
+ *     more than max_points / 2 points of that kind). Scans in firing order stay far below (a few groups per tile). Raise max_points.
+ *   - clusters: 4096 per frame. REACHABLE with mot_params.dilate == 0 (preset OBJECT_TRACKING0: single occupied cells two cells apart, up to
+ *     10 000 on its 200 x 200 grid) and through mot_box_fit's num_cluster argument. NOT reachable through mot_cluster with the 3 x 3 dilation
+ *     of preset OBJECT_TRACKING: separate components are at least 4 cells apart, 63 x 63 = 3969 on the 250 x 250 grid.
+ *     mot_cluster itself delivers such a frame (the cluster stage has no limit of this kind). mot_box_fit_resident turns it down before a
+ *     kernel runs and leaves the refusal on slot 0: mot_get_boxes / mot_box_markers / mot_get_clusters / mot_cluster_products of slot 0 answer
+ *     it like a refusal raised on the device, until a stage call puts a new cloud there. mot_box_fit with num_cluster > 4096 is turned down
+ *     before anything of slot 0 is overwritten: the slot keeps the frame it held, and its getters what they answered before.
+ *   - accepted boxes: MOT_MAX_BOXES_PER_FRAME (1024) per frame. REACHABLE: 1025 clusters that pass the rule-based filter (about 33 000 points).
+ *   - convex hull: 384 vertices per cluster. NOT reachable: a cluster's picture lies in 901 x 901 pixels, and a convex lattice polygon there
+ *     (collinear points are not vertices) has at most 328 vertices — tests/test_emu_capacity.py computes the bound.
+ *   - L-shape sampling: 128 pre-generated raw draws per cluster for ram_points (1 .. 128, checked by mot_create) indices. NOT reachable: a draw
+ *     is rejected with probability below numPoints / 2^64 (the rejection sampling of std::uniform_int_distribution), so a cluster needs a
+ *     129th raw draw with probability below 128 x numPoints / 2^64 (2^-33 for a cluster of 16 million points): a guard, not a limit an
+ *     input can hit. */
 int mot_get_ground(mot_ctx* ctx, int slot, float* elevated_xyzw, int* n_elevated, float* ground_xyzw,
                    int* n_ground, uint8_t* mask, int capacity_points);
 int mot_get_clusters(mot_ctx* ctx, int slot, int32_t* grid, int* num_cluster, int32_t* point_label, int label_capacity);
@@ -399,7 +423,8 @@ int mot_get_boxes(mot_ctx* ctx, int slot, float* boxes, int max_boxes, int* n_bo
  * of 44 B x n_tracks + the live slots: consumers that only need the LIVE tracks every frame read mot_fetch_tracks_async /
  * mot_export_tracks[_packed]_dev instead, whose cost does not grow with the stream's age.
  * MOT_E_CAPACITY WITH the records delivered (n_tracks <= max_tracks) when births were dropped on this stream (no free track slot, or
- * max_tracks_ever tracks created): STICKY until mot_reset / mot_reset_slot / mot_reset_tracks_slot. */
+ * max_tracks_ever tracks created), or when the box stage refused a frame of this stream in a fused call with the tracker on (the per-frame
+ * limits above: the tracker stepped on an incomplete box list): STICKY until mot_reset / mot_reset_slot / mot_reset_tracks_slot. */
 int mot_get_tracks(mot_ctx* ctx, int slot, mot_track* tracks, int max_tracks, int* n_tracks);
 
 /* immUkfJpdaf for one frame of every slot 0..batch-1 with the boxes already on the DEVICE (global frame):
