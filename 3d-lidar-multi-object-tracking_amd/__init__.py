@@ -155,7 +155,8 @@ class Context:
         h = C.c_void_p()
         rc = self.lib.mot_create(C.byref(self.params), device, max_points, max_batch, max_tracks_total, C.byref(h))
         if rc:
-            raise MotError(rc, "mot_create failed (no GPU / bad arguments); this library has no CPU fallback")
+            why = self.lib.mot_last_error(None)
+            raise MotError(rc, "mot_create failed (no GPU / bad arguments); this library has no CPU fallback: " + (why.decode(errors="replace") if why else ""))
         self._h = h
 
     # ------------------------------------------------------------------ plumbing

@@ -190,7 +190,10 @@ ccl_kernel(MotDevParams p, ClusterBuffers c) {
       unsigned v = s_occ[i];
       unsigned prev = w > 0 ? s_occ[i - 1] : 0u, next = w < kRowWords - 1 ? s_occ[i + 1] : 0u;
       unsigned h = v | (v << 1) | (v >> 1) | (prev >> 31) | (next << 31);
-      int lo = w << 5;  // mask columns >= G
+      // mask columns >= G: invariant "no bit at or beyond column G in any word of the plane", which the run-start and popcount code below is
+      // written against. (A bit at column G would sit beside an occupied column G-1 of its own row: it starts no run, joins no two runs and
+      // gets no label — no output depends on it; the invariant is kept for the code, not for a result.)
+      int lo = w << 5;
       unsigned keep = (G - lo >= 32) ? 0xffffffffu : (G - lo <= 0 ? 0u : ((1u << (G - lo)) - 1u));
       s_aux[i] = (x < G) ? (h & keep) : 0u;
     }

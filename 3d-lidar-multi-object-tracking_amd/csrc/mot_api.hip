@@ -12,6 +12,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <cmath>
 #include <condition_variable>
 #include <mutex>
 #include <random>
@@ -294,12 +295,47 @@ extern "C" int mot_params_preset(int preset, mot_params* o) {
   return MOT_OK;
 }
 
+static std::string range_message(const char* field, float lo, float hi) {
+  char buf[96];
+  snprintf(buf, sizeof buf, "%s must be in %g .. %g m", field, (double)lo, (double)hi);
+  return buf;
+}
+
 static int make_dev_params(const mot_params& p, MotDevParams* d, std::string* err) {
   if (p.gauss_samples != 3) { *err = "gauss_samples must be 3"; return MOT_E_ARG; }
   if (p.num_grid < 8 || p.num_grid > MOT_MAX_GRID) { *err = "num_grid out of range"; return MOT_E_ARG; }
   if (p.ram_points < 1 || p.ram_points > 128) { *err = "ram_points must be in 1..128"; return MOT_E_ARG; }
   if (p.rng_mapping != MOT_RNG_LIBSTDCXX10 && p.rng_mapping != MOT_RNG_LIBSTDCXX11) { *err = "rng_mapping must be MOT_RNG_LIBSTDCXX10 or MOT_RNG_LIBSTDCXX11"; return MOT_E_ARG; }
+  // The declared domain (include/mot.h, "parameter domain"): inside it every stage answers as the reference does, outside it mot_create refuses.
+  {
+    const struct { const char* name; double v; } reals[] = {
+        {"r_min", p.r_min}, {"r_max", p.r_max}, {"t_hmin", p.t_hmin}, {"t_hmax", p.t_hmax}, {"t_hdiff", p.t_hdiff}, {"h_sensor", p.h_sensor},
+        {"ground_margin", p.ground_margin}, {"gauss_sigma", p.gauss_sigma}, {"crop_z_min", p.crop_z_min}, {"crop_z_max", p.crop_z_max},
+        {"crop_x_min", p.crop_x_min}, {"crop_x_max", p.crop_x_max}, {"crop_y_min", p.crop_y_min}, {"crop_y_max", p.crop_y_max}, {"roi_m", p.roi_m},
+        {"pic_scale", p.pic_scale}, {"sensor_height", p.sensor_height}, {"t_height_min", p.t_height_min}, {"t_height_max", p.t_height_max},
+        {"t_width_min", p.t_width_min}, {"t_width_max", p.t_width_max}, {"t_len_min", p.t_len_min}, {"t_len_max", p.t_len_max},
+        {"t_area_max", p.t_area_max}, {"t_ratio_min", p.t_ratio_min}, {"t_ratio_max", p.t_ratio_max}, {"min_len_ratio", p.min_len_ratio},
+        {"t_pt_per_m3", p.t_pt_per_m3}, {"gamma_g", p.gamma_g}, {"p_g", p.p_g}, {"p_d", p.p_d}, {"distance_thres", p.distance_thres},
+        {"bb_yaw_change_thres", p.bb_yaw_change_thres}, {"first_ego_yaw_offset", p.first_ego_yaw_offset}, {"seed_px", p.seed_px}, {"seed_py", p.seed_py}};
+    for (const auto& f : reals)
+      if (!std::isfinite(f.v)) { *err = std::string(f.name) + " must be finite"; return MOT_E_ARG; }
+  }
+  if (p.occ_min_count != 1 && p.occ_min_count != 2) { *err = "occ_min_count must be 1 or 2"; return MOT_E_ARG; }
+  if (p.dilate != 0 && p.dilate != 1) { *err = "dilate must be 0 or 1"; return MOT_E_ARG; }
+  if (!(p.gauss_sigma > 0)) { *err = "gauss_sigma must be > 0"; return MOT_E_ARG; }
+  if (!(p.roi_m >= MOT_ROI_M_MIN && p.roi_m <= MOT_ROI_M_MAX)) { *err = range_message("roi_m", MOT_ROI_M_MIN, MOT_ROI_M_MAX); return MOT_E_ARG; }
+  if (!(p.pic_scale > 0.f)) { *err = "pic_scale must be > 0"; return MOT_E_ARG; }
   if (!(p.pic_scale * p.roi_m <= 1000.f)) { *err = "pic_scale * roi_m must be <= 1000 pixels"; return MOT_E_ARG; }
+  if (!(p.r_min >= 0.f)) { *err = "r_min must be >= 0"; return MOT_E_ARG; }
+  if (!(p.r_max > p.r_min)) { *err = "r_max must be > r_min"; return MOT_E_ARG; }
+  if (!(p.r_max >= MOT_R_MAX_MIN && p.r_max <= MOT_R_MAX_MAX)) { *err = range_message("r_max", MOT_R_MAX_MIN, MOT_R_MAX_MAX); return MOT_E_ARG; }
+  // the guarded fast polar bin (kCellGuard, mot_internal.h) is proven for r_max / (r_max - r_min) <= MOT_POLAR_RATIO_MAX only;
+  // the test uses the fp32 span the kernels divide by
+  if (!(p.r_max <= MOT_POLAR_RATIO_MAX * (p.r_max - p.r_min))) {
+    char buf[160];
+    snprintf(buf, sizeof buf, "r_max / (r_max - r_min) must be <= %g: polar range too narrow for the guarded cell estimate", (double)MOT_POLAR_RATIO_MAX);
+    *err = buf; return MOT_E_ARG;
+  }
   memset(d, 0, sizeof *d);
   d->r_min = p.r_min; d->r_max = p.r_max; d->r_span = p.r_max - p.r_min;
   d->k_bin = (float)MOT_NUM_BIN / d->r_span;
@@ -524,8 +560,12 @@ static int create_impl(mot_ctx* c) {
   return MOT_OK;
 }
 
+// why the calling thread's last mot_create failed: there is no context to ask then (mot_last_error(NULL))
+static thread_local std::string g_create_err;
+
 extern "C" int mot_create(const mot_params* params, int device, int max_points, int max_batch, int max_tracks_total,
                           mot_ctx** out) {
+  g_create_err = "mot_create: null pointer, or max_points / max_batch / max_tracks_total out of range";
   if (!params || !out || max_points < 1 || max_points > kMaxPointsPerFrame || max_batch < 1 || max_tracks_total < 1) return MOT_E_ARG;
   *out = nullptr;
   mot_ctx* c = new mot_ctx();
@@ -546,10 +586,12 @@ extern "C" int mot_create(const mot_params* params, int device, int max_points, 
   if (rc == MOT_OK) rc = create_impl(c);
   if (rc != MOT_OK) {
     fprintf(stderr, "mot_create failed: %s\n", c->err.c_str());
+    g_create_err = c->err;
     mot_destroy(c);
     return rc;
   }
   *out = c;
+  g_create_err.clear();
   return MOT_OK;
 }
 
@@ -558,7 +600,7 @@ extern "C" int mot_get_params(const mot_ctx* c, mot_params* out) {
   *out = c->params;
   return MOT_OK;
 }
-extern "C" const char* mot_last_error(const mot_ctx* c) { return c ? c->err.c_str() : "null context"; }
+extern "C" const char* mot_last_error(const mot_ctx* c) { return c ? c->err.c_str() : (g_create_err.empty() ? "null context" : g_create_err.c_str()); }
 extern "C" void* mot_stream(mot_ctx* c) { return c ? (void*)c->stream : nullptr; }
 extern "C" int mot_synchronize(mot_ctx* c) {
   if (!c) return MOT_E_ARG;

@@ -374,6 +374,11 @@ MOT_HD bool mot_cart_cell(const MotDevParams& p, float x, float y, int* xI, int*
 // differs from that quotient by at most 4 roundings of a value below 256 (< 6.2e-5), so whenever the estimate is farther
 // than kCartGuard from an integer both floors agree. NaN fails every guard compare and lands in the exact path, which
 // drops it. tests/test_math_exact.py::test_fast_cart_cell_agrees checks the claim.
+// The admitted parameters keep this true: with V = G * xC / roiM < G <= 256 (mot_create: num_grid <= MOT_MAX_GRID), u = 2^-24,
+// the exact quotient carries the roundings of G * xC and of the divide, the estimate those of k_grid and of its multiply, each
+// at most u * V relative to the real V: |estimate - quotient| <= 4 u V (1 + 2u) < 6.2e-5 = kCartGuard / 4, whatever roiM is. roiM
+// enters only through over- and underflow: for MOT_ROI_M_MIN <= roiM <= MOT_ROI_M_MAX (1e-3 .. 1e6, mot_create) k_grid lies in
+// 8e-6 .. 2.6e5 and G * xC below 2.6e8, all normal numbers; a denormal xC gives V < 1e-30, far below the guard.
 constexpr float kCartGuard = 2.5e-4f;
 MOT_HD int mot_cart_bit_try(const MotDevParams& p, float x, float y) {
   const float xC = x + p.roi_half, yC = y + p.roi_half;
@@ -409,13 +414,36 @@ MOT_HD int mot_polar_cell_exact(const MotDevParams& p, float x, float y) {
 
 // Guarded fast path. The cell is floor() of two quantities; floor only depends on them to within the distance to the
 // nearest integer. Both are first estimated cheaply: the hardware's 1-ulp square root and one multiply instead of the
-// correctly rounded sqrtf and the IEEE divide for the bin (error < 4e-5 bins); a degree-13 odd polynomial for atan on
+// correctly rounded sqrtf and the IEEE divide for the bin (error < 5.8e-5 bins at the presets, derived below); a degree-13 odd polynomial for atan on
 // [0,1] with a hardware reciprocal for the channel (absolute error < 1e-6 rad => < 2e-5 channels). If either estimate is
 // within kCellGuard of an integer — or anything is NaN/Inf — the answer is -2 and the exact evaluation decides;
 // otherwise the estimate's floor IS the exact floor, and the range filter rMin < d < rMax is the test 0 <= bin < 120
 // (a distance within an ulp of either limit lands inside the guard). ~4e-4 of the points need the exact path.
 // tests/test_math_exact.py::test_fast_cell_agrees checks the claim on 2e8 points (square root and reciprocal perturbed by
 // +-1 ulp to cover v_sqrt_f32 / v_rcp_f32), the -m gpu parity tests check it end to end.
+//
+// The bin's error, and the polar ranges for which the guard is enough (mot_create refuses every other one: make_dev_params,
+// MOT_POLAR_RATIO_MAX in mot.h). Notation: u = 2^-24, K = MOT_NUM_BIN = 120, s = r_span = fl(rMax - rMin), d = sqrtf(x*x + y*y)
+// correctly rounded, d' the hardware's root of the same argument (within 1 ulp of the real root, so d' is d or a neighbour of d:
+// |d' - d| <= ulp(d) <= 2 u d), T = (d - rMin) K / s in real arithmetic, rho = rMax / s.
+//   exact     E  = fl(fl(fl(d - rMin) / s) * K)           = T (1 + e1)(1 + e2)(1 + e3),                    |e_i| <= u
+//   estimate  tb = fl(fl(d' - rMin) * k_bin), k_bin = fl(K / s)  = ((d' - rMin) K / s)(1 + e4)(1 + e5)(1 + e6)
+//   |tb - E| <= |d' - d| K / s + 6 u T (1 + 3u)  <=  2 u K d / s + 6 u T (1 + 3u)
+// Only T in [0, K + 1] matters (beyond it both sides are far from 0 .. K and answer "outside"), where d / s <= rho + 1 / K and
+// T <= K + 1. For rho >= 2 the range starts at rMin >= rMax / 2, so both subtractions are exact (Sterbenz) and two of the six
+// rounding terms vanish:
+//   rho <  2:  |tb - E| < u K (2 rho + 6) (1 + 1/K)  <  10 u K (1 + 1/K) = 7.2e-5
+//   rho <= 4:  |tb - E| < u K (2 rho + 4) (1 + 1/K) <=  12 u K (1 + 1/K) = 8.7e-5        (u K = 7.153e-6)
+// i.e. below kCellGuard = 1e-4 with a margin of 1.15 for rMax / (rMax - rMin) <= 4 — the declared domain — and the presets
+// (rho = 1.03) have 5.8e-5. When the estimate's fraction lies in (kCellGuard, 1 - kCellGuard), E therefore has the same floor.
+// The range filter follows from the same bound: tb > kCellGuard means (d' - rMin) K / s > 2 u K d / s (1 + 3u), so d' - rMin >
+// ulp(d) and d > rMin; tb < K - kCellGuard means d' < rMax - s (kCellGuard / K - 4u) < rMax - ulp(d), so d < rMax; tb beyond
+// either end by more than the guard puts E beyond it as well, and the exact evaluation answers -1 there too.
+// The sqrt term is attained (a neighbour of d IS what the hardware may return), the rounding terms seldom all at once: ranges with
+// 4 < rho < ~7 are refused because they are unproven, not because a wrong answer is known; from 2^-23 * 2^floor(log2 rMax) * K / s >
+// kCellGuard + 4 u K on (rho = 9.3 at rMax = 65) a wrong answer exists whatever the roundings do — the negative control of
+// tests/test_math_exact.py. rMax itself: MOT_R_MAX_MIN .. MOT_R_MAX_MAX (1e-3 .. 1e6 m) keeps x*x + y*y, s and k_bin normal
+// numbers for every d near the range, which the relative-error model above assumes.
 constexpr float kCellGuard = 1.0e-4f;
 MOT_HD int mot_polar_cell_fast(const MotDevParams& p, float x, float y, float distance_approx, float rcp_mx) {
   // bin

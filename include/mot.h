@@ -73,8 +73,38 @@ enum { MOT_MASK_DROPPED = 0, MOT_MASK_GROUND = 1, MOT_MASK_ELEVATED = 2 };
 /* by-products of groundRemove that nothing downstream of it reads (mot_set_fused_outputs) */
 enum { MOT_OUT_GROUND = 1, /* groundCloud */ MOT_OUT_MASK = 2, /* the per-point classification */ MOT_OUT_LABELS = 4 /* the cluster label of every elevated point */ };
 
+/* ---- parameter domain ------------------------------------------------------------------------------------------------
+ * The rule: a parameter set is either answered exactly as the reference answers it, or mot_create() refuses it with
+ * MOT_E_ARG and a message that names the field. What mot_create() admits:
+ *   every float / double field   finite (no NaN, no Inf)
+ *   gauss_samples                3;    gauss_sigma > 0
+ *   r_min, r_max                 0 <= r_min < r_max, MOT_R_MAX_MIN <= r_max <= MOT_R_MAX_MAX, and
+ *                                r_max / (r_max - r_min) <= MOT_POLAR_RATIO_MAX (the same as r_min <= 0.75 r_max; the difference
+ *                                is the fp32 one). The streaming kernels estimate a point's polar bin with the hardware's 1-ulp
+ *                                square root, and that estimate's error, in bins, grows with this ratio: up to the bound it is
+ *                                proven to stay inside the guard band that sends a point to the exact evaluation
+ *                                (csrc/mot_internal.h, kCellGuard: the derivation). A narrower range is REFUSED, not run on a
+ *                                slower path.
+ *   num_grid                     8 .. MOT_MAX_GRID
+ *   roi_m                        MOT_ROI_M_MIN .. MOT_ROI_M_MAX (the guarded Cartesian cell, kCartGuard, holds for every such
+ *                                roi_m: its bound depends on num_grid <= 256 only)
+ *   occ_min_count                1 or 2 (the device keeps the two bit planes "cell seen >= 1" and ">= 2" and nothing else)
+ *   dilate                       0 or 1
+ *   pic_scale                    > 0, pic_scale * roi_m <= 1000 pixels
+ *   ram_points                   1 .. 128;   rng_mapping  MOT_RNG_LIBSTDCXX10 or MOT_RNG_LIBSTDCXX11
+ * Every other field is taken as it is. The two presets are pinned to the reference's own build; away from them "as the
+ * reference answers" means its restatement with the same constants (oracle/), since the reference compiles its constants in.
+ * What the suite establishes away from the presets: the ground, cluster and box stages over the lattice of tests/param_cases.py,
+ * bit for bit; the tracker's thresholds (life_time_thres, seed_box_index, distance_thres, bb_yaw_change_thres, gamma_g, p_d, p_g)
+ * on short sequences chosen so that each of them changes the answer. */
+#define MOT_POLAR_RATIO_MAX 4.0f
+#define MOT_R_MAX_MIN 1.0e-3f
+#define MOT_R_MAX_MAX 1.0e6f
+#define MOT_ROI_M_MIN 1.0e-3f
+#define MOT_ROI_M_MAX 1.0e6f
+
 /* All tunables of the path. The reference keeps them as file-scope globals; file:line in the
- * comments. mot_params_preset() fills either preset. */
+ * comments. mot_params_preset() fills either preset. Their admitted values: "parameter domain" above. */
 typedef struct mot_params {
   /* ---- ground stage: OT/src/groundremove/ground_removal.cpp:24-33 ---- */
   float r_min;          /* rMin 3.4 */
@@ -204,6 +234,8 @@ int mot_stream_save(mot_ctx* ctx, int slot, void* blob, size_t capacity, size_t*
 int mot_stream_load(mot_ctx* ctx, int slot, const void* blob, size_t bytes);
 /* the parameters the context was created with */
 int mot_get_params(const mot_ctx* ctx, mot_params* out);
+/* ctx == NULL: why the calling thread's last mot_create() failed (which field of mot_params it refused). That string belongs
+ * to the calling thread and is valid until its next mot_create(); a context's string until the next call on the context. */
 const char* mot_last_error(const mot_ctx* ctx);
 int mot_synchronize(mot_ctx* ctx);
 /* the HIP stream (hipStream_t) the context launches on, for callers that enqueue their own work */

@@ -37,7 +37,7 @@ __device__ __forceinline__ float ulp_step(float f, int k) {   // k representable
   return mot_i2f(i);
 }
 
-// mode 0: uniform random in [-R, R]^2     (R = 130 polar / 1.2 * roi_half Cartesian)
+// mode 0: uniform random in [-R, R]^2     (R = rMax * 13 / 12 polar: 130 at the presets / 1.2 * roi_half Cartesian)
 // mode 1: regular lattice over the same square (index -> (i % side, i / side))
 // mode 2: points ON the cell boundaries, moved by -3..+3 steps of 1..64 ulp in x and in y:
 //           polar: every channel spoke (k * 2 pi / 80) at random radii, and every bin ring (rMin + k * span / 120) at random angles
@@ -47,7 +47,7 @@ __global__ void MOT_LAUNCH_BOUNDS(256)
 sweep_kernel(MotDevParams p, int what, int mode, unsigned long long seed, unsigned long long count, int per_thread, SweepStats* out) {
   const unsigned long long t0 = ((unsigned long long)blockIdx.x * 256 + threadIdx.x) * (unsigned long long)per_thread;
   unsigned long long n_und = 0, n_bad = 0, n_pts = 0;
-  const float R = what != 1 ? 130.0f : 1.2f * p.roi_half;
+  const float R = what != 1 ? p.r_max + p.r_max / 12.0f : 1.2f * p.roi_half;   // polar: 13/12 of rMax (exactly 130 at the presets' rMax = 120)
   const unsigned long long side = 1ull << 16;
   for (int j = 0; j < per_thread; j++) {
     const unsigned long long i = t0 + j;

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import hiprt
+import param_cases as PC
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "devcheck"))
 
@@ -39,6 +40,32 @@ def test_fast_cells_agree_with_exact_on_device(mot, hip_lib):
                 assert und < (0.999 if mode == 2 else 3e-3), (what, mode, und)   # the exact path stays rare away from boundaries (mode 2 sits ON them)
                 total += count
     assert total > 4e9
+
+
+@pytest.mark.parametrize("k", range(len(PC.GRID_SETTINGS)), ids=lambda k: "G%d-roi%g-r%g-%g" % (PC.GRID_SETTINGS[k] + PC.POLAR_RANGES[k % len(PC.POLAR_RANGES)]))
+def test_fast_cells_agree_with_exact_on_device_off_the_presets(mot, hip_lib, k):
+    """the same sweep with contexts created AWAY from the presets (tests/param_cases.py: every (num_grid, roi_m) pair of the grid lattice, each
+    with one of the polar ranges of the declared domain in turn, its edge r_max / (r_max - r_min) = 4 included): 2^26 points for each of the
+    nine (what, mode) entries per setting, the real v_sqrt_f32 / v_rcp_f32. The polar and the Cartesian cell do not depend on each other, so the ranges
+    rotate over the grids (each range meets 4 or 5 of them) instead of every pair being swept"""
+    import build_sweep
+    S = C.CDLL(build_sweep.build())
+    (G, roi), (r_min, r_max) = PC.GRID_SETTINGS[k], PC.POLAR_RANGES[k % len(PC.POLAR_RANGES)]
+    count = 1 << 26
+    with mot.Context(mot.params(k % 2, num_grid=G, roi_m=roi, pic_scale=900.0 / roi, r_min=r_min, r_max=r_max), max_points=1024) as c:
+        dp = (C.c_char * 512)()
+        assert hip_lib.mot_debug_dev_params(c._h, dp, C.c_size_t(512)) == 0
+        st = (C.c_ulonglong * 8)()
+        for what, mode in ((0, 0), (0, 1), (0, 2), (1, 0), (1, 1), (1, 2), (2, 0), (2, 1), (2, 2)):
+            rc = S.mot_sweep_run(dp, what, mode, C.c_ulonglong(7654321 + 17 * mode + k), C.c_ulonglong(count), st)
+            assert rc == 0
+            assert st[0] == count
+            x = np.array([st[3] & 0xffffffff], np.uint32).view(np.float32)[0]; y = np.array([st[3] >> 32], np.uint32).view(np.float32)[0]
+            assert st[2] == 0, f"what={what} mode={mode} G={G} roi={roi} r={r_min}..{r_max}: {st[2]} mismatches, first at ({x!r}, {y!r}) fast/exact {st[4] & 0xffffffff:#x}/{st[4] >> 32:#x}"
+            und = st[1] / count
+            # the exact path stays rare away from boundaries (mode 2 sits ON them). The share of undecided points is the guard band's share of a
+            # cell: 2 * kCartGuard = 5e-4 per axis and 2 * kCellGuard = 2e-4 per polar axis, whatever the grid — the presets' bound holds
+            assert und < (0.999 if mode == 2 else 3e-3), (what, mode, und)
 
 
 def test_polar_grid_intermediates_on_device(mot, hip_lib, oracle, synth):

@@ -57,7 +57,8 @@ def test_emu_ram_points_edge(env, oracle):
 
 
 def test_hull_limit_is_out_of_reach():
-    """kMaxHull against a computed bound. A cluster's picture lies in 901 x 901 pixels (box.hip: kMaxHullIn = 2 * 901): a span of 900 steps.
+    """kMaxHull against a computed bound. A cluster's picture lies in 901 x 901 pixels at the presets (box.hip: kMaxHullIn = 2 * 901): a span of 900
+    steps (bound 328); in 1001 x 1001 pixels at the largest pic_scale * roi_m mot_create admits (bound 352).
     The bound counts STRICTLY convex polygons; the hull code must therefore drop collinear points — peel_chain keeps a point only on a strict
     turn (`cr < 0` / `cr > 0`), which is checked here against the source as well."""
     src = open(os.path.join(CSRC, "box.hip")).read()
@@ -67,4 +68,8 @@ def test_hull_limit_is_out_of_reach():
     bound = CC.lattice_polygon_vertex_bound(900)
     print("vertex bound of a convex lattice polygon in 901 x 901 pixels:", bound)
     assert 300 < bound <= k_max_hull
+    # mot_create admits pic_scale * roi_m up to 1000: a picture of 1001 x 1001 pixels, a span of 1000 steps
+    wide = CC.lattice_polygon_vertex_bound(1000)
+    print("vertex bound of a convex lattice polygon in 1001 x 1001 pixels:", wide)
+    assert bound <= wide <= k_max_hull
     assert [CC.lattice_polygon_vertex_bound(s) for s in (1, 2, 3)] == [4, 6, 8]   # tight where it can be checked by hand: unit square, hexagon, octagon

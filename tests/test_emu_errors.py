@@ -28,6 +28,28 @@ def test_create_rejects_bad_arguments(mot, emu):
     for field, value in (("num_grid", 4), ("num_grid", 100000), ("gauss_samples", 5), ("ram_points", 0), ("pic_scale", 1000.0)):
         q = mot.params(0, lib=L, **{field: value})
         assert L.mot_create(C.byref(q), 0, 1024, 1, 16, C.byref(h)) == mot.MOT_E_ARG, field
+    # the declared parameter domain (include/mot.h): one case per refusal, each with a message that names the field
+    nan, inf = float("nan"), float("inf")
+    for over, names in ((dict(occ_min_count=0), ["occ_min_count"]), (dict(occ_min_count=3), ["occ_min_count"]), (dict(dilate=2), ["dilate"]), (dict(dilate=-1), ["dilate"]),
+                        (dict(r_min=-0.5), ["r_min"]), (dict(r_min=120.0), ["r_max", "r_min"]), (dict(r_min=130.0), ["r_max", "r_min"]),
+                        (dict(r_min=115.0), ["r_max", "r_min"]),                    # r_max / (r_max - r_min) = 24: the guarded polar bin is not proven there
+                        (dict(r_min=45.5, r_max=60.0), ["r_max", "r_min"]),         # just beyond the ratio 4
+                        (dict(r_max=1e-4, r_min=0.0), ["r_max"]), (dict(r_max=1e7), ["r_max"]),
+                        (dict(roi_m=0.0), ["roi_m"]), (dict(roi_m=-30.0), ["roi_m"]), (dict(roi_m=1e-4, pic_scale=1.0), ["roi_m"]), (dict(roi_m=1e7, pic_scale=1e-5), ["roi_m"]),
+                        (dict(pic_scale=0.0), ["pic_scale"]), (dict(pic_scale=-18.0), ["pic_scale"]), (dict(gauss_sigma=0.0), ["gauss_sigma"]), (dict(gauss_sigma=-1.0), ["gauss_sigma"]),
+                        (dict(r_min=nan), ["r_min"]), (dict(r_max=inf), ["r_max"]), (dict(roi_m=nan), ["roi_m"]), (dict(pic_scale=nan), ["pic_scale"]),
+                        (dict(t_hmin=nan), ["t_hmin"]), (dict(t_hmax=inf), ["t_hmax"]), (dict(t_hdiff=nan), ["t_hdiff"]), (dict(h_sensor=-inf), ["h_sensor"]),
+                        (dict(ground_margin=nan), ["ground_margin"]), (dict(gauss_sigma=inf), ["gauss_sigma"]), (dict(crop_z_min=nan), ["crop_z_min"]),
+                        (dict(sensor_height=nan), ["sensor_height"]), (dict(t_area_max=inf), ["t_area_max"]), (dict(t_pt_per_m3=nan), ["t_pt_per_m3"]),
+                        (dict(gamma_g=nan), ["gamma_g"]), (dict(p_d=inf), ["p_d"]), (dict(distance_thres=nan), ["distance_thres"]), (dict(seed_px=nan), ["seed_px"])):
+        for preset in (0, 1):
+            q = mot.params(preset, lib=L, **over)
+            with pytest.raises(mot.MotError) as e:
+                mot.Context(q, lib_path=lib, max_points=1024)
+            assert e.value.code == mot.MOT_E_ARG and any(nm in str(e.value) for nm in names), (over, str(e.value))
+    # ... and the edge of the domain is inside it
+    for over in (dict(r_min=45.0, r_max=60.0), dict(r_min=0.0), dict(occ_min_count=1, dilate=1), dict(occ_min_count=2, dilate=0), dict(roi_m=1e-3, pic_scale=1.0), dict(ground_margin=0.0)):
+        mot.Context(mot.params(0, lib=L, **over), lib_path=lib, max_points=1024).close()
     assert not h.value
 
 

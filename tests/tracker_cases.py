@@ -136,6 +136,28 @@ def blinking_world(seed, spots, frames):
         yield np.array(boxes, np.float32).reshape(-1, 8, 3), 1.0e9 + f * 1.0e5, 1.0 + 0.5 * np.sin(0.01 * f), 0.0005 * f
 
 
+def fast_lanes(seed, frames, lanes=5, speeds=(10.3, 11.5), turns=(0.3, 1.2), start=(5.0, 7.0)):
+    """objects on lanes 15 m apart that drive along x through the origin at 10.3 .. 11.5 m/s (more than a metre a frame; meant for a dozen frames: near the
+    origin an fp32 ulp of x is small against the step, so a last bit of a coordinate moves the estimated speed by less than 1e-6 of it), their boxes turned against the direction of
+    travel by up to 1.2 rad: once such a track is confirmed, the box inside its gate lies MORE than 1 m from the track's last position — the
+    situation in which distance_thres decides whether the track takes the box over (getNearestEuclidBBox, imm_ukf_jpda.cpp:396-463) — and
+    the box's yaw differs from the track's by more than the preset's bb_yaw_change_thres"""
+    import test_emu_tracker_random as TR
+    rng = np.random.default_rng(seed)
+    sign = np.where(rng.random(lanes) < 0.5, -1.0, 1.0)
+    speed = rng.uniform(speeds[0], speeds[1], lanes) * sign
+    x0 = -sign * rng.uniform(start[0], start[1], lanes); y0 = (np.arange(lanes) - lanes / 2) * 15.0 + rng.uniform(-2, 2, lanes)
+    turn = rng.uniform(turns[0], turns[1], lanes) * np.where(rng.random(lanes) < 0.5, -1.0, 1.0)
+    size = rng.uniform(1.5, 4.5, (lanes, 2))
+    for f in range(frames):
+        # every fourth frame a lane's box arrives smaller and turned by half a radian (a partial view): the frame-to-frame yaw change that
+        # bb_yaw_change_thres judges (updateBB, imm_ukf_jpda.cpp:565-653) lies between the preset's 0.2 rad and pi / 2
+        part = [f >= 6 and f % 4 == k % 4 for k in range(lanes)]
+        boxes = [TR.box(x0[k] + speed[k] * 0.1 * f + rng.normal(0, 0.02), y0[k] + rng.normal(0, 0.02), size[k, 0] * (0.9 if part[k] else 1.0), size[k, 1] * (0.9 if part[k] else 1.0),
+                        (0.0 if sign[k] > 0 else np.pi) + turn[k] + (0.5 if part[k] else 0.0) + rng.normal(0, 0.01), -0.3) for k in range(lanes)]
+        yield np.array(boxes, np.float32).reshape(-1, 8, 3), 1.0e9 + f * 1.0e5, 0.0, 0.0
+
+
 def long_run_bounded_slots(mot, oracle, lib_path=None, frames=1500, slots=16, spots=10, seed=3, state_every=25, min_ever_factor=4, max_chaos_restarts=0,
                            ref_frames=500):
     """SURVEY.md H14 / the reference never frees a track: a long run on `slots` track slots must give what the oracle gives with
