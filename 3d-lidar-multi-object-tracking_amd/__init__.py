@@ -19,6 +19,7 @@ LIB_PATH = os.path.join(_HERE, "libmot_hip.so")
 MOT_OK, MOT_E_ARG, MOT_E_CAPACITY, MOT_E_HIP, MOT_E_STATE = 0, 1, 2, 3, 4
 MOT_MAX_BOXES_PER_FRAME = 1024   # include/mot.h
 MOT_TRACKER_AUTO, MOT_TRACKER_SPLIT, MOT_TRACKER_STREAM = 0, 1, 2   # mot_set_tracker_mode (include/mot.h)
+MOT_ORDER_SCAN, MOT_ORDER_ANY = 0, 1   # mot_set_point_order (include/mot.h)
 PRESET_OBJECT_TRACKING, PRESET_OBJECT_TRACKING0 = 0, 1
 MASK_DROPPED, MASK_GROUND, MASK_ELEVATED = 0, 1, 2
 NUM_CHANNEL, NUM_BIN = 80, 120
@@ -76,7 +77,7 @@ EXPORTS = (
     "mot_get_boxes", "mot_get_tracks", "mot_export_tracks_dev", "mot_side_params_default", "mot_cluster_products", "mot_cluster_products_host", "mot_box_markers", "mot_decode_pointcloud2_dev", "mot_time_stage",
     "mot_ground_remove_pointcloud2", "mot_box_fit_resident", "mot_frame_pointcloud2",
     "mot_reset_slot", "mot_stream_snapshot_size", "mot_stream_save", "mot_stream_load", "mot_frames_host", "mot_frames_host_xyz", "mot_frames_host_pointcloud2", "mot_wait_uploads", "mot_host_alloc", "mot_host_free", "mot_fetch_tracks_async",
-    "mot_track_steps_dev", "mot_profile_kernel", "mot_profile_read", "mot_get_params", "mot_set_fused_outputs", "mot_set_tracker_mode", "mot_set_trace_ranges", "mot_reset_tracks_slot", "mot_export_tracks_packed_dev", "mot_set_launch_graphs",
+    "mot_track_steps_dev", "mot_profile_kernel", "mot_profile_read", "mot_get_params", "mot_set_fused_outputs", "mot_set_point_order", "mot_set_tracker_mode", "mot_set_trace_ranges", "mot_reset_tracks_slot", "mot_export_tracks_packed_dev", "mot_set_launch_graphs",
     "mot_cluster_node_frame", "mot_ground_node_frame",
     "mot_gather_unique_id", "mot_gather_create", "mot_gather_contribute", "mot_gather_result", "mot_gather_synchronize", "mot_gather_destroy", "mot_gather_last_error",
 )
@@ -221,6 +222,11 @@ class Context:
     def set_fused_outputs(self, flags: int):
         """which by-products of the ground stage the fused entry points write (OUT_GROUND | OUT_MASK | OUT_LABELS; default 0: on demand)"""
         self._ck(self.lib.mot_set_fused_outputs(self._h, flags))
+
+    def set_point_order(self, order: int):
+        """MOT_ORDER_SCAN (default) or MOT_ORDER_ANY: clouds in no point order — the box stage regroups the elevated points by cluster on the device
+        first; same results, every output in input order, no frame refused for its (tile, cluster) groups"""
+        self._ck(self.lib.mot_set_point_order(self._h, int(order)))
 
     def _track_buffer(self, slot, max_tracks):
         """records a call can deliver: one per track EVER created on the stream, which outgrows the number of slots on a long run"""

@@ -470,7 +470,8 @@ cluster_index_kernel(ClusterBuffers c) {
       //   2. a wave per cluster ranks its bucket by TILE: a cluster has at most one group per tile, so a byte table tile -> points of that group
       //      (2048 tiles per pass) and its prefix sums over 32-tile blocks give every group "groups / points of my cluster in earlier tiles" with
       //      one table walk of at most 31 bytes — O(groups + tiles / 64) per cluster. Buckets of up to 64 groups are ranked in registers.
-      uint2* __restrict__ gbuck = reinterpret_cast<uint2*>(c.poly + (long)b * c.cap);   // {tile << 8 | points, index of the group}
+      // (MOT_ORDER_ANY in a small context has more group slots than the pool holds entries: buckets of its own, mot_internal.h)
+      uint2* __restrict__ gbuck = c.group_scratch ? c.group_scratch + (long)b * c.group_cap : reinterpret_cast<uint2*>(c.poly + (long)b * c.cap);   // {tile << 8 | points, index of the group}
       for (int ci = tid; ci < num_cluster; ci += kIndexBlock) s_start[ci] = cgstart[ci];   // running fill position of every bucket
       __syncthreads();
       for (int e = tid; e < E; e += kIndexBlock) {
@@ -1332,21 +1333,8 @@ __global__ void MOT_LAUNCH_BOUNDS(256)
 point_labels_kernel(MotDevParams p, ClusterBuffers c, int b) {
   const int n = c.counts[b * kCountsStride + kCntElev];
   const int num_cluster = c.counts[b * kCountsStride + kCntClusters];
-  const GridLabel* __restrict__ grid = c.grid + (long)b * (MOT_MAX_GRID * MOT_MAX_GRID);
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    int cell;
-    if (c.ecell) {
-      const unsigned e = c.ecell[(long)b * c.cap + i];
-      cell = e != 0xffffu ? (int)((e >> 8) * (unsigned)p.num_grid + (e & 255u)) : -1;
-    } else {
-      const float4 q = mot_load_xyz(c.elevated + (long)b * c.cap, i, c.elevated_packed);
-      const int bit = mot_cart_bit(p, q.x, q.y);
-      cell = bit >= 0 ? (bit >> 8) * p.num_grid + (bit & 255) : -1;
-    }
-    int lab = cell >= 0 ? grid[cell] : 0;
-    if (lab < 0 || lab > num_cluster) lab = 0;
-    c.label[(long)b * c.cap + i] = lab;
-  }
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
+    c.label[(long)b * c.cap + i] = mot_point_label(p, c, b, i, num_cluster);
 }
 void mot_launch_point_labels(const MotDevParams& p, const ClusterBuffers& c, int slot, int max_n, hipStream_t stream) {
   int blocks = (max_n + 255) / 256;

@@ -28,6 +28,7 @@
 //   slot0_taken (mot_cluster, _box_fit, _cluster_products_host, _cluster_node_frame)  0        no           FromPoints                    no     Foreign                       no
 //   labels_written (mot_get_clusters on demand, mot_cluster with labels)           one         -            Ready                         -      -                             -
 //   box_stage (mot_box_fit, _box_fit_resident, _cluster_node_frame once it fit)    one         -            Ready                         yes    -                             -
+//   (fused_batch and box_stage also record `regrouped`: whether the box stage ran on the cluster-ordered copy, MOT_ORDER_ANY; every transition that clears `boxes` clears it)
 //   compaction_rerun (mot_get_ground on demand, mot_time_stage)                    0..batch-1  as run       -                             -      as run, unless Foreign        -
 //   describe_batch (set_batch): the last_* input description. Nothing is vouched for in a slot at or beyond last_batch that needs the batch's input.
 // per-point labels: not computed, the cloud was uploaded by a stage-wise call (no cell codes: mot_get_clusters computes them from the points) / not computed, cloud and cell
@@ -41,6 +42,8 @@ struct SlotState {
   LabelState labels = kLabelsFromPoints;
   bool boxes = false;                     // the box stage's products (boxes, cluster order, groups) belong to the cloud now resident in the slot
   GroundState ground = kGroundNone;
+  bool regrouped = false;                 // the box stage ran in MOT_ORDER_ANY: its products (groups, cluster order, first / extreme point indices) index the slot's
+                                          // cluster-ordered COPY of the cloud, not the cloud itself. Meaningful while `boxes`; every reader that walks clusters asks.
 };
 struct Residency {
   std::vector<SlotState> slots;
@@ -53,9 +56,9 @@ struct Residency {
   static bool fused_keeps_ground(int outputs) { return (outputs & (MOT_OUT_GROUND | MOT_OUT_MASK)) == (MOT_OUT_GROUND | MOT_OUT_MASK); }
   // a fused call over slots 0..batch-1 was issued: what those slots hold from now on (the slots beyond keep what an earlier, larger batch left). Host
   // state, so it also holds when a captured graph is replayed: every reader built from cluster_buffers afterwards is told the layout
-  void fused_batch(int batch, int outputs) {
+  void fused_batch(int batch, int outputs, bool regrouped) {
     last_fused = true;
-    for (int b = 0; b < batch; b++) slots[b] = {fused_packs(outputs), (outputs & MOT_OUT_LABELS) ? kLabelsReady : kLabelsFromCells, true, fused_keeps_ground(outputs) ? kGroundResident : kGroundNone};
+    for (int b = 0; b < batch; b++) slots[b] = {fused_packs(outputs), (outputs & MOT_OUT_LABELS) ? kLabelsReady : kLabelsFromCells, true, fused_keeps_ground(outputs) ? kGroundResident : kGroundNone, regrouped};
   }
   // a stage-wise ground stage ran on slot 0 (float4 records); without a mask a later mot_get_ground that asks for one answers MOT_E_STATE
   void ground_stage(bool with_mask) { last_fused = false; slots[0] = {false, kLabelsFromPoints, false, with_mask ? kGroundResident : kGroundNone}; }
@@ -65,7 +68,7 @@ struct Residency {
   // the label kernel ran on the slot's cloud; written = false: in the fused geometry without per-point labels (mot_time_stage)
   void labels_written(int slot, bool written = true) { slots[slot].labels = written ? kLabelsReady : kLabelsFromCells; }
   // the box stage (label kernel included) ran on the slot's cloud: mot_box_markers / mot_get_boxes / mot_get_clusters may read its products
-  void box_stage(int slot) { slots[slot].labels = kLabelsReady; slots[slot].boxes = true; }
+  void box_stage(int slot, bool regrouped) { slots[slot].labels = kLabelsReady; slots[slot].boxes = true; slots[slot].regrouped = regrouped; }
   // the compaction of the last batch was run again: same points in the same order (what the later stages hold stays valid), in the layout and with the outputs
   // of this run. (A slot a stage-wise call has taken since stays refused: only mot_time_stage gets here in that state.)
   void compaction_rerun(int batch, bool packed, bool ground_and_mask) {
@@ -75,6 +78,7 @@ struct Residency {
   bool labels_ready(int slot) const { return slots[slot].labels == kLabelsReady; }
   bool cells_usable(int slot) const { return slots[slot].labels == kLabelsFromCells; }
   bool boxes_valid(int slot) const { return slots[slot].boxes; }
+  bool regrouped(int slot) const { return slots[slot].boxes && slots[slot].regrouped; }
   bool ground_foreign(int slot) const { return slots[slot].ground == kGroundForeign; }
   // (a slot beyond the last batch: whatever an earlier batch left is not vouched for)
   bool ground_readable(int slot) const { return slots[slot].ground == kGroundResident && slot < last_batch; }
@@ -128,6 +132,17 @@ struct mot_ctx {
   SortedGroup* d_gsorted = nullptr;
   int* d_cluster_gstart = nullptr;
   int* d_pix = nullptr;
+  // MOT_ORDER_ANY (mot_set_point_order): allocated at the first request, kept until mot_destroy
+  int point_order = MOT_ORDER_SCAN;
+  unsigned short* d_rg_key = nullptr;
+  unsigned* d_rg_tmp = nullptr;
+  int* d_rg_hist = nullptr;
+  float4* d_rg_xyz = nullptr;          // the cluster-ordered copy of every slot's elevated cloud (12-byte points) ...
+  unsigned short* d_rg_cell = nullptr; // ... and of its cells
+  PointGroup* d_rg_groups = nullptr;   // group buffers of the mode's own, only in contexts whose cap / 2 is below the mode's group bound
+  SortedGroup* d_rg_gsorted = nullptr;
+  uint2* d_rg_gscratch = nullptr;
+  int rg_group_cap = 0;
   // cluster-node side products (allocated on first use)
   int* d_side_cell = nullptr;
   float4* d_side_cloud = nullptr;
@@ -184,7 +199,7 @@ struct mot_ctx {
   char* h_argring = nullptr;           // pinned, kArgRing blocks of arg_bytes
   size_t arg_bytes = 0, arg_off_targs = 0, arg_off_ego = 0, arg_off_launch = 0;
   // launch sequences captured as hipGraphs (contexts of few streams: the per-frame latency path), keyed by launch geometry
-  struct GraphKey { int batch, chunks, tracker, outputs; };
+  struct GraphKey { int batch, chunks, tracker, outputs, order; };
   struct GraphEntry { GraphKey key; void* exec; };
   std::vector<GraphEntry> graphs;
   int graph_mode = 0;                  // 0 off, 1 on; turned off for good when a capture fails
@@ -392,7 +407,7 @@ extern "C" void mot_destroy(mot_ctx* c) {
   for (int i = 0; i < mot_ctx::kArgRing; i++) if (c->arg_ev[i]) (void)hipEventDestroy(c->arg_ev[i]);
   if (c->h_argring) (void)hipHostFree(c->h_argring);
   void* bufs[] = {c->d_in, c->d_argblk, c->d_ecell, c->d_pairs, c->d_pair_count, c->d_hg, c->d_cell, c->d_desc, c->d_ticket, c->d_elev, c->d_ground, c->d_mask, c->d_counts,
-                  c->d_plane_a, c->d_plane_b, c->d_ccl_parent, c->d_occ_list, c->d_occ_count, c->d_grid, c->d_label, c->d_stats, c->d_cand, c->d_boxes, c->d_box_cluster, c->d_rng, c->d_poly, c->d_groups, c->d_cluster_start, c->d_cluster_gstart, c->d_order, c->d_gsorted, c->d_pix, c->d_wgtab, c->d_side_cell, c->d_side_cloud, c->d_side_obs, c->d_side_cost, c->d_side_counts, c->d_side_chunks, c->d_markers, c->d_raw,
+                  c->d_plane_a, c->d_plane_b, c->d_ccl_parent, c->d_occ_list, c->d_occ_count, c->d_grid, c->d_label, c->d_stats, c->d_cand, c->d_boxes, c->d_box_cluster, c->d_rng, c->d_poly, c->d_groups, c->d_cluster_start, c->d_cluster_gstart, c->d_order, c->d_gsorted, c->d_pix, c->d_wgtab, c->d_rg_key, c->d_rg_tmp, c->d_rg_hist, c->d_rg_xyz, c->d_rg_cell, c->d_rg_groups, c->d_rg_gsorted, c->d_rg_gscratch, c->d_side_cell, c->d_side_cloud, c->d_side_obs, c->d_side_cost, c->d_side_counts, c->d_side_chunks, c->d_markers, c->d_raw,
                   c->d_tracks, c->d_nt, c->d_tboxes, c->d_gate, c->d_prog, c->d_live, c->d_tout, c->d_tflags, c->d_nlive, c->d_pos, c->d_slot_of, c->d_tomb, c->d_used, c->d_zomb, c->d_nzomb, c->d_cp, c->d_items, c->d_nitems};
   for (void* b : bufs) if (b) (void)hipFree(b);
   if (c->h_counts) (void)hipHostFree(c->h_counts);
@@ -436,7 +451,59 @@ static ClusterBuffers cluster_buffers(mot_ctx* c, int slot = -1) {
   b.box_cluster = c->d_box_cluster; b.rng = c->d_rng; b.poly = c->d_poly; b.groups = c->d_groups; b.group_cap = c->cap / 2; b.cluster_start = c->d_cluster_start; b.cluster_gstart = c->d_cluster_gstart; b.order = c->d_order; b.gsorted = c->d_gsorted;
   b.pix = c->d_pix; b.wgtab = c->d_wgtab; b.max_wg = c->max_wg;
   b.ecell = nullptr;   // stage-wise: the label kernel computes the cells itself
+  b.group_scratch = nullptr;
   return b;
+}
+
+// ---------------------------------------------------------------------------------------- MOT_ORDER_ANY
+// What the box stage — and every later reader that walks clusters (mot_box_markers) — is handed for a slot whose points were regrouped: the same buffers
+// with `elevated`, `ecell` pointing at the cluster-ordered copy, so that pix, first, the groups and cluster_gstart index the copy consistently. The label
+// kernel writes no per-point labels there (they would come out in copy order): regroup_label_kernel has written them in input order.
+static ClusterBuffers regrouped_view(const mot_ctx* c, ClusterBuffers cb) {
+  cb.elevated = c->d_rg_xyz; cb.elevated_packed = 1;
+  cb.ecell = cb.ecell ? c->d_rg_cell : nullptr;
+  cb.label = nullptr;
+  if (c->d_rg_groups) { cb.groups = c->d_rg_groups; cb.gsorted = c->d_rg_gsorted; cb.group_scratch = c->d_rg_gscratch; cb.group_cap = c->rg_group_cap; }
+  return cb;
+}
+static RegroupBuffers regroup_buffers(const mot_ctx* c, int* label) {
+  RegroupBuffers r;
+  r.key = c->d_rg_key; r.tmp = c->d_rg_tmp; r.hist = c->d_rg_hist; r.xyz = c->d_rg_xyz; r.cell = c->d_rg_cell; r.label = label;
+  return r;
+}
+// a reader's view of a slot's box-stage products, whichever mode produced them (the mode may have been switched since)
+static ClusterBuffers box_products(mot_ctx* c, int slot) {
+  ClusterBuffers cb = cluster_buffers(c, slot);
+  return c->res.regrouped(slot) ? regrouped_view(c, cb) : cb;
+}
+// the box stage of a stage-wise call on slot 0's resident cloud; returns the view its products are read through
+static ClusterBuffers launch_box_stage(mot_ctx* c, const ClusterBuffers& cb, int n) {
+  if (c->point_order != MOT_ORDER_ANY) { mot_launch_box(c->dp, cb, 1, n, c->stream); return cb; }
+  mot_launch_regroup(-1, c->dp, cb, regroup_buffers(c, c->d_label), 1, n, c->stream);
+  const ClusterBuffers view = regrouped_view(c, cb);
+  mot_launch_box(c->dp, view, 1, n, c->stream);
+  return view;
+}
+// The mode's buffers, at the first request (a context that never asks pays nothing). A failure half-way leaves what exists for mot_destroy and the
+// next request; the mode is not entered.
+static int ensure_regroup(mot_ctx* c) {
+  const size_t B = c->batch, N = c->cap;
+  if (!c->d_rg_key) MOT_HIP(c, hipMalloc(&c->d_rg_key, B * N * sizeof(unsigned short)));
+  if (!c->d_rg_tmp) MOT_HIP(c, hipMalloc(&c->d_rg_tmp, B * N * sizeof(unsigned)));
+  if (!c->d_rg_hist) MOT_HIP(c, hipMalloc(&c->d_rg_hist, B * c->max_wg * kRegroupDigits * sizeof(int)));
+  if (!c->d_rg_xyz) MOT_HIP(c, hipMalloc(&c->d_rg_xyz, B * N * sizeof(float4)));   // (a slot every cap * 16 bytes, as the box kernels address `elevated`; the points are 12 bytes)
+  if (!c->d_rg_cell) MOT_HIP(c, hipMalloc(&c->d_rg_cell, B * N * sizeof(unsigned short)));
+  // Group slots. After regrouping a frame has at most kMaxClusters + cap / 64 - 1 groups (derivation: mot_internal.h, mot_regroup_group_cap; include/mot.h,
+  // "limits"), so with that many slots no frame is refused for its groups. The context's own cap / 2 slots are fewer only below ~8456 points per frame:
+  // such a context gets group buffers of the mode's own, and buckets for the index kernel (the polygon pool it otherwise borrows holds cap / 2 entries).
+  const long gc = mot_regroup_group_cap((long)N);
+  if (gc > (long)(N / 2)) {
+    if (!c->d_rg_groups) MOT_HIP(c, hipMalloc(&c->d_rg_groups, B * gc * sizeof(PointGroup)));
+    if (!c->d_rg_gsorted) MOT_HIP(c, hipMalloc(&c->d_rg_gsorted, B * gc * sizeof(SortedGroup)));
+    if (!c->d_rg_gscratch) MOT_HIP(c, hipMalloc(&c->d_rg_gscratch, B * gc * sizeof(uint2)));
+    c->rg_group_cap = (int)gc;
+  }
+  return MOT_OK;
 }
 
 static int create_impl(mot_ctx* c) {
@@ -666,7 +733,7 @@ static int set_batch(mot_ctx* c, const int* n_points, int batch, const float4* i
 }
 
 // kernel ids used by mot_time_stage and mot_profile_kernel
-enum { kK1 = 10, kK2 = 11, kK3 = 12, kC1 = 20, kC2 = 21, kB1 = 30, kB2 = 31, kB3 = 32, kB2b = 33, kB1b = 34, kT1 = 40 };
+enum { kK1 = 10, kK2 = 11, kK3 = 12, kC1 = 20, kC2 = 21, kB1 = 30, kB2 = 31, kB3 = 32, kB2b = 33, kB1b = 34, kR1 = 35, kR2 = 36, kR3 = 37, kT1 = 40 };
 
 // in-run timing of one kernel: an event pair around its launch, on the context stream, while the ring has room
 // roctx ranges around the stages of a launch sequence (the reference has none; a tracing aid of this library):
@@ -801,6 +868,9 @@ static void fused_buffers(mot_ctx* c, GroundBuffers* g, ClusterBuffers* cb) {
   if (!(c->fused_outputs & MOT_OUT_LABELS)) cb->label = nullptr;
 }
 
+// the regrouping pass of a fused launch writes the per-point labels (input order) where the label kernel would have
+static RegroupBuffers fused_regroup_buffers(const mot_ctx* c) { return regroup_buffers(c, (c->fused_outputs & MOT_OUT_LABELS) ? c->d_label : nullptr); }
+
 static void issue_frame_kernels(mot_ctx* c, int batch, int max_n, int run_tracker, bool from_block) {
   GroundBuffers g; ClusterBuffers cb;
   fused_buffers(c, &g, &cb);
@@ -816,6 +886,13 @@ static void issue_frame_kernels(mot_ctx* c, int batch, int max_n, int run_tracke
   for (int k = 0; k < ((c->dbg_skip >> 8) & 15); k++) mot_launch_noop(batch, c->stream);
   if (!(c->dbg_skip & 2)) { RangeScope rs(c, "mot:cluster"); ProfScope ps(c, kC2); mot_launch_cluster(c->dp, cb, batch, max_n, c->stream, true); }
   RangeScope rb(c, "mot:box");
+  if (c->point_order == MOT_ORDER_ANY) {   // the points into cluster order first; the box stage runs on the copy
+    const RegroupBuffers rg = fused_regroup_buffers(c);
+    { ProfScope ps(c, kR1); mot_launch_regroup(0, c->dp, cb, rg, batch, max_n, c->stream); }
+    { ProfScope ps(c, kR2); mot_launch_regroup(1, c->dp, cb, rg, batch, max_n, c->stream); }
+    { ProfScope ps(c, kR3); mot_launch_regroup(2, c->dp, cb, rg, batch, max_n, c->stream); }
+    cb = regrouped_view(c, cb);
+  }
   { ProfScope ps(c, kB1); mot_launch_box_kernel(0, c->dp, cb, batch, max_n, c->stream); }
   if (!(c->dbg_skip & 4)) { ProfScope ps(c, kB1b); mot_launch_box_kernel(4, c->dp, cb, batch, max_n, c->stream); }
   { ProfScope ps(c, kB2); mot_launch_box_kernel(1, c->dp, cb, batch, max_n, c->stream); }
@@ -860,16 +937,16 @@ static int launch_frames(mot_ctx* c, int batch, int run_tracker, const double* t
   if ((rc = next_epoch(c))) return rc;
   const int max_n = c->res.last_max_n;
   if ((rc = send_frame_args(c, batch, run_tracker, false, timestamps, ego_v, ego_yaw))) return rc;
-  c->res.fused_batch(batch, c->fused_outputs);
+  c->res.fused_batch(batch, c->fused_outputs, c->point_order == MOT_ORDER_ANY);
 #ifndef MOT_HIPEMU
   // Few streams per launch = somebody waits for every frame: the sequence's 10-13 launches go out as ONE hipGraph launch, captured
   // once per launch geometry. What differs from call to call without changing the geometry (the cloud's address, the look-back
   // epoch) travels in the argument block (FrameLaunch). Not while a kernel is being timed (the event pairs are host calls).
   if (c->graph_mode && c->prof_kernel == 0) {
-    const mot_ctx::GraphKey key = {batch, (max_n + kGroundChunk - 1) / kGroundChunk, run_tracker ? 1 : 0, c->fused_outputs};
+    const mot_ctx::GraphKey key = {batch, (max_n + kGroundChunk - 1) / kGroundChunk, run_tracker ? 1 : 0, c->fused_outputs, c->point_order};
     void* exec = nullptr;
     for (const auto& ge : c->graphs)
-      if (ge.key.batch == key.batch && ge.key.chunks == key.chunks && ge.key.tracker == key.tracker && ge.key.outputs == key.outputs) { exec = ge.exec; break; }
+      if (ge.key.batch == key.batch && ge.key.chunks == key.chunks && ge.key.tracker == key.tracker && ge.key.outputs == key.outputs && ge.key.order == key.order) { exec = ge.exec; break; }
     if (!exec) {
       hipGraph_t graph = nullptr;
       hipGraphExec_t ge = nullptr;
@@ -933,7 +1010,7 @@ extern "C" int mot_sequence_dev(mot_ctx* c, const float* d_xyzw, long frame_stri
   if ((rc = next_epoch(c))) return rc;
   const int K = frames, max_n = c->res.last_max_n;
   if ((rc = send_frame_args(c, K, 1, true, timestamps, ego_v, ego_yaw))) return rc;   // one argument block for the whole sequence
-  c->res.fused_batch(K, c->fused_outputs);
+  c->res.fused_batch(K, c->fused_outputs, c->point_order == MOT_ORDER_ANY);
   issue_frame_kernels(c, K, max_n, 0, false);   // slots = frames; ends with the plain box_finalize_kernel
   const TrackBuffers base = track_buffers(c, true);
   RangeScope rt(c, "mot:tracker (sequence)");
@@ -1290,9 +1367,8 @@ extern "C" int mot_box_fit(mot_ctx* c, const float* elev, int n, const int32_t* 
   for (size_t i = 0, ng = (size_t)G * G; i < ng; i++) { const int32_t v = grid[i]; c->h_grid16[i] = (v < 0 || v > num_cluster) ? (GridLabel)0 : (GridLabel)v; }
   if ((rc = take_slot0(c, elev, n, true))) return rc;
   if ((rc = set_count(c, 0, kCntClusters, num_cluster))) return rc;
-  ClusterBuffers cb = cluster_buffers(c, 0);
-  mot_launch_box(c->dp, cb, 1, n, c->stream);
-  c->res.box_stage(0);
+  launch_box_stage(c, cluster_buffers(c, 0), n);
+  c->res.box_stage(0, c->point_order == MOT_ORDER_ANY);
   MOT_HIP(c, hipGetLastError());
   return mot_get_boxes(c, 0, boxes, max_boxes, n_boxes, box_cluster, n_undefined);
 }
@@ -1313,8 +1389,8 @@ extern "C" int mot_box_fit_resident(mot_ctx* c, float* boxes, int max_boxes, int
     if ((rc = set_count(c, 0, kCntFlags, kFlagClusterOverflow))) return rc;
     return fail(c, MOT_E_CAPACITY, kMsgClusterOverflow);
   }
-  mot_launch_box(c->dp, cluster_buffers(c, 0), 1, n, c->stream);
-  c->res.box_stage(0);
+  launch_box_stage(c, cluster_buffers(c, 0), n);
+  c->res.box_stage(0, c->point_order == MOT_ORDER_ANY);
   MOT_HIP(c, hipGetLastError());
   return mot_get_boxes(c, 0, boxes, max_boxes, n_boxes, box_cluster, n_undefined);
 }
@@ -1439,7 +1515,7 @@ extern "C" int mot_box_markers(mot_ctx* c, int slot, float* centroid_extent, int
   if (nb > max_boxes) return fail(c, MOT_E_CAPACITY, "more boxes than the caller's buffer holds");
   if (nb == 0 || !centroid_extent) return MOT_OK;
   if ((rc = ensure_markers(c))) return rc;
-  mot_launch_box_markers(cluster_buffers(c, slot), slot, nb < kMaxBoxesPerFrame ? nb : kMaxBoxesPerFrame, c->d_markers, c->stream);
+  mot_launch_box_markers(box_products(c, slot), slot, nb < kMaxBoxesPerFrame ? nb : kMaxBoxesPerFrame, c->d_markers, c->stream);
   MOT_HIP(c, hipGetLastError());
   MOT_HIP(c, hipMemcpyAsync(centroid_extent, c->d_markers, (size_t)nb * 6 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   MOT_HIP(c, hipStreamSynchronize(c->stream));
@@ -1472,8 +1548,8 @@ extern "C" int mot_cluster_node_frame(mot_ctx* c, const float* elev, int n, cons
   ClusterBuffers cb = cluster_buffers(c, 0);
   mot_launch_cluster(c->dp, cb, 1, n, c->stream);
   mot_launch_side_products(c->dp, d, s, n > 0 ? n : 1, c->stream);
-  mot_launch_box(c->dp, cb, 1, n, c->stream);
-  mot_launch_box_markers(cb, 0, kMaxBoxesPerFrame, c->d_markers, c->stream);   // (the box count is still on the device: workgroups beyond it leave at once)
+  const ClusterBuffers products = launch_box_stage(c, cb, n);
+  mot_launch_box_markers(products, 0, kMaxBoxesPerFrame, c->d_markers, c->stream);   // (the box count is still on the device: workgroups beyond it leave at once)
   MOT_HIP(c, hipGetLastError());
   int* h = reinterpret_cast<int*>(pin);
   MOT_HIP(c, hipMemcpyAsync(h, c->d_counts, kCountsStride * sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -1483,7 +1559,7 @@ extern "C" int mot_cluster_node_frame(mot_ctx* c, const float* elev, int n, cons
   if ((rc = capacity_error(c, h[kCntFlags]))) return rc;
   const int ncc = h[kCountsStride], nob = h[kCountsStride + 1], nb = h[kCntBoxes];
   if (ncc < 0 || ncc > n || nob < 0 || (size_t)nob > max_obs || nb < 0 || nb > kMaxBoxesPerFrame) return fail(c, MOT_E_STATE, "mot_cluster_node_frame: inconsistent counts");
-  c->res.box_stage(0);   // no overflow: slot 0 holds this cloud's labels and boxes
+  c->res.box_stage(0, c->point_order == MOT_ORDER_ANY);   // no overflow: slot 0 holds this cloud's labels and boxes
   if (ncc > 0) MOT_HIP(c, hipMemcpyAsync(pin + o_cc, c->d_side_cloud, (size_t)ncc * 16, hipMemcpyDeviceToHost, c->stream));
   if (nob > 0) MOT_HIP(c, hipMemcpyAsync(pin + o_ob, c->d_side_obs, (size_t)nob * 16, hipMemcpyDeviceToHost, c->stream));
   MOT_HIP(c, hipMemcpyAsync(pin + o_cm, c->d_side_cost, cost_cells * sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -1631,16 +1707,20 @@ static int launch_one(mot_ctx* c, int id, int batch) {
   if (id == kK3) c->res.compaction_rerun(batch, Residency::fused_packs(c->fused_outputs), Residency::fused_keeps_ground(c->fused_outputs));
   GroundBuffers g; ClusterBuffers cb;
   fused_buffers(c, &g, &cb);   // as in the fused path
+  const bool any = c->point_order == MOT_ORDER_ANY;
+  const ClusterBuffers src = cb;           // the frame as the cluster stage left it: what the regrouping pass reads
+  if (any && id >= kB1 && id <= kB1b) cb = regrouped_view(c, cb);
   switch (id) {
     case kK1: mot_launch_ground_kernel(0, c->dp, g, batch, max_n, c->stream); break;
     case kK2: mot_launch_ground_kernel(1, c->dp, g, batch, max_n, c->stream); break;
     case kK3: mot_launch_ground_kernel(2, c->dp, g, batch, max_n, c->stream); break;
     case kC2: mot_launch_cluster_kernel(1, c->dp, cb, batch, max_n, c->stream); break;
-    case kB1: mot_launch_box_kernel(0, c->dp, cb, batch, max_n, c->stream); for (int b = 0; b < batch; b++) c->res.labels_written(b, cb.label != nullptr); break;
+    case kB1: mot_launch_box_kernel(0, c->dp, cb, batch, max_n, c->stream); if (!any) for (int b = 0; b < batch; b++) c->res.labels_written(b, cb.label != nullptr); break;   // (MOT_ORDER_ANY: the labels are the regrouping pass's)
     case kB2: mot_launch_box_kernel(1, c->dp, cb, batch, max_n, c->stream); break;
     case kB3: mot_launch_box_kernel(2, c->dp, cb, batch, max_n, c->stream); break;
     case kB2b: mot_launch_box_kernel(3, c->dp, cb, batch, max_n, c->stream); break;
     case kB1b: mot_launch_box_kernel(4, c->dp, cb, batch, max_n, c->stream); break;
+    case kR1: case kR2: case kR3: mot_launch_regroup(id - kR1, c->dp, src, fused_regroup_buffers(c), batch, max_n, c->stream); break;
     case kT1: mot_launch_track(track_buffers(c, true), batch, c->stream); break;  // last frame's arguments again
     default: return fail(c, MOT_E_ARG, "unknown kernel id");
   }
@@ -1657,6 +1737,10 @@ extern "C" int mot_time_stage(mot_ctx* c, int stage, int batch, int iters, float
   MOT_GUARD(c);
   if (!ms_per_iter || iters < 1) return fail(c, MOT_E_ARG, "mot_time_stage: null result pointer or iters < 1");
   if (!c->res.last_in || batch != c->res.last_batch) return fail(c, MOT_E_STATE, "call mot_frames_dev with the same batch first");
+  // MOT_ORDER_ANY: the box stage includes the regrouping pass (35-37), and its kernels run on the copy that pass left — which must be the last batch's
+  const bool any = c->point_order == MOT_ORDER_ANY;
+  if ((stage == 2 || stage == 100 || (stage >= kB1 && stage <= kR3)) && any != c->res.regrouped(0)) return fail(c, MOT_E_STATE, "mot_time_stage: call mot_frames_dev in the current point order first");
+  if (stage >= kR1 && stage <= kR3 && !any) return fail(c, MOT_E_STATE, "mot_time_stage: kernels 35-37 exist in MOT_ORDER_ANY only");
   struct Seq { int pre[4], timed[12], post[3]; };
   Seq s = {{0, 0, 0, 0}, {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, {0, 0, 0}};
   switch (stage) {
@@ -1664,8 +1748,8 @@ extern "C" int mot_time_stage(mot_ctx* c, int stage, int batch, int iters, float
     // of the stage-wise mot_cluster is not timed here)
     case 0: s = {{0}, {kK1, kK2, kK3}, {kC2}}; break;
     case 1: s = {{kK3}, {kC2}, {0}}; break;
-    case 2: s = {{0}, {kB1, kB1b, kB2, kB2b, kB3}, {0}}; break;
-    case 100: s = {{0}, {kK1, kK2, kK3, kC2, kB1, kB1b, kB2, kB2b, kB3}, {0}}; break;
+    case 2: if (any) s = {{0}, {kR1, kR2, kR3, kB1, kB1b, kB2, kB2b, kB3}, {0}}; else s = {{0}, {kB1, kB1b, kB2, kB2b, kB3}, {0}}; break;
+    case 100: if (any) s = {{0}, {kK1, kK2, kK3, kC2, kR1, kR2, kR3, kB1, kB1b, kB2, kB2b, kB3}, {0}}; else s = {{0}, {kK1, kK2, kK3, kC2, kB1, kB1b, kB2, kB2b, kB3}, {0}}; break;
     case kK1: s = {{0}, {kK1}, {0}}; break;
     case kK2: s = {{0}, {kK2}, {0}}; break;
     case kK3: s = {{0}, {kK3}, {kC2}}; break;
@@ -1675,6 +1759,11 @@ extern "C" int mot_time_stage(mot_ctx* c, int stage, int batch, int iters, float
     case kB2: s = {{kB1, kB1b}, {kB2}, {kB3}}; break;
     case kB2b: s = {{kB1, kB1b, kB2}, {kB2b}, {kB3}}; break;
     case kB3: s = {{kB1, kB1b, kB2, kB2b}, {kB3}, {0}}; break;
+    // (the regrouping kernels hand the chunk histograms on: 35 leaves the low digit's counts, 36 scans them IN PLACE into offsets and leaves the high digit's
+    // offsets, which 37 scatters by. Each is therefore timed behind the ones before it and followed by the ones after it: the cluster-ordered copy the slots vouch for is whole again)
+    case kR1: s = {{0}, {kR1}, {kR2, kR3}}; break;
+    case kR2: s = {{kR1}, {kR2}, {kR3}}; break;
+    case kR3: s = {{kR1, kR2}, {kR3}, {0}}; break;
     case kT1: s = {{0}, {kT1}, {0}}; break;
     default: return fail(c, MOT_E_ARG, "unknown stage");
   }
@@ -1861,6 +1950,26 @@ extern "C" int mot_set_tracker_mode(mot_ctx* c, int mode) {
   for (auto& ge : c->graphs) (void)hipGraphExecDestroy((hipGraphExec_t)ge.exec);   // captured launch sequences hold the old choice
 #endif
   c->graphs.clear();
+  return MOT_OK;
+}
+
+// MOT_ORDER_ANY: every box stage from now on first regroups the frame's elevated points by cluster (regroup.hip). Sticky; what is resident stays readable
+// (each slot remembers which view its box stage ran on).
+extern "C" int mot_set_point_order(mot_ctx* c, int order) {
+  if (!c) return MOT_E_ARG;
+  MOT_GUARD(c);
+  if (order != MOT_ORDER_SCAN && order != MOT_ORDER_ANY) return fail(c, MOT_E_ARG, "mot_set_point_order: order must be MOT_ORDER_SCAN or MOT_ORDER_ANY");
+  if (order == c->point_order) return MOT_OK;
+  if (order == MOT_ORDER_ANY) { const int rc = ensure_regroup(c); if (rc) return rc; }   // MOT_E_HIP: the mode stays as it was
+#ifndef MOT_HIPEMU
+  // the mode is part of the launch sequence: graphs captured in the other mode go (none is running once the stream has drained)
+  if (!c->graphs.empty()) {
+    MOT_HIP(c, hipStreamSynchronize(c->stream));
+    for (auto& ge : c->graphs) if (ge.exec) (void)hipGraphExecDestroy((hipGraphExec_t)ge.exec);
+    c->graphs.clear();
+  }
+#endif
+  c->point_order = order;
   return MOT_OK;
 }
 
@@ -2350,10 +2459,10 @@ extern "C" int mot_debug_copy(mot_ctx* c, int which, int slot, void* dst, size_t
   if (which == 0) src = c->d_cand + (size_t)slot * kMaxClusters;
   else if (which == 1) src = c->d_stats + (size_t)slot * kMaxClusters;
   else if (which == 3) src = c->d_poly + (size_t)slot * c->cap;
-  else if (which == 5) src = c->d_gsorted + (size_t)slot * (c->cap / 2);
+  else if (which == 5) { const ClusterBuffers v = box_products(c, slot); src = v.gsorted + (size_t)slot * v.group_cap; }   // (the buffers and stride of the mode the slot's box stage ran in)
   else if (which == 7) src = c->d_cluster_start + (size_t)slot * (kMaxClusters + 1);
   else if (which == 8) src = c->d_pix + (size_t)slot * c->cap;
-  else if (which == 9) src = c->d_groups + (size_t)slot * (c->cap / 2);
+  else if (which == 9) { const ClusterBuffers v = box_products(c, slot); src = v.groups + (size_t)slot * v.group_cap; }
   else if (which == 10) src = c->d_hg + (size_t)slot * MOT_POLAR_CELLS;
   else if (which == 11) src = c->d_tboxes + (size_t)slot * kMaxBoxesPerFrame * 24;
   else if (which == 12) src = reinterpret_cast<const long long*>(c->d_items) + (size_t)slot * 32;   // -DMOT_DBG_STREAM_TIMING builds: phase clocks of track_step_stream_kernel

@@ -202,7 +202,9 @@ struct ClusterBuffers {
   const unsigned long long* rng;  // [kRngTable]
   int* poly;                   // [B][cap] candidate hull points (x | y << 16) of the min-area-rectangle clusters
   PointGroup* groups;          // [B][cap / 2] (tile, cluster) groups of the frame, any order
-  int group_cap;               // cap / 2
+  int group_cap;               // cap / 2 (MOT_ORDER_ANY: max(cap / 2, kMaxClusters + cap / 64), see mot_regroup_group_cap)
+  uint2* group_scratch;        // [B][group_cap] or null: where the index kernel buckets the groups of a many-group frame. Null: in the polygon pool
+                               // (cap ints = cap / 2 entries per slot: only large enough while group_cap <= cap / 2)
   int* order;                  // [B][kMaxClusters] clusters by falling size: the per-cluster kernels start on the largest ones
   int* cluster_start;          // [B][kMaxClusters + 1] points of all earlier clusters (a cluster's own slots of the polygon pool start here)
   int* cluster_gstart;         // [B][kMaxClusters + 1] first entry of every cluster in `gsorted`
@@ -220,6 +222,29 @@ void mot_launch_cluster_kernel(int which, const MotDevParams& p, const ClusterBu
 void mot_launch_stats_init(const ClusterBuffers& c, int batch, hipStream_t stream);
 void mot_launch_point_labels(const MotDevParams& p, const ClusterBuffers& c, int slot, int max_n, hipStream_t stream);
 void mot_launch_box_kernel(int which, const MotDevParams& p, const ClusterBuffers& c, int batch, int max_n, hipStream_t stream);
+
+// ---- MOT_ORDER_ANY: the elevated points regrouped by cluster before the box stage (regroup.hip) -------------------------------
+// A stable sort of every frame's elevated points by cluster label (0 = no cluster, first; labels 1 .. 4096 after it), two LSD radix passes
+// of 7 + 6 bits over 2048-point chunks, and a copy of the points (12 bytes each) and their cells in that order. The box stage then runs on
+// the copy: a cluster's points are neighbours there, in the order they had in the input.
+constexpr int kRegroupDigits = 128;               // histogram row of a chunk (pass 0: 128 digits, pass 1: 64)
+// Groups of a frame AFTER regrouping: a cluster's points form one run of the copy, and a run of r points that starts at position s meets
+// floor((s + r - 1) / 64) - floor(s / 64) + 1 tiles: one group, plus one for every tile boundary inside the run. The N_e points of a frame have
+// ceil(N_e / 64) - 1 tile boundaries between them and each lies inside at most one run, so a frame of C clusters has at most
+// C + ceil(N_e / 64) - 1 <= kMaxClusters + cap / 64 - 1 groups, whatever the input order. (The unlabelled points in front form no group.)
+// That exceeds the default cap / 2 only for cap < 2 * kMaxClusters * 64 / 62 ~ 8456 points.
+constexpr long mot_regroup_group_cap(long cap) { return cap / 2 > kMaxClusters + cap / 64 ? cap / 2 : kMaxClusters + cap / 64; }
+struct RegroupBuffers {
+  unsigned short* key;         // [B][cap] cluster label of every elevated point (0 .. kMaxClusters), input order
+  unsigned* tmp;               // [B][cap] after pass 0: input index (bits 0-20) | high digit of the key (bits 21-26), by low digit
+  int* hist;                   // [B][max_wg][kRegroupDigits] per-chunk digit counts, turned into the chunks' scatter offsets by the scan kernel
+  float4* xyz;                 // [B][cap] the cluster-ordered copy: 12-byte points, a slot every cap * 16 bytes like `elevated`
+  unsigned short* cell;        // [B][cap] their Cartesian cells (fused path; unused when the source has none)
+  int* label;                  // [B][cap] per-point labels IN INPUT ORDER are written here by the label pass, or null
+};
+// which = 0 label pass (+ histogram of the low digit), 1 the sort (scan, scatter by low digit, histogram of the high digit, scan),
+// 2 scatter by high digit = gather of points and cells into the copy, -1 all three. `src` is the frame as the cluster stage left it.
+void mot_launch_regroup(int which, const MotDevParams& p, const ClusterBuffers& src, const RegroupBuffers& r, int batch, int max_n, hipStream_t stream);
 
 // ---- cluster-node side products (side.hip) ------------------------------------------------------
 struct SideDevParams {
@@ -394,6 +419,23 @@ MOT_HD int mot_cart_bit(const MotDevParams& p, float x, float y) {
   int bit = mot_cart_bit_try(p, x, y);
   if (bit == -2) { int xI, yI; bit = mot_cart_cell(p, x, y, &xI, &yI) ? xI * MOT_MAX_GRID + yI : -1; }
   return bit;
+}
+
+// getClusteredPoints' label of elevated point i of slot b (box_fitting.cpp:46-72): its cell — the 2 bytes the compaction kernel left (fused path) or
+// the guarded cell computation — then the label grid; a value that names no cluster of the frame reads as 0
+MOT_HD int mot_point_label(const MotDevParams& p, const ClusterBuffers& c, int b, long i, int num_cluster) {
+  int cell;
+  if (c.ecell) {
+    const unsigned e = c.ecell[(long)b * c.cap + i];
+    cell = e != 0xffffu ? (int)((e >> 8) * (unsigned)p.num_grid + (e & 255u)) : -1;
+  } else {
+    const float4 q = mot_load_xyz(c.elevated + (long)b * c.cap, i, c.elevated_packed);
+    const int bit = mot_cart_bit(p, q.x, q.y);
+    cell = bit >= 0 ? (bit >> 8) * p.num_grid + (bit & 255) : -1;
+  }
+  int lab = cell >= 0 ? (int)c.grid[(long)b * (MOT_MAX_GRID * MOT_MAX_GRID) + cell] : 0;
+  if (lab < 0 || lab > num_cluster) lab = 0;
+  return lab;
 }
 
 // getCellIndexFromPoints (ground_removal.cpp:67-76) + filterCloud's range test (:53) + the callers'

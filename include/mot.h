@@ -70,6 +70,9 @@ enum {
 /* per-point classification written by the ground stage */
 enum { MOT_MASK_DROPPED = 0, MOT_MASK_GROUND = 1, MOT_MASK_ELEVATED = 2 };
 
+/* order of the points of an input cloud (mot_set_point_order) */
+enum { MOT_ORDER_SCAN = 0, /* default: a scan's own order (beam-major or firing order): the box stage works on the cloud as it lies */
+       MOT_ORDER_ANY = 1   /* no order assumed: the box stage first regroups the elevated points by cluster on the device */ };
 /* by-products of groundRemove that nothing downstream of it reads (mot_set_fused_outputs) */
 enum { MOT_OUT_GROUND = 1, /* groundCloud */ MOT_OUT_MASK = 2, /* the per-point classification */ MOT_OUT_LABELS = 4 /* the cluster label of every elevated point */ };
 
@@ -366,6 +369,19 @@ int mot_sequence_dev(mot_ctx* ctx, const float* d_xyzw, long frame_stride, const
  * (OT/src/groundremove/ground_removal.cpp:226-247). */
 int mot_set_fused_outputs(mot_ctx* ctx, int flags);
 
+/* The order the library may assume of an input cloud's points. MOT_ORDER_SCAN (default): the box stage describes a cluster by its groups in the
+ * cloud as it lies, which is compact for scans in beam-major or firing order; a cloud in no order is slow there and can be refused (the group limit
+ * under mot_get_ground). MOT_ORDER_ANY: for merged, voxel- or KD-tree-filtered clouds and non-repetitive scanners. Every entry point that runs the box
+ * stage — mot_frames_dev, mot_frames_host*, mot_frame_pointcloud2, mot_sequence_dev, mot_box_fit, mot_box_fit_resident, mot_cluster_node_frame — first
+ * puts the frame's elevated points into cluster order on the device (a stable sort by cluster label; unlabelled points are kept, in front) and fits
+ * the boxes on that internal copy, as the reference's getClusteredPoints copies the cloud into one vector per cluster (box_fitting.cpp:46-72). Every
+ * result equals MOT_ORDER_SCAN's bit for bit on any frame that mode accepts — boxes, box_cluster, n_undefined, mot_box_markers, tracks — and
+ * everything the caller reads keeps the INPUT order: per-point labels, the elevated / ground clouds, the side products. No frame is refused for its
+ * groups; the cluster and box limits hold in both modes with their own messages. Cost: the extra pass (48 bytes per elevated point).
+ * Sticky per context. The mode's buffers (24 bytes per point and slot) are allocated by the first MOT_ORDER_ANY request: MOT_E_HIP if that fails, and
+ * the mode stays as it was. Switching leaves every resident result readable, and drops the captured launch graphs. Unknown order: MOT_E_ARG. */
+int mot_set_point_order(mot_ctx* ctx, int order);
+
 /* on != 0: the fused entry points send their launch sequence (13 kernels with the tracker) as ONE hipGraph launch, captured once per launch geometry
  * (batch, chunks of the largest frame, tracker on / off, outputs); what changes per call without changing the geometry travels in the
  * device-resident argument block. For contexts somebody waits on frame by frame (one or a few streams): the host's part of a frame
@@ -427,7 +443,13 @@ int mot_fetch_tracks_async(mot_ctx* ctx, int batch, void* h_tracks, int max_per_
  * stream's mot_get_tracks reports MOT_E_CAPACITY like a dropped birth: sticky until mot_reset / mot_reset_slot / mot_reset_tracks_slot.
  *   - (tile, cluster) groups: at most max_points / 2 per frame, a group = the points of one cluster among 64 consecutive elevated points.
  *     REACHABLE: a cloud in no order at all whose clusters are tiny (n elevated points in random order over >> 64 clusters give ~n groups:
- *     more than max_points / 2 points of that kind). Scans in firing order stay far below (a few groups per tile). Raise max_points.
+ *     more than max_points / 2 points of that kind). Scans in firing order stay far below (a few groups per tile). Raise max_points — or
+ *     call mot_set_point_order(MOT_ORDER_ANY): the box stage then works on a copy of the elevated points in cluster order, where a cluster is
+ *     ONE run of consecutive points. A run of r points starting at position s meets floor((s + r - 1) / 64) - floor(s / 64) + 1 tiles: one
+ *     group, plus one per tile boundary inside the run; the N_e elevated points have ceil(N_e / 64) - 1 tile boundaries, each inside at most
+ *     one run. A frame of C clusters therefore has at most C + ceil(N_e / 64) - 1 <= 4096 + max_points / 64 groups in that mode, whatever the
+ *     input order; the mode sizes its group buffers to that bound (it exceeds max_points / 2 only below about 8500 points), so NOT reachable
+ *     there: no frame is refused for its groups.
  *   - clusters: 4096 per frame. REACHABLE with mot_params.dilate == 0 (preset OBJECT_TRACKING0: single occupied cells two cells apart, up to
  *     10 000 on its 200 x 200 grid) and through mot_box_fit's num_cluster argument. NOT reachable through mot_cluster with the 3 x 3 dilation
  *     of preset OBJECT_TRACKING: separate components are at least 4 cells apart, 63 x 63 = 3969 on the 250 x 250 grid.
@@ -562,7 +584,9 @@ int mot_decode_pointcloud2_dev(mot_ctx* ctx, const void* d_data, int n_points, i
 /* Re-runs only the named stage `iters` times on the data resident from the last mot_frames_dev call,
  * bracketed by hipEvents ON THE CONTEXT STREAM; returns average milliseconds per iteration.
  * stage: 0 ground, 1 cluster, 2 box, 100 the three stateless stages; single kernels: 10-12 ground, 21 cluster,
- * 30-34 box; 40 re-runs the tracker kernel with the last frame's arguments (that ADVANCES tracker state: bench only). */
+ * 30-34 box; 35-37 the regrouping pass of MOT_ORDER_ANY (35 labels + first histogram, 36 the sort by cluster label, 37 the gather of points and
+ * cells into the cluster-ordered copy: MOT_E_STATE in MOT_ORDER_SCAN; stages 2 and 100 include them when the mode is on, and need the last
+ * mot_frames_dev to have run in the current mode); 40 re-runs the tracker kernel with the last frame's arguments (that ADVANCES tracker state: bench only). */
 int mot_time_stage(mot_ctx* ctx, int stage, int batch, int iters, float* ms_per_iter);
 /* In-run timing: from now on every `every`-th mot_frames_dev / mot_frames_host call brackets its launch of kernel `kernel_id`
  * (ids as for mot_time_stage; 0 = off) with a HIP event pair on the context stream, up to 64 launches; mot_profile_read synchronises,

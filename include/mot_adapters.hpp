@@ -61,6 +61,7 @@ struct Config {
   int max_points = 262144;
   int max_tracks_total = 16384;   // track SLOTS: tracks alive at the same time
   int max_tracks_ever = 0;        // tracks a stream may create before it is restarted (0 = 64 x max_tracks_total); see immUkfJpdaf below
+  int point_order = MOT_ORDER_SCAN;   // MOT_ORDER_ANY: clouds in no point order (merged / filtered clouds): mot_set_point_order
 };
 inline Config& config() { static Config c; return c; }
 inline void configure(const Config& c) { config() = c; }
@@ -73,6 +74,7 @@ inline mot_ctx* context() {
     if (config().max_tracks_ever > 0) p.max_tracks_ever = config().max_tracks_ever;   // 0: the library's default, 64 x max_tracks_total
     if (mot_create(&p, config().device, config().max_points, 1, config().max_tracks_total, &ctx) != MOT_OK)
       throw std::runtime_error("mot_create failed (no MI355X / HIP device?) — this library has no CPU fallback");
+    if (mot_set_point_order(ctx, config().point_order) != MOT_OK) throw std::runtime_error(std::string("mot_set_point_order: ") + mot_last_error(ctx));
   }
   return ctx;
 }

@@ -43,8 +43,14 @@ inline void track_step_or_restart(mot_ctx* ctx, int slot, const float* boxes_glo
 // private parameters common to the nodes (read from a NodeHandle("~")): ~device (HIP ordinal), ~max_points, ~preset
 // (0 = object_tracking, 1 = object_tracking0), ~max_tracks_total, ~rng_mapping (how the reference build being replaced maps its
 // mt19937_64 draws to sample indices, include/mot.h: 0 = libstdc++ <= 10 — the compiler of every ROS1 distribution, hence the
-// default here — 1 = libstdc++ >= 11; the two agree except with probability ~5e-14 per draw)
-struct Settings { int device = 0, max_points = 262144, preset = MOT_PRESET_OBJECT_TRACKING, max_tracks_total = 16384, rng_mapping = MOT_RNG_LIBSTDCXX10; };
+// default here — 1 = libstdc++ >= 11; the two agree except with probability ~5e-14 per draw), ~point_order ("scan", the default: the cloud
+// is a scan in the sensor's own order; "any": a merged, voxel- or KD-tree-filtered cloud, or a non-repetitive scanner's — mot_set_point_order)
+struct Settings { int device = 0, max_points = 262144, preset = MOT_PRESET_OBJECT_TRACKING, max_tracks_total = 16384, rng_mapping = MOT_RNG_LIBSTDCXX10, point_order = MOT_ORDER_SCAN; };
+inline int point_order_value(const std::string& name) {
+  if (name == "scan") return MOT_ORDER_SCAN;
+  if (name == "any") return MOT_ORDER_ANY;
+  throw std::runtime_error("~point_order must be \"scan\" or \"any\", not \"" + name + "\"");
+}
 inline Settings settings(const ros::NodeHandle& nh) {
   Settings s;
   nh.param<int>("device", s.device, s.device);
@@ -52,6 +58,9 @@ inline Settings settings(const ros::NodeHandle& nh) {
   nh.param<int>("preset", s.preset, s.preset);
   nh.param<int>("max_tracks_total", s.max_tracks_total, s.max_tracks_total);
   nh.param<int>("rng_mapping", s.rng_mapping, s.rng_mapping);
+  std::string order = "scan";
+  nh.param<std::string>("point_order", order, order);
+  s.point_order = point_order_value(order);
   return s;
 }
 inline mot_ctx* create(const mot_params& p_in, const Settings& s) {
@@ -61,6 +70,7 @@ inline mot_ctx* create(const mot_params& p_in, const Settings& s) {
   p.max_tracks_ever = s.max_tracks_total;   // = the nodes' record buffers (tracks_): see track_step_or_restart
   if (mot_create(&p, s.device, s.max_points, 1, s.max_tracks_total, &ctx) != MOT_OK)
     throw std::runtime_error("mot_create failed: no MI355X / HIP device? (this library has no CPU path)");
+  check(ctx, mot_set_point_order(ctx, s.point_order), "mot_set_point_order");
   return ctx;
 }
 
