@@ -20,6 +20,7 @@ MOT_OK, MOT_E_ARG, MOT_E_CAPACITY, MOT_E_HIP, MOT_E_STATE = 0, 1, 2, 3, 4
 MOT_MAX_BOXES_PER_FRAME = 1024   # include/mot.h
 MOT_TRACKER_AUTO, MOT_TRACKER_SPLIT, MOT_TRACKER_STREAM = 0, 1, 2   # mot_set_tracker_mode (include/mot.h)
 MOT_ORDER_SCAN, MOT_ORDER_ANY = 0, 1   # mot_set_point_order (include/mot.h)
+MOT_FRAME_GLOBAL, MOT_FRAME_SENSOR = 0, 1   # mot_export_tracks*_frame_dev, mot_fetch_tracks_frame_async (include/mot.h)
 PRESET_OBJECT_TRACKING, PRESET_OBJECT_TRACKING0 = 0, 1
 MASK_DROPPED, MASK_GROUND, MASK_ELEVATED = 0, 1, 2
 NUM_CHANNEL, NUM_BIN = 80, 120
@@ -79,6 +80,7 @@ EXPORTS = (
     "mot_reset_slot", "mot_stream_snapshot_size", "mot_stream_save", "mot_stream_load", "mot_frames_host", "mot_frames_host_xyz", "mot_frames_host_pointcloud2", "mot_wait_uploads", "mot_host_alloc", "mot_host_free", "mot_fetch_tracks_async",
     "mot_track_steps_dev", "mot_profile_kernel", "mot_profile_read", "mot_get_params", "mot_set_fused_outputs", "mot_set_point_order", "mot_set_tracker_mode", "mot_set_trace_ranges", "mot_reset_tracks_slot", "mot_export_tracks_packed_dev", "mot_set_launch_graphs",
     "mot_cluster_node_frame", "mot_ground_node_frame",
+    "mot_sensor_pose", "mot_export_tracks_frame_dev", "mot_export_tracks_packed_frame_dev", "mot_fetch_tracks_frame_async", "mot_tracking_node_frame",
     "mot_gather_unique_id", "mot_gather_create", "mot_gather_contribute", "mot_gather_result", "mot_gather_synchronize", "mot_gather_destroy", "mot_gather_last_error",
 )
 ABI_VERSION = 6
@@ -132,6 +134,25 @@ class MotClusterFrame(C.Structure):
     _fields_ = [("num_cluster", C.c_int32), ("n_clustered", C.c_int32), ("n_obstacles", C.c_int32), ("n_boxes", C.c_int32), ("n_undefined", C.c_int32),
                 ("cost_cells", C.c_int32), ("clustered_xyzw", C.POINTER(C.c_float)), ("obstacles_xyzc", C.POINTER(C.c_float)), ("cost_map", C.POINTER(C.c_int32)),
                 ("boxes", C.POINTER(C.c_float)), ("box_cluster", C.POINTER(C.c_int32)), ("centroid_extent", C.POINTER(C.c_float))]
+
+
+class MotTrackingFrame(C.Structure):
+    """mirror of struct mot_tracking_frame (include/mot.h): the ego origin, counts and a view of the live records in the sensor frame"""
+    _fields_ = [("origin6", C.c_double * 6), ("n_live", C.c_int32), ("n_ever", C.c_int32), ("tracks", C.POINTER(MotTrack))]
+
+
+# struct mot_track as a numpy record (144 bytes)
+TRACK_DTYPE = np.dtype([("id", "i4"), ("track_manage", "i4"), ("is_static", "i4"), ("is_vis", "i4"), ("p", "f4", 3), ("lifetime", "i4"),
+                        ("v_yaw", "f8", 2), ("vis_box", "f4", 24)])
+
+
+def _frame(frame) -> int:
+    """"global" / "sensor" (or MOT_FRAME_GLOBAL / MOT_FRAME_SENSOR) -> the enum of include/mot.h"""
+    if frame in ("global", MOT_FRAME_GLOBAL):
+        return MOT_FRAME_GLOBAL
+    if frame in ("sensor", MOT_FRAME_SENSOR):
+        return MOT_FRAME_SENSOR
+    raise ValueError(f'frame must be "global" or "sensor", not {frame!r}')
 
 
 def _pts(a) -> np.ndarray:
@@ -472,8 +493,29 @@ class Context:
     def wait_uploads(self):
         self._ck(self.lib.mot_wait_uploads(self._h))
 
-    def fetch_tracks_async(self, batch: int, h_tracks_ptr: int, max_per_slot: int, h_counts_ptr: int):
-        self._ck(self.lib.mot_fetch_tracks_async(self._h, batch, C.c_void_p(h_tracks_ptr), max_per_slot, C.c_void_p(h_counts_ptr)))
+    def fetch_tracks_async(self, batch: int, h_tracks_ptr: int, max_per_slot: int, h_counts_ptr: int, frame="global"):
+        """frame="sensor": the records relative to each stream's vehicle (mot_fetch_tracks_frame_async)"""
+        if _frame(frame) == MOT_FRAME_GLOBAL:
+            self._ck(self.lib.mot_fetch_tracks_async(self._h, batch, C.c_void_p(h_tracks_ptr), max_per_slot, C.c_void_p(h_counts_ptr)))
+        else:
+            self._ck(self.lib.mot_fetch_tracks_frame_async(self._h, batch, _frame(frame), C.c_void_p(h_tracks_ptr), max_per_slot, C.c_void_p(h_counts_ptr)))
+
+    def sensor_pose(self, slot: int = 0):
+        """(sensor_from_global, global_from_sensor): the float 3 x 4 matrices of the pose the slot's dead reckoning holds (mot_sensor_pose)"""
+        a, b = np.zeros(12, np.float32), np.zeros(12, np.float32)
+        self._ck(self.lib.mot_sensor_pose(self._h, slot, _vp(a), _vp(b)))
+        return a.reshape(3, 4), b.reshape(3, 4)
+
+    def tracking_node_frame(self, boxes_sensor, timestamp: float, v_gps: float, yaw_gps: float, slot: int = 0, copy: bool = True):
+        """the tracking node's whole callback in one call (mot_tracking_node_frame): getOriginPoints, the boxes sensor -> global on the device, immUkfJpdaf,
+        the live tracks back in the sensor frame. `tracks`: a TRACK_DTYPE record array, in id order. Dropped births: capacity_exceeded, records delivered."""
+        b = np.ascontiguousarray(boxes_sensor, np.float32).reshape(-1, 8, 3); fr = MotTrackingFrame()
+        rc = self.lib.mot_tracking_node_frame(self._h, slot, _vp(b), len(b), C.c_double(timestamp), C.c_double(v_gps), C.c_double(yaw_gps), C.byref(fr))
+        full = rc == MOT_E_CAPACITY
+        if not full:
+            self._ck(rc)
+        rec = np.ctypeslib.as_array(C.cast(fr.tracks, C.POINTER(C.c_uint8)), shape=(fr.n_live * C.sizeof(MotTrack),)).view(TRACK_DTYPE) if fr.n_live else np.zeros(0, TRACK_DTYPE)
+        return dict(origin=np.array(fr.origin6[:]), n_live=fr.n_live, n_ever=fr.n_ever, tracks=rec.copy() if copy else rec, capacity_exceeded=full)
 
     def track_steps_dev(self, d_boxes_ptr: int, box_stride_floats: int, m, timestamps):
         """immUkfJpdaf for one frame of every slot, boxes (global frame) already on the device"""
@@ -489,13 +531,25 @@ class Context:
         self._ck(self.lib.mot_profile_read(self._h, C.byref(mean), C.byref(mn), C.byref(mx), C.byref(k)))
         return dict(mean_ms=mean.value, min_ms=mn.value, max_ms=mx.value, samples=k.value)
 
-    def export_tracks_dev(self, batch: int, d_tracks_ptr: int, max_per_slot: int, d_counts_ptr: int):
-        """live tracks of every slot -> caller's device buffer (the block that is all-gathered across GPUs)"""
-        self._ck(self.lib.mot_export_tracks_dev(self._h, batch, C.c_void_p(d_tracks_ptr), max_per_slot, C.c_void_p(d_counts_ptr)))
+    def export_tracks_dev(self, batch: int, d_tracks_ptr: int, max_per_slot: int, d_counts_ptr: int, frame="global"):
+        """live tracks of every slot -> caller's device buffer (the block that is all-gathered across GPUs); frame="sensor": relative to each stream's vehicle"""
+        if _frame(frame) == MOT_FRAME_GLOBAL:
+            self._ck(self.lib.mot_export_tracks_dev(self._h, batch, C.c_void_p(d_tracks_ptr), max_per_slot, C.c_void_p(d_counts_ptr)))
+        else:
+            self._ck(self.lib.mot_export_tracks_frame_dev(self._h, batch, _frame(frame), C.c_void_p(d_tracks_ptr), max_per_slot, C.c_void_p(d_counts_ptr)))
 
-    def export_tracks_packed_dev(self, batch: int, d_block_ptr: int, block_bytes: int):
-        """live tracks of every slot, packed (counts header + records back to back) -> caller's device block"""
-        self._ck(self.lib.mot_export_tracks_packed_dev(self._h, batch, C.c_void_p(d_block_ptr), C.c_long(block_bytes)))
+    def export_tracks_packed_dev(self, batch: int, d_block_ptr: int, block_bytes: int, frame="global"):
+        """live tracks of every slot, packed (counts header + records back to back) -> caller's device block; frame="sensor" as above"""
+        if _frame(frame) == MOT_FRAME_GLOBAL:
+            self._ck(self.lib.mot_export_tracks_packed_dev(self._h, batch, C.c_void_p(d_block_ptr), C.c_long(block_bytes)))
+        else:
+            self._ck(self.lib.mot_export_tracks_packed_frame_dev(self._h, batch, _frame(frame), C.c_void_p(d_block_ptr), C.c_long(block_bytes)))
+
+    def export_tracks(self, batch: int, d_ptr: int, max_per_slot: int | None = None, d_counts_ptr: int | None = None, block_bytes: int | None = None, frame="global"):
+        """either export by its arguments: (d_tracks, max_per_slot, d_counts) the fixed block, (d_block, block_bytes=) the packed one"""
+        if block_bytes is not None:
+            return self.export_tracks_packed_dev(batch, d_ptr, block_bytes, frame=frame)
+        return self.export_tracks_dev(batch, d_ptr, max_per_slot, d_counts_ptr, frame=frame)
 
     def time_stage(self, stage: int, batch: int, iters: int) -> float:
         """average ms per iteration of one stage re-run on resident data, HIP events on the context stream"""

@@ -233,6 +233,18 @@ struct mot_ctx {
   mot_track* d_fetch = nullptr;
   int* d_fetch_counts = nullptr;
   int fetch_cap = 0;
+  // MOT_FRAME_SENSOR exports (mot_export_tracks*_frame_dev, mot_fetch_tracks_frame_async, mot_tracking_node_frame): every slot's global -> sensor matrix, computed
+  // from the slot's dead reckoning at call time, goes to d_sensor_tf in ONE stream-ordered copy ahead of the export kernel, from a ring of page-locked blocks
+  // like the argument block's (no host synchronisation; nothing here reads d_ego, which the fused sequence rewrites every call). Allocated at the first such call.
+  EgoTf* d_sensor_tf = nullptr;
+  EgoTf* h_sensor_tf = nullptr;        // pinned, kArgRing blocks of `batch` matrices
+  hipEvent_t sensor_tf_ev[kArgRing] = {};
+  bool sensor_tf_used[kArgRing] = {};
+  int sensor_tf_next = 0;
+  // mot_tracking_node_frame (allocated at its first call): the frame's boxes in the sensor frame — a staging buffer of their own, d_boxes belongs to the box
+  // stage — and the device block its results leave in: [T records][n_live, n_ever, flags, 0]
+  float* d_node_boxes = nullptr;
+  char* d_node_out = nullptr;
   // in-run kernel timing (mot_profile_kernel): event pairs around one kernel inside mot_frames_dev / mot_frames_host
   int prof_kernel = 0;
   int prof_every = 1, prof_seen = 0;   // every prof_every-th launch of the kernel is recorded
@@ -399,6 +411,11 @@ extern "C" void mot_destroy(mot_ctx* c) {
   }
   if (c->d_fetch) (void)hipFree(c->d_fetch);
   if (c->d_fetch_counts) (void)hipFree(c->d_fetch_counts);
+  if (c->d_sensor_tf) (void)hipFree(c->d_sensor_tf);
+  if (c->h_sensor_tf) (void)hipHostFree(c->h_sensor_tf);
+  for (int i = 0; i < mot_ctx::kArgRing; i++) if (c->sensor_tf_ev[i]) (void)hipEventDestroy(c->sensor_tf_ev[i]);
+  if (c->d_node_boxes) (void)hipFree(c->d_node_boxes);
+  if (c->d_node_out) (void)hipFree(c->d_node_out);
   if (c->prof_created)
     for (int i = 0; i < mot_ctx::kProfRing; i++) { (void)hipEventDestroy(c->prof_ev[i][0]); (void)hipEventDestroy(c->prof_ev[i][1]); }
 #ifndef MOT_HIPEMU
@@ -849,6 +866,41 @@ static void tf_velodyne_to_global(double x, double y, double yaw, float m[12]) {
   m[8] = txz - twy; m[9] = tyz + twx; m[10] = 1.0f - (txx + tyy); m[11] = (float)v[2];
 }
 
+// The way back: the float 3 x 4 matrix that pcl_ros::transformPointCloud("/velodyne", cloud_in_global, cloud_out, listener) applies after the node has broadcast
+// StampedTransform(transform, stamp, "velodyne", "global") (OT/tracking/main.cpp:76-83, 183-184, 195): what takes targetPoints and every visBBs[i] back into the
+// sensor frame. The lookup velodyne <- global walks the stored edge AS IT LIES (global is the child of velodyne), so nothing is inverted here — and this is not
+// inverse(tf_velodyne_to_global): that matrix went through a quaternion inversion and a quatRotate this one never sees. Same slices of tf, tf2 and pcl_ros as above
+// (oracle/ref_shim); tests/test_emu_sensor_tracks.py compares with the node's own call sequence on that shim, bit for bit.
+static void tf_global_to_velodyne(double x, double y, double yaw, float m[12]) {
+  // 1. tf::Quaternion::setRPY(0, 0, yaw) (cos(0) = 1 and sin(0) = 0 exactly), then Transform::setRotation -> Matrix3x3::setRotation   (double, tf LinearMath)
+  const double halfYaw = yaw * 0.5;
+  const double cosYaw = cos(halfYaw), sinYaw = sin(halfYaw);
+  const double cosPitch = 1.0, sinPitch = 0.0, cosRoll = 1.0, sinRoll = 0.0;
+  const double q[4] = {sinRoll * cosPitch * cosYaw - cosRoll * sinPitch * sinYaw, cosRoll * sinPitch * cosYaw + sinRoll * cosPitch * sinYaw,
+                       cosRoll * cosPitch * sinYaw - sinRoll * sinPitch * cosYaw, cosRoll * cosPitch * cosYaw + sinRoll * sinPitch * sinYaw};
+  double b[3][3];
+  tf_set_rotation(q, b);
+  // 2. TransformBroadcaster::sendTransform stores (Transform::getRotation() = Matrix3x3::getRotation, origin)   (double, tf2)
+  double e[4];
+  tf_get_rotation(b, e);
+  // 3. BufferCore's walk from "global" up to "velodyne" meets that one edge, child to parent: TransformAccum starts from the identity and its first (only)
+  //    accumulation step takes the stored (quaternion, vector) over unchanged; the looked-up StampedTransform is a Transform(e, v), i.e. e becomes a matrix once more
+  const double v[3] = {x, y, 0.0};
+  double b2[3][3], q2[4];
+  tf_set_rotation(e, b2);
+  // 4. pcl_ros::transformPointCloud(cloud, cloud, tf::Transform): transform.getRotation() -> Eigen::Quaternionf, origin -> Eigen::Vector3f   (double -> float)
+  tf_get_rotation(b2, q2);
+  const float fx = (float)q2[0], fy = (float)q2[1], fz = (float)q2[2], fw = (float)q2[3];
+  // 5. Translation3f * Quaternionf: Eigen's QuaternionBase::toRotationMatrix in FLOAT   (Eigen 3.2)
+  const float tx = 2.0f * fx, ty = 2.0f * fy, tz = 2.0f * fz;
+  const float twx = tx * fw, twy = ty * fw, twz = tz * fw;
+  const float txx = tx * fx, txy = ty * fx, txz = tz * fx;
+  const float tyy = ty * fy, tyz = tz * fy, tzz = tz * fz;
+  m[0] = 1.0f - (tyy + tzz); m[1] = txy - twz; m[2] = txz + twy; m[3] = (float)v[0];
+  m[4] = txy + twz; m[5] = 1.0f - (txx + tzz); m[6] = tyz - twx; m[7] = (float)v[1];
+  m[8] = txz - twy; m[9] = tyz + twx; m[10] = 1.0f - (txx + tyy); m[11] = (float)v[2];
+}
+
 // the kernels of one fused launch sequence, in order, on the context stream (plain launches, or under stream capture)
 RangeScope::RangeScope(const mot_ctx* c, const char* name) : on(false) {
   if (!c->trace_ranges) return;
@@ -1197,17 +1249,24 @@ extern "C" int mot_host_alloc(size_t bytes, void** out) {
 }
 extern "C" int mot_host_free(void* p) { return (!p || hipHostFree(p) == hipSuccess) ? MOT_OK : MOT_E_HIP; }
 
-// live tracks of every slot -> the caller's HOST block, asynchronously on the context stream (read after mot_synchronize)
-extern "C" int mot_fetch_tracks_async(mot_ctx* c, int batch, void* h_tracks, int max_per_slot, int32_t* h_counts) {
-  if (!c) return MOT_E_ARG;
-  MOT_GUARD(c);
-  if (!h_tracks || !h_counts || batch < 1 || batch > c->batch || max_per_slot < 1) return fail(c, MOT_E_ARG, "mot_fetch_tracks_async: bad argument");
+// the device block of mot_fetch_tracks_async / mot_fetch_tracks_frame_async: grown (never shrunk) to the largest max_per_slot asked for
+static int ensure_fetch_block(mot_ctx* c, int max_per_slot) {
   if (c->fetch_cap < max_per_slot) {
     if (c->d_fetch) { MOT_HIP(c, hipStreamSynchronize(c->stream)); MOT_HIP(c, hipFree(c->d_fetch)); c->d_fetch = nullptr; }
     MOT_HIP(c, hipMalloc(&c->d_fetch, (size_t)c->batch * max_per_slot * sizeof(mot_track)));
     if (!c->d_fetch_counts) MOT_HIP(c, hipMalloc(&c->d_fetch_counts, (size_t)c->batch * sizeof(int)));
     c->fetch_cap = max_per_slot;
   }
+  return MOT_OK;
+}
+
+// live tracks of every slot -> the caller's HOST block, asynchronously on the context stream (read after mot_synchronize)
+extern "C" int mot_fetch_tracks_async(mot_ctx* c, int batch, void* h_tracks, int max_per_slot, int32_t* h_counts) {
+  if (!c) return MOT_E_ARG;
+  MOT_GUARD(c);
+  if (!h_tracks || !h_counts || batch < 1 || batch > c->batch || max_per_slot < 1) return fail(c, MOT_E_ARG, "mot_fetch_tracks_async: bad argument");
+  int rc;
+  if ((rc = ensure_fetch_block(c, max_per_slot))) return rc;
   mot_launch_export_tracks(track_buffers(c, false), batch, c->d_fetch, max_per_slot, c->d_fetch_counts, c->stream);
   MOT_HIP(c, hipGetLastError());
   MOT_HIP(c, hipMemcpyAsync(h_tracks, c->d_fetch, (size_t)batch * max_per_slot * sizeof(mot_track), hipMemcpyDeviceToHost, c->stream));
@@ -2239,6 +2298,133 @@ extern "C" int mot_export_tracks_packed_dev(mot_ctx* c, int batch, void* d_block
   return MOT_OK;
 }
 
+// ---------------------------------------------------------------------------------------- live tracks in the sensor frame
+// both matrices of the pose the slot's dead reckoning holds now (mot_ego_update or a fused step last wrote it; (0, 0, 0) before the first). Host only.
+extern "C" int mot_sensor_pose(mot_ctx* c, int slot, float* sensor_from_global, float* global_from_sensor) {
+  if (!c) return MOT_E_ARG;
+  if (slot < 0 || slot >= c->batch) return fail(c, MOT_E_ARG, "slot out of range");
+  const double* p = c->ego[slot].egoPoint;
+  if (sensor_from_global) tf_global_to_velodyne(p[0], p[1], p[2], sensor_from_global);
+  if (global_from_sensor) tf_velodyne_to_global(p[0], p[1], p[2], global_from_sensor);
+  return MOT_OK;
+}
+
+// The global -> sensor matrices of slots first .. first + n - 1 onto the device, ahead of the export kernel that reads them: one stream-ordered copy from the
+// next block of the page-locked ring. The host waits only when the copy queued from that block kArgRing calls ago has not executed yet.
+static int send_sensor_tf(mot_ctx* c, int first, int n, const EgoTf** d_tf) {
+  if (!c->d_sensor_tf) {
+    MOT_HIP(c, hipMalloc(&c->d_sensor_tf, (size_t)c->batch * sizeof(EgoTf)));
+    MOT_HIP(c, hipHostMalloc(&c->h_sensor_tf, (size_t)c->batch * sizeof(EgoTf) * mot_ctx::kArgRing, hipHostMallocDefault));
+    for (int i = 0; i < mot_ctx::kArgRing; i++) MOT_HIP(c, hipEventCreateWithFlags(&c->sensor_tf_ev[i], hipEventDisableTiming));
+  }
+  const int i = c->sensor_tf_next;
+  if (c->sensor_tf_used[i]) MOT_HIP(c, hipEventSynchronize(c->sensor_tf_ev[i]));
+  EgoTf* blk = c->h_sensor_tf + (size_t)i * c->batch;
+  for (int k = 0; k < n; k++) { const double* p = c->ego[first + k].egoPoint; tf_global_to_velodyne(p[0], p[1], p[2], blk[k].m); }
+  MOT_HIP(c, hipMemcpyAsync(c->d_sensor_tf, blk, (size_t)n * sizeof(EgoTf), hipMemcpyHostToDevice, c->stream));
+  MOT_HIP(c, hipEventRecord(c->sensor_tf_ev[i], c->stream));
+  c->sensor_tf_used[i] = true;
+  c->sensor_tf_next = (i + 1) % mot_ctx::kArgRing;
+  *d_tf = c->d_sensor_tf;
+  return MOT_OK;
+}
+
+extern "C" int mot_export_tracks_frame_dev(mot_ctx* c, int batch, int frame, void* d_tracks, int max_per_slot, int32_t* d_counts) {
+  if (!c) return MOT_E_ARG;
+  if (frame == MOT_FRAME_GLOBAL) return mot_export_tracks_dev(c, batch, d_tracks, max_per_slot, d_counts);
+  MOT_GUARD(c);
+  if (frame != MOT_FRAME_SENSOR) return fail(c, MOT_E_ARG, "mot_export_tracks_frame_dev: frame must be MOT_FRAME_GLOBAL or MOT_FRAME_SENSOR");
+  if (!d_tracks || !d_counts || batch < 1 || batch > c->batch || max_per_slot < 1) return fail(c, MOT_E_ARG, "mot_export_tracks_frame_dev: bad argument");
+  const EgoTf* tf; int rc;
+  if ((rc = send_sensor_tf(c, 0, batch, &tf))) return rc;
+  mot_launch_export_tracks_sensor(track_buffers(c, false), 0, batch, tf, (mot_track*)d_tracks, max_per_slot, (int*)d_counts, c->stream);
+  MOT_HIP(c, hipGetLastError());
+  return MOT_OK;
+}
+
+extern "C" int mot_export_tracks_packed_frame_dev(mot_ctx* c, int batch, int frame, void* d_block, long block_bytes) {
+  if (!c) return MOT_E_ARG;
+  if (frame == MOT_FRAME_GLOBAL) return mot_export_tracks_packed_dev(c, batch, d_block, block_bytes);
+  MOT_GUARD(c);
+  if (frame != MOT_FRAME_SENSOR) return fail(c, MOT_E_ARG, "mot_export_tracks_packed_frame_dev: frame must be MOT_FRAME_GLOBAL or MOT_FRAME_SENSOR");
+  const long head = ((long)batch * 4 + 15) & ~15l;
+  if (!d_block || batch < 1 || batch > c->batch || ((size_t)d_block & 15) || block_bytes < head) return fail(c, MOT_E_ARG, "mot_export_tracks_packed_frame_dev: bad argument");
+  const long cap = (block_bytes - head) / (long)sizeof(mot_track);
+  const EgoTf* tf; int rc;
+  if ((rc = send_sensor_tf(c, 0, batch, &tf))) return rc;
+  mot_launch_export_tracks_packed_sensor(track_buffers(c, false), batch, tf, (int*)d_block, (mot_track*)((char*)d_block + head), (int)(cap > 0x7fffffff ? 0x7fffffff : cap), c->stream);
+  MOT_HIP(c, hipGetLastError());
+  return MOT_OK;
+}
+
+extern "C" int mot_fetch_tracks_frame_async(mot_ctx* c, int batch, int frame, void* h_tracks, int max_per_slot, int32_t* h_counts) {
+  if (!c) return MOT_E_ARG;
+  if (frame == MOT_FRAME_GLOBAL) return mot_fetch_tracks_async(c, batch, h_tracks, max_per_slot, h_counts);
+  MOT_GUARD(c);
+  if (frame != MOT_FRAME_SENSOR) return fail(c, MOT_E_ARG, "mot_fetch_tracks_frame_async: frame must be MOT_FRAME_GLOBAL or MOT_FRAME_SENSOR");
+  if (!h_tracks || !h_counts || batch < 1 || batch > c->batch || max_per_slot < 1) return fail(c, MOT_E_ARG, "mot_fetch_tracks_frame_async: bad argument");
+  int rc;
+  if ((rc = ensure_fetch_block(c, max_per_slot))) return rc;
+  const EgoTf* tf;
+  if ((rc = send_sensor_tf(c, 0, batch, &tf))) return rc;
+  mot_launch_export_tracks_sensor(track_buffers(c, false), 0, batch, tf, c->d_fetch, max_per_slot, c->d_fetch_counts, c->stream);
+  MOT_HIP(c, hipGetLastError());
+  MOT_HIP(c, hipMemcpyAsync(h_tracks, c->d_fetch, (size_t)batch * max_per_slot * sizeof(mot_track), hipMemcpyDeviceToHost, c->stream));
+  MOT_HIP(c, hipMemcpyAsync(h_counts, c->d_fetch_counts, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  return MOT_OK;
+}
+
+// The tracking node's callback (OT/tracking/main.cpp:65-196) in one call: getOriginPoints on the host, then on the device the frame's boxes sensor -> global in the
+// tracker's prologue (mot_track_prep.h, the code the fused sequence runs, fed from a staging buffer of this call's own instead of the box stage's d_boxes),
+// immUkfJpdaf, and the live tracks back in the sensor frame (export_tracks_sensor_kernel on this one stream). One upload, one synchronisation, one batch of copies back.
+extern "C" int mot_tracking_node_frame(mot_ctx* c, int slot, const float* boxes_sensor, int m, double timestamp, double v_gps, double yaw_gps, mot_tracking_frame* out) {
+  if (!c) return MOT_E_ARG;
+  MOT_GUARD(c);
+  if (slot < 0 || slot >= c->batch || m < 0 || (!boxes_sensor && m > 0) || !out) return fail(c, MOT_E_ARG, "mot_tracking_node_frame: slot out of range, negative m, null boxes or null result");
+  if (m > kMaxBoxesPerFrame) return fail(c, MOT_E_ARG, "mot_tracking_node_frame: more boxes in a frame than the library supports (1024): nothing was run");
+  memset(out, 0, sizeof *out);
+  const size_t T = c->max_tracks_total, o_meta = T * sizeof(mot_track);
+  int rc; char* pin;
+  if ((rc = pinned_scratch(c, o_meta + 16, &pin))) return rc;
+  if (!c->d_node_boxes) MOT_HIP(c, hipMalloc(&c->d_node_boxes, (size_t)kMaxBoxesPerFrame * 24 * sizeof(float)));
+  if (!c->d_node_out) MOT_HIP(c, hipMalloc(&c->d_node_out, o_meta + 16));
+  if ((rc = mot_ego_update(c, slot, timestamp, v_gps, yaw_gps, out->origin6))) return rc;
+  {
+    char* blk;
+    if ((rc = arg_block_acquire(c, &blk))) return rc;
+    TrackFrameArgs* targs = reinterpret_cast<TrackFrameArgs*>(blk + c->arg_off_targs);
+    EgoTf* ego = reinterpret_cast<EgoTf*>(blk + c->arg_off_ego);
+    for (int b = 0; b < c->batch; b++) targs[b].run = 0;
+    prepare_track_args(c, targs, slot, m, timestamp, true);
+    tf_velodyne_to_global(c->ego[slot].egoPoint[0], c->ego[slot].egoPoint[1], c->ego[slot].egoPoint[2], ego[slot].m);
+    if ((rc = arg_block_commit(c, c->arg_off_targs, c->arg_off_launch - c->arg_off_targs))) return rc;   // the tracker arguments and the matrices lie back to back
+  }
+  if (m > 0) MOT_HIP(c, hipMemcpyAsync(c->d_node_boxes, boxes_sensor, (size_t)m * 24 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  TrackBuffers t = track_buffers(c, false);
+  // the prologue addresses stream b's sensor-frame boxes at boxes_sensor + b * 1024 * 24 and only the stream that runs reads them: the base is placed so that
+  // `slot` finds the staging buffer (an address computation, nothing is read before it)
+  t.boxes_sensor = reinterpret_cast<const float*>(reinterpret_cast<uintptr_t>(c->d_node_boxes) - (uintptr_t)slot * kMaxBoxesPerFrame * 24 * sizeof(float));
+  t.ego = c->d_ego; t.boxes_out = c->d_tboxes;
+  mot_launch_track(t, c->batch, c->stream);
+  const EgoTf* tf;
+  if ((rc = send_sensor_tf(c, slot, 1, &tf))) return rc;
+  int* d_meta = reinterpret_cast<int*>(c->d_node_out + o_meta);
+  mot_launch_export_tracks_sensor(t, slot, 1, tf, reinterpret_cast<mot_track*>(c->d_node_out), (int)T, d_meta, c->stream);
+  MOT_HIP(c, hipGetLastError());
+  int* meta = reinterpret_cast<int*>(pin + o_meta);
+  MOT_HIP(c, hipMemcpyAsync(pin, c->d_node_out, o_meta + sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  MOT_HIP(c, hipMemcpyAsync(&meta[1], c->d_nt + slot, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  MOT_HIP(c, hipMemcpyAsync(&meta[2], c->d_tflags + slot, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  MOT_HIP(c, hipStreamSynchronize(c->stream));
+  if (meta[0] < 0 || (size_t)meta[0] > T) return fail(c, MOT_E_STATE, "mot_tracking_node_frame: inconsistent counts");
+  c->ego[slot].nt = meta[1];
+  out->n_live = meta[0]; out->n_ever = meta[1]; out->tracks = reinterpret_cast<const mot_track*>(pin);
+  if (meta[2])   // sticky, like mot_get_tracks: the step has run and the records are delivered
+    return fail(c, MOT_E_CAPACITY, "a stream ran out of track slots (more than max_tracks_total tracks alive or just dead) or of its lifetime track budget "
+                                   "(mot_params.max_tracks_ever): births are being dropped; mot_reset_tracks_slot() starts its tracks over");
+  return MOT_OK;
+}
+
 // ---------------------------------------------------------------------------------------- native per-tick gather of the live tracks (RCCL)
 // SURVEY.md 8(e) / BASELINE.json north_star: "frames shard naturally across the 8 x MI355X node with a trivial RCCL/xGMI gather of track outputs",
 // host code in C++. Until round 5 the collective lived in Python (multi.py: torch.distributed.all_gather_into_tensor), which put torch into the
@@ -2493,5 +2679,12 @@ extern "C" int mot_debug_dev_params(mot_ctx* c, void* dst, size_t bytes) {
 extern "C" int mot_debug_tf_matrix(double x, double y, double yaw, float* m12) {
   if (!m12) return MOT_E_ARG;
   tf_velodyne_to_global(x, y, yaw, m12);
+  return MOT_OK;
+}
+
+// test hook (mot_debug_api.h): the float matrix of the way back, global -> sensor, for an ego pose
+extern "C" int mot_debug_tf_matrix_inv(double x, double y, double yaw, float* m12) {
+  if (!m12) return MOT_E_ARG;
+  tf_global_to_velodyne(x, y, yaw, m12);
   return MOT_OK;
 }

@@ -20,6 +20,8 @@ int mot_debug_dev_params(mot_ctx* ctx, void* dst, size_t bytes);
 int mot_debug_skip_kernels(mot_ctx* ctx, int mask);
 /* the float 3 x 4 matrix (row major) the fused path applies to take boxes from the sensor frame to the tracker's global frame */
 int mot_debug_tf_matrix(double x, double y, double yaw, float* m12);
+/* the matrix of the way back: global -> sensor, what the MOT_FRAME_SENSOR exports apply to the track records (mot_sensor_pose's sensor_from_global) */
+int mot_debug_tf_matrix_inv(double x, double y, double yaw, float* m12);
 #ifdef __cplusplus
 }
 #endif

@@ -312,7 +312,7 @@ struct MotTrackParams {
 struct Vec2d { double x, y; };
 struct TrackItem { int b, li; };  // one unit of per-track work: live track `li` (index into the stream's live list) of stream `b`
 // sensor -> global change of frame of the fused path: the float 3 x 4 matrix the tracking node's tf chain ends in
-// (mot_api.hip: tf_velodyne_to_global), row major
+// (mot_api.hip: tf_velodyne_to_global), row major; the MOT_FRAME_SENSOR exports carry the way back (tf_global_to_velodyne) in the same record
 struct EgoTf { float m[12]; };
 
 struct TrackBuffers {
@@ -352,6 +352,9 @@ void mot_launch_track(const TrackBuffers& t, int batch, hipStream_t stream, bool
 void mot_launch_box_finalize_prep(const MotDevParams& p, const ClusterBuffers& c, const TrackBuffers& tb, int batch, hipStream_t stream);
 void mot_launch_export_tracks(const TrackBuffers& t, int batch, mot_track* dst, int max_per_slot, int* dst_counts, hipStream_t stream);
 void mot_launch_export_tracks_packed(const TrackBuffers& t, int batch, int* header, mot_track* dst, int capacity, hipStream_t stream);
+// the same blocks in the SENSOR frame: tf[k] = the global -> sensor matrix of the k-th stream of the launch (streams first .. first + batch - 1; the packed block always starts at stream 0)
+void mot_launch_export_tracks_sensor(const TrackBuffers& t, int first, int batch, const EgoTf* tf, mot_track* dst, int max_per_slot, int* dst_counts, hipStream_t stream);
+void mot_launch_export_tracks_packed_sensor(const TrackBuffers& t, int batch, const EgoTf* tf, int* header, mot_track* dst, int capacity, hipStream_t stream);
 
 #ifdef MOT_HIPEMU
 #define MOT_WAVE_SYNC() ((void)__ballot(1))

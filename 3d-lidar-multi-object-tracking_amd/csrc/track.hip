@@ -1292,6 +1292,73 @@ void mot_launch_export_tracks(const TrackBuffers& t, int batch, mot_track* dst, 
   hipLaunchKernelGGL(export_tracks_kernel, dim3(batch), dim3(kTrackBlock), 0, stream, t.out, t.nlive, t.live, t.T, dst, max_per_slot, dst_counts);
 }
 
+// ---- the same two exports with the records taken back into the SENSOR frame (MOT_FRAME_SENSOR): what the tracking node does to targetPoints and every
+// visBBs[i] before it draws them (OT/tracking/main.cpp:180-196: pcl_ros::transformPointCloud("/velodyne", ...)). `tf` is the stream's global -> sensor
+// matrix (mot_api.hip: tf_global_to_velodyne), per point m(r,0)*x + m(r,1)*y + m(r,2)*z + m(r,3) in fp32, left to right, as pcl::transformPointCloud
+// evaluates it (the build has -ffp-contract=off) — the form of mot_track_prep.h's sensor -> global step.
+// A record is 36 dwords; px, py, pz are dwords 4..6 and the 8 corners of vis_box dwords 12..35 (transformed when is_vis, dword 3, is not 0; a hidden
+// track's zeros stay zeros). A tile of 64 records is 64 x 36 = 9 x 256 dwords: the workgroup loads it into LDS with coalesced dword reads, and after
+// the barrier every thread writes the dwords it loaded — raw, or, for a coordinate, the row of the matrix applied to the triple it belongs to, read
+// from LDS. Every dword of the destination is written once, by consecutive threads.
+constexpr int kRecWords = (int)(sizeof(mot_track) / 4);
+constexpr int kSensorTile = 64;
+static_assert(sizeof(mot_track) == 144 && offsetof(mot_track, is_vis) == 3 * 4 && offsetof(mot_track, px) == 4 * 4 && offsetof(mot_track, vis_box) == 12 * 4 &&
+              (kSensorTile * kRecWords) % 256 == 0, "export_sensor_records works on the dwords of mot_track");
+// ids: the stream's live list; src32: its records by slot; n: records to write; dst32: where the first of them goes. Uniform over the workgroup (256 threads).
+static __device__ void export_sensor_records(const int* __restrict__ ids, const int* __restrict__ src32, const EgoTf* __restrict__ tf, int n, int* __restrict__ dst32) {
+  __shared__ int s_rec[kSensorTile * kRecWords];
+  __shared__ float s_m[12];
+  const int tid = threadIdx.x;
+  if (tid < 12) s_m[tid] = tf->m[tid];
+  for (int i0 = 0; i0 < n; i0 += kSensorTile) {
+    const int words = (n - i0 < kSensorTile ? n - i0 : kSensorTile) * kRecWords;
+    __syncthreads();   // the matrix is there; the previous tile has been written out
+    for (int e = tid; e < words; e += 256) { const int i = e / kRecWords, w = e - i * kRecWords; s_rec[e] = src32[(long)ids[i0 + i] * kRecWords + w]; }
+    __syncthreads();
+    for (int e = tid; e < words; e += 256) {
+      const int i = e / kRecWords, w = e - i * kRecWords;
+      int v = s_rec[e];
+      const int c = w >= 12 ? w - 12 : w - 4;   // index of the coordinate inside its run of triples
+      if ((w >= 4 && w < 7) || (w >= 12 && s_rec[i * kRecWords + 3] != 0)) {
+        const int r = c % 3;
+        const float x = __int_as_float(s_rec[e - r]), y = __int_as_float(s_rec[e - r + 1]), z = __int_as_float(s_rec[e - r + 2]);
+        v = __float_as_int(s_m[4 * r] * x + s_m[4 * r + 1] * y + s_m[4 * r + 2] * z + s_m[4 * r + 3]);
+      }
+      dst32[(long)i0 * kRecWords + e] = v;
+    }
+  }
+}
+// export_tracks_kernel's block. Workgroup k serves stream `first + k` and fills block k of dst / dst_counts with matrix tf[k].
+__global__ void MOT_LAUNCH_BOUNDS(256)
+export_tracks_sensor_kernel(const mot_track* out, const int* nlive, const int* live, int T, int first, const EgoTf* tf, mot_track* dst, int max_per_slot, int* dst_counts) {
+  const int k = blockIdx.x, b = first + k;
+  const int n = nlive[b] < max_per_slot ? nlive[b] : max_per_slot;
+  export_sensor_records(live + (long)b * 2 * T, reinterpret_cast<const int*>(out + (long)b * T), tf + k, n, reinterpret_cast<int*>(dst + (long)k * max_per_slot));
+  if (threadIdx.x == 0) dst_counts[k] = n;
+}
+// export_tracks_packed_kernel's block
+__global__ void MOT_LAUNCH_BOUNDS(256)
+export_tracks_packed_sensor_kernel(const mot_track* out, const int* nlive, const int* live, int T, int batch, const EgoTf* tf, int* header, mot_track* dst, int capacity) {
+  __shared__ int s_part[4];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int before = 0;
+  for (int j = tid; j < b; j += 256) before += nlive[j];
+  before = wave_sum_i32(before);
+  if (lane == 0) s_part[wave] = before;
+  __syncthreads();
+  const int off = s_part[0] + s_part[1] + s_part[2] + s_part[3];
+  const int n = nlive[b];
+  if (tid == 0) header[b] = n;
+  const int fit = capacity - off < 0 ? 0 : capacity - off;   // records of this stream that still fit the block
+  export_sensor_records(live + (long)b * 2 * T, reinterpret_cast<const int*>(out + (long)b * T), tf + b, n < fit ? n : fit, reinterpret_cast<int*>(dst + off));
+}
+void mot_launch_export_tracks_sensor(const TrackBuffers& t, int first, int batch, const EgoTf* tf, mot_track* dst, int max_per_slot, int* dst_counts, hipStream_t stream) {
+  hipLaunchKernelGGL(export_tracks_sensor_kernel, dim3(batch), dim3(256), 0, stream, t.out, t.nlive, t.live, t.T, first, tf, dst, max_per_slot, dst_counts);
+}
+void mot_launch_export_tracks_packed_sensor(const TrackBuffers& t, int batch, const EgoTf* tf, int* header, mot_track* dst, int capacity, hipStream_t stream) {
+  hipLaunchKernelGGL(export_tracks_packed_sensor_kernel, dim3(batch), dim3(256), 0, stream, t.out, t.nlive, t.live, t.T, batch, tf, header, dst, capacity);
+}
+
 void mot_launch_track(const TrackBuffers& t, int batch, hipStream_t stream, bool prep_done) {
 #ifdef MOT_HIPEMU
   const int item_groups = 2;   // the per-track kernels loop over the work list: any grid size gives the same result

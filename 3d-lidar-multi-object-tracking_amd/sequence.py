@@ -62,14 +62,22 @@ def play(ctx, frames, dt_us: float = 1.0e5, t0: float = 1.0e9):
         yield play_frame(ctx, cloud, t0 + k * dt_us, v, yaw)
 
 
-def play_fused(ctx, frames, dt_us: float = 1.0e5, t0: float = 1.0e9, slot_count: int = 1):
+def play_fused(ctx, frames, dt_us: float = 1.0e5, t0: float = 1.0e9, slot_count: int = 1, frame: str = "global"):
     """The same sequence on the THROUGHPUT path: one `frames_host` call per frame (pipelined upload from a page-locked staging
     block, ground -> cluster -> box -> tf -> tracker in one launch sequence, nothing but the results comes back). The change of
     frame is the tracking node's own tf chain (mot_api.hip: tf_velodyne_to_global), not the numpy transform of `play`.
 
     frames: iterable of (cloud, v, yaw) — or of lists of `slot_count` such triples, one per stream. Yields per frame a list of
-    per-stream dicts (boxes in the sensor frame, tracks)."""
+    per-stream dicts (boxes in the sensor frame, tracks).
+
+    frame="sensor": each dict also carries `live`, the stream's live tracks relative to its vehicle at this frame (records of
+    the package's TRACK_DTYPE in id order, `Context.fetch_tracks_async(frame="sensor")`: what the tracking node draws,
+    OT/tracking/main.cpp:180-196). `tracks` stays what it is with the default: every track ever created, global frame."""
     import ctypes as C
+    if frame not in ("global", "sensor"):
+        raise ValueError(f'frame must be "global" or "sensor", not {frame!r}')
+    track_dtype = np.dtype([("id", "i4"), ("track_manage", "i4"), ("is_static", "i4"), ("is_vis", "i4"), ("p", "f4", 3), ("lifetime", "i4"),
+                            ("v_yaw", "f8", 2), ("vis_box", "f4", 24)])   # struct mot_track
     stride = ctx.max_points                       # points between the streams of a batch
     hp = C.c_void_p()
     ctx._ck(ctx.lib.mot_host_alloc(C.c_size_t(slot_count * stride * 16), C.byref(hp)))
@@ -89,7 +97,15 @@ def play_fused(ctx, frames, dt_us: float = 1.0e5, t0: float = 1.0e9, slot_count:
                 n.append(len(a))
             ts = [t0 + k * dt_us] * slot_count
             ctx.frames_host(hp.value, stride * 4, n, run_tracker=True, timestamps=ts, ego_v=[p[1] for p in per], ego_yaw=[p[2] for p in per])
-            yield [dict(boxes=ctx.get_boxes(s)["boxes"], tracks=ctx.get_tracks(s)) for s in range(slot_count)]
+            out = [dict(boxes=ctx.get_boxes(s)["boxes"], tracks=ctx.get_tracks(s)) for s in range(slot_count)]
+            if frame == "sensor":
+                T = ctx.max_tracks_total
+                rec = np.zeros((slot_count, T), track_dtype); cnt = np.zeros(slot_count, np.int32)
+                ctx.fetch_tracks_async(slot_count, rec.ctypes.data, T, cnt.ctypes.data, frame="sensor")
+                ctx.synchronize()
+                for s in range(slot_count):
+                    out[s]["live"] = rec[s, : cnt[s]].copy()
+            yield out
     finally:
         ctx.synchronize()
         ctx.lib.mot_host_free(hp)

@@ -500,6 +500,51 @@ int mot_export_tracks_dev(mot_ctx* ctx, int batch, void* d_tracks, int max_per_s
  * the multi-GPU harness all-gathers: at ~17 live tracks per stream it is a quarter of the fixed 64-slot block. Asynchronous. */
 int mot_export_tracks_packed_dev(mot_ctx* ctx, int batch, void* d_block, long block_bytes);
 
+/* ---------------------------------------------------------------- live tracks in the SENSOR frame
+ * The tracker works in its own global frame (origin: the stream's first pose); the reference never publishes a position in it: OT/tracking/main.cpp:180-196
+ * takes targetPoints and every visBBs[i] back into /velodyne through tf and pcl_ros::transformPointCloud and draws from those. The calls below do that on
+ * the device, per stream, with the pose the stream's dead reckoning holds when the call is made.
+ *
+ * mot_sensor_pose: the two float 3 x 4 matrices (row major) of `slot`'s current pose — after the last mot_ego_update or fused tracker step; the pose
+ * (0, 0, 0) before the first. global_from_sensor is what the fused path applies to the boxes (pcl_ros::transformPointCloud("/global", ...), main.cpp:143-158),
+ * sensor_from_global what the calls below apply (transformPointCloud("/velodyne", ...), :183-184, :195). Each is restated step by step from the tf chain the
+ * node runs (tf LinearMath, tf2 BufferCore, pcl_ros, Eigen in float): they are NOT each other's inverse bit for bit. A point p becomes
+ * m[4r] * p.x + m[4r + 1] * p.y + m[4r + 2] * p.z + m[4r + 3], r = 0..2, in fp32, left to right. Host only, does not synchronise; either pointer may be NULL. */
+int mot_sensor_pose(mot_ctx* ctx, int slot, float sensor_from_global[12], float global_from_sensor[12]);
+
+/* mot_export_tracks_dev / mot_export_tracks_packed_dev / mot_fetch_tracks_async with the frame of the records chosen: same layouts, counts, order,
+ * truncation rules and asynchrony.
+ *   MOT_FRAME_GLOBAL  the existing call (byte-identical output)
+ *   MOT_FRAME_SENSOR  px, py, pz of every record, and the 8 corners of vis_box when is_vis != 0, are replaced by their image under the slot's
+ *                     sensor_from_global matrix; every other field is copied untouched — id, track_manage, is_static, is_vis, lifetime, v, yaw (the
+ *                     reference draws its arrows with targetVandYaw as it is, main.cpp:230-246) and the zeros of a hidden track's vis_box.
+ * The matrices are computed on the host from each slot's dead reckoning at call time and go out in one stream-ordered copy of batch x 48 bytes ahead of
+ * the kernel (page-locked ring: no host synchronisation): the records are those of the pose of the LAST tracker step as long as no mot_ego_update of a
+ * later frame has been made. Cost: unmeasured so far (profiles/sensor_frame_export.md: the method, and the figures once taken). Any other `frame`: MOT_E_ARG. */
+enum { MOT_FRAME_GLOBAL = 0, MOT_FRAME_SENSOR = 1 };
+int mot_export_tracks_frame_dev(mot_ctx* ctx, int batch, int frame, void* d_tracks, int max_per_slot, int32_t* d_counts);
+int mot_export_tracks_packed_frame_dev(mot_ctx* ctx, int batch, int frame, void* d_block, long block_bytes);
+int mot_fetch_tracks_frame_async(mot_ctx* ctx, int batch, int frame, void* h_tracks, int max_per_slot, int32_t* h_counts);
+
+/* The `tracking` node's callback (OT/tracking/main.cpp:65-196, one track_box message) as ONE call: getOriginPoints (mot_ego_update), the frame's boxes
+ * sensor -> global on the device (the tracker prologue of the fused path), immUkfJpdaf, and the live tracks back in the sensor frame. One upload of
+ * m x 24 floats, ONE synchronisation, one device-to-host batch (max_tracks_total records + three counters) into the context's page-locked block; `tracks`
+ * is a VIEW into that block, valid until the next call on this context (like mot_cluster_frame). Results equal, bit for bit, the stage-wise sequence
+ * mot_ego_update -> boxes through global_from_sensor -> mot_track_step -> live records through sensor_from_global; mot_get_tracks / mot_track_get_state
+ * afterwards see the same state.
+ *   m > MOT_MAX_BOXES_PER_FRAME: MOT_E_ARG before anything runs (the ego pose is not advanced either).
+ *   Dropped births: MOT_E_CAPACITY with the records delivered, sticky, as mot_track_step / mot_get_tracks report them: the step has run.
+ *   The boxes go into a staging buffer of their own: the slot's box-stage residency is not touched — mot_get_boxes / mot_box_markers of the slot answer
+ *   what they answered before. */
+typedef struct mot_tracking_frame {
+  double origin6[6];          /* getOriginPoints' egoPoints: what the node broadcasts as tf */
+  int32_t n_live;             /* records below */
+  int32_t n_ever;             /* tracks ever created on the stream: the size of the reference's output vectors */
+  const mot_track* tracks;    /* n_live live tracks in id order, SENSOR frame; view into the context's page-locked block */
+} mot_tracking_frame;
+int mot_tracking_node_frame(mot_ctx* ctx, int slot, const float* boxes_sensor, int m, double timestamp,
+                            double v_gps, double yaw_gps, mot_tracking_frame* out);
+
 /* ---------------------------------------------------------------- cluster-node side products
  * What OT/src/cluster/main.cpp publishes besides the boxes, computed from the elevated cloud and the label grid resident in
  * `slot` (after mot_cluster / mot_box_fit on slot 0, or mot_frames_dev on any slot). SURVEY.md 8(f) rank 3.

@@ -294,4 +294,53 @@ inline void immUkfJpdaf(std::vector<pcl::PointCloud<pcl::PointXYZ>> bBoxes, doub
   for (int i = 0; i < nt; i++) trackManage.push_back(tr[i].track_manage);
 }
 
+// The tracking node's whole callback (OT/tracking/main.cpp:65-196) in the node's own shape — the boxes of a track_box message in the SENSOR frame in, the
+// tf origin and the track outputs back in the SENSOR frame out — as ONE library call (mot_tracking_node_frame): getOriginPoints, the boxes into /global,
+// immUkfJpdaf and the way back through pcl_ros::transformPointCloud("/velodyne", ...) all happen on the device, bit for bit what the node's tf calls
+// compute. What differs from getOriginPoints + immUkfJpdaf above: the outputs hold the LIVE tracks only, in id order (every consumer in the reference
+// skips trackManage == 0), with their reference indices in `ids` (the marker ids of main.cpp:214); targetPoints and visBBs are sensor-frame points
+// already, so the node needs no listener. Dropped births: reported on stderr, the records delivered, the stream's tracks started over — as immUkfJpdaf.
+namespace mot_adapters {
+struct TrackingFrame {
+  std::vector<std::vector<double>> egoPoints;                 // getOriginPoints' two rows: what the node broadcasts as tf
+  std::vector<int> ids;                                       // reference index of every live track below
+  pcl::PointCloud<pcl::PointXYZ> targetPoints;                // sensor frame
+  std::vector<std::vector<double>> targetVandYaw;
+  std::vector<int> trackManage;
+  std::vector<bool> isStaticVec, isVisVec;
+  std::vector<pcl::PointCloud<pcl::PointXYZ>> visBBs;         // sensor frame, one per shown track
+  int tracksEver = 0;                                         // the size the reference's output vectors would have
+};
+inline TrackingFrame trackingNodeFrame(const std::vector<pcl::PointCloud<pcl::PointXYZ>>& bBoxesSensor, double timestamp, double v_gps, double yaw_gps) {
+  std::vector<float> boxes(bBoxesSensor.size() * 24 + 24);
+  for (size_t b = 0; b < bBoxesSensor.size(); b++)
+    for (int k = 0; k < 8; k++) { boxes[(b * 8 + k) * 3] = bBoxesSensor[b][k].x; boxes[(b * 8 + k) * 3 + 1] = bBoxesSensor[b][k].y; boxes[(b * 8 + k) * 3 + 2] = bBoxesSensor[b][k].z; }
+  mot_tracking_frame fr;
+  int rc = mot_tracking_node_frame(context(), 0, boxes.data(), (int)bBoxesSensor.size(), timestamp, v_gps, yaw_gps, &fr);
+  TrackingFrame out;
+  if (rc != MOT_OK && rc != MOT_E_CAPACITY) check(rc);
+  out.egoPoints = {{fr.origin6[0], fr.origin6[1], fr.origin6[2]}, {fr.origin6[3], fr.origin6[4], fr.origin6[5]}};
+  out.tracksEver = fr.n_ever;
+  for (int i = 0; i < fr.n_live; i++) {   // (copied before anything else is called on the context: `tracks` is a view)
+    const mot_track& t = fr.tracks[i];
+    out.ids.push_back(t.id);
+    out.targetPoints.push_back(pcl::PointXYZ(t.px, t.py, t.pz));
+    out.targetVandYaw.push_back({t.v, t.yaw});
+    out.trackManage.push_back(t.track_manage);
+    out.isStaticVec.push_back(t.is_static != 0);
+    out.isVisVec.push_back(t.is_vis != 0);
+    if (t.is_vis) {
+      pcl::PointCloud<pcl::PointXYZ> bb;
+      for (int k = 0; k < 8; k++) bb.push_back(pcl::PointXYZ(t.vis_box[3 * k], t.vis_box[3 * k + 1], t.vis_box[3 * k + 2]));
+      out.visBBs.push_back(bb);
+    }
+  }
+  if (rc == MOT_E_CAPACITY) {   // the step ran, the records are above: births were dropped
+    std::fprintf(stderr, "mot_adapters: %s -- restarting the tracks of this stream\n", mot_last_error(context()));
+    check(mot_reset_tracks_slot(context(), 0));
+  }
+  return out;
+}
+}  // namespace mot_adapters
+
 #endif  // MOT_ADAPTERS_HPP_

@@ -40,6 +40,20 @@ inline void track_step_or_restart(mot_ctx* ctx, int slot, const float* boxes_glo
   check(ctx, rc, "mot_track_step");
 }
 
+// The same policy for the one-call tracking node (mot_tracking_node_frame): dropped births come back as MOT_E_CAPACITY with the live records delivered —
+// warn, let the caller publish them, and start the stream's tracks over with its ego pose kept. `out->tracks` is a view into the context's block: the reset
+// that follows does not touch it (it queues device work only), the next mot_tracking_node_frame does.
+inline void tracking_frame_or_restart(mot_ctx* ctx, int slot, const float* boxes_sensor, int n_boxes, double timestamp, double v_gps, double yaw_gps,
+                                      mot_tracking_frame* out) {
+  const int rc = mot_tracking_node_frame(ctx, slot, boxes_sensor, n_boxes, timestamp, v_gps, yaw_gps, out);
+  if (rc == MOT_E_CAPACITY) {
+    ROS_WARN("tracker: %s — restarting the tracker of this stream (raise ~max_tracks_total to postpone this)", mot_last_error(ctx));
+    check(ctx, mot_reset_tracks_slot(ctx, slot), "mot_reset_tracks_slot");
+    return;
+  }
+  check(ctx, rc, "mot_tracking_node_frame");
+}
+
 // private parameters common to the nodes (read from a NodeHandle("~")): ~device (HIP ordinal), ~max_points, ~preset
 // (0 = object_tracking, 1 = object_tracking0), ~max_tracks_total, ~rng_mapping (how the reference build being replaced maps its
 // mt19937_64 draws to sample indices, include/mot.h: 0 = libstdc++ <= 10 — the compiler of every ROS1 distribution, hence the
