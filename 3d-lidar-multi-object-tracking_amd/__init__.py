@@ -81,6 +81,7 @@ EXPORTS = (
     "mot_track_steps_dev", "mot_profile_kernel", "mot_profile_read", "mot_get_params", "mot_set_fused_outputs", "mot_set_point_order", "mot_set_tracker_mode", "mot_set_trace_ranges", "mot_reset_tracks_slot", "mot_export_tracks_packed_dev", "mot_set_launch_graphs",
     "mot_cluster_node_frame", "mot_ground_node_frame",
     "mot_sensor_pose", "mot_export_tracks_frame_dev", "mot_export_tracks_packed_frame_dev", "mot_fetch_tracks_frame_async", "mot_tracking_node_frame",
+    "mot_set_track_links", "mot_get_box_tracks", "mot_get_point_tracks", "mot_export_point_tracks_dev",
     "mot_gather_unique_id", "mot_gather_create", "mot_gather_contribute", "mot_gather_result", "mot_gather_synchronize", "mot_gather_destroy", "mot_gather_last_error",
 )
 ABI_VERSION = 6
@@ -248,6 +249,28 @@ class Context:
         """MOT_ORDER_SCAN (default) or MOT_ORDER_ANY: clouds in no point order — the box stage regroups the elevated points by cluster on the device
         first; same results, every output in input order, no frame refused for its (tile, cluster) groups"""
         self._ck(self.lib.mot_set_point_order(self._h, int(order)))
+
+    def set_track_links(self, on: bool = True):
+        """keep the tracker's box -> track association per step and compose the per-point track ids at the end of every fused call with the tracker
+        (mot_set_track_links; default off): get_box_tracks, get_point_tracks, export_point_tracks_dev"""
+        self._ck(self.lib.mot_set_track_links(self._h, int(on)))
+
+    def get_box_tracks(self, slot: int = 0, max_boxes: int = 1024) -> np.ndarray:
+        """id of the track that owns every box of the slot's last tracker step, in that step's box order (-1: none)"""
+        out = np.full(max_boxes, -1, np.int32); nb = C.c_int(0)
+        self._ck(self.lib.mot_get_box_tracks(self._h, slot, _vp(out), max_boxes, C.byref(nb)))
+        return out[: nb.value].copy()
+
+    def get_point_tracks(self, slot: int = 0, capacity: int | None = None) -> np.ndarray:
+        """track id of every elevated point of the slot's last fused frame, in the elevated cloud's input order (-1: none)"""
+        cap = self.max_points if capacity is None else capacity
+        out = np.full(cap, -1, np.int32); ne = C.c_int(0)
+        self._ck(self.lib.mot_get_point_tracks(self._h, slot, _vp(out), cap, C.byref(ne)))
+        return out[: ne.value].copy()
+
+    def export_point_tracks_dev(self, batch: int, d_ids_ptr: int, stride: int, d_counts_ptr: int):
+        """the per-point track ids of slots 0..batch-1 -> caller's device block d_ids[b * stride + i] and d_counts[b] (asynchronous)"""
+        self._ck(self.lib.mot_export_point_tracks_dev(self._h, batch, C.c_void_p(d_ids_ptr), C.c_long(stride), C.c_void_p(d_counts_ptr)))
 
     def _track_buffer(self, slot, max_tracks):
         """records a call can deliver: one per track EVER created on the stream, which outgrows the number of slots on a long run"""

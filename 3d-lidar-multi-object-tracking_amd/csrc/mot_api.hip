@@ -28,6 +28,11 @@
 //   slot0_taken (mot_cluster, _box_fit, _cluster_products_host, _cluster_node_frame)  0        no           FromPoints                    no     Foreign                       no
 //   labels_written (mot_get_clusters on demand, mot_cluster with labels)           one         -            Ready                         -      -                             -
 //   box_stage (mot_box_fit, _box_fit_resident, _cluster_node_frame once it fit)    one         -            Ready                         yes    -                             -
+//   every transition above also moves `links` (mot_set_track_links): fused_batch with the tracker and links on -> Points (box stage and tracker step of ONE fused call: the owner
+//   row and the per-point ids belong to the slot's cloud); every other transition that gives the slot a new cloud or new boxes (fused_batch without the tracker, ground_stage,
+//   slot0_taken) takes Points back to Boxes: the owner row still is the last tracker step's, the point chain is broken
+//   tracker_fed (mot_track_step, _track_steps_dev, _tracking_node_frame: boxes from outside)  the slots stepped   links on ? Boxes : as before
+//   links_switched (mot_set_track_links)                                           all         links -> None (no step since)
 //   (fused_batch and box_stage also record `regrouped`: whether the box stage ran on the cluster-ordered copy, MOT_ORDER_ANY; every transition that clears `boxes` clears it)
 //   compaction_rerun (mot_get_ground on demand, mot_time_stage)                    0..batch-1  as run       -                             -      as run, unless Foreign        -
 //   describe_batch (set_batch): the last_* input description. Nothing is vouched for in a slot at or beyond last_batch that needs the batch's input.
@@ -37,6 +42,9 @@ enum LabelState : char { kLabelsFromPoints, kLabelsFromCells, kLabelsReady };
 // d_ground / d_mask of the slot: not (both) resident, a fused batch's can be rebuilt (can_rebuild_ground) / hold the ground cloud and the mask that go with the slot's elevated cloud /
 // belong to ANOTHER cloud: a stage-wise cluster / box call has put its own elevated cloud into the slot since the ground stage ran
 enum GroundState : char { kGroundNone, kGroundResident, kGroundForeign };
+// mot_set_track_links: no tracker step wrote the slot's owner row since the links were turned on / the row is the slot's last tracker step's (mot_get_box_tracks) / and that step
+// was fed by the box stage of the same fused call, whose cloud, cells, label grid and boxes are the slot's: the per-point ids are valid too (mot_get_point_tracks)
+enum LinkState : char { kLinksNone, kLinksBoxes, kLinksPoints };
 struct SlotState {
   bool packed = false;                    // the elevated cloud is 12-byte points (the elevated-only compaction: mot_internal.h PackedXyz), not float4 records
   LabelState labels = kLabelsFromPoints;
@@ -44,6 +52,7 @@ struct SlotState {
   GroundState ground = kGroundNone;
   bool regrouped = false;                 // the box stage ran in MOT_ORDER_ANY: its products (groups, cluster order, first / extreme point indices) index the slot's
                                           // cluster-ordered COPY of the cloud, not the cloud itself. Meaningful while `boxes`; every reader that walks clusters asks.
+  LinkState links = kLinksNone;
 };
 struct Residency {
   std::vector<SlotState> slots;
@@ -56,15 +65,19 @@ struct Residency {
   static bool fused_keeps_ground(int outputs) { return (outputs & (MOT_OUT_GROUND | MOT_OUT_MASK)) == (MOT_OUT_GROUND | MOT_OUT_MASK); }
   // a fused call over slots 0..batch-1 was issued: what those slots hold from now on (the slots beyond keep what an earlier, larger batch left). Host
   // state, so it also holds when a captured graph is replayed: every reader built from cluster_buffers afterwards is told the layout
-  void fused_batch(int batch, int outputs, bool regrouped) {
+  // linked: the call runs the tracker with mot_set_track_links on
+  void fused_batch(int batch, int outputs, bool regrouped, bool linked) {
     last_fused = true;
-    for (int b = 0; b < batch; b++) slots[b] = {fused_packs(outputs), (outputs & MOT_OUT_LABELS) ? kLabelsReady : kLabelsFromCells, true, fused_keeps_ground(outputs) ? kGroundResident : kGroundNone, regrouped};
+    for (int b = 0; b < batch; b++)
+      slots[b] = {fused_packs(outputs), (outputs & MOT_OUT_LABELS) ? kLabelsReady : kLabelsFromCells, true, fused_keeps_ground(outputs) ? kGroundResident : kGroundNone, regrouped,
+                  linked ? kLinksPoints : unlinked(slots[b].links)};
   }
+  static LinkState unlinked(LinkState l) { return l == kLinksPoints ? kLinksBoxes : l; }   // the slot's cloud or boxes are being replaced: its owner row stays the last tracker step's
   // a stage-wise ground stage ran on slot 0 (float4 records); without a mask a later mot_get_ground that asks for one answers MOT_E_STATE
-  void ground_stage(bool with_mask) { last_fused = false; slots[0] = {false, kLabelsFromPoints, false, with_mask ? kGroundResident : kGroundNone}; }
+  void ground_stage(bool with_mask) { last_fused = false; slots[0] = {false, kLabelsFromPoints, false, with_mask ? kGroundResident : kGroundNone, false, unlinked(slots[0].links)}; }
   // slot 0 now holds a stage-wise cluster / box call's cloud, as float4 records: mot_get_ground must not re-run a fused batch's compaction over it, slot 0's ground cloud / mask (if any) are another
   // cloud's (mot_get_ground(0) answers MOT_E_STATE, as include/mot.h promises), what an earlier label kernel or box stage left is stale (mot_box_markers: MOT_E_STATE). The caller then states what it produced.
-  void slot0_taken() { last_fused = false; slots[0] = {false, kLabelsFromPoints, false, kGroundForeign}; }
+  void slot0_taken() { last_fused = false; slots[0] = {false, kLabelsFromPoints, false, kGroundForeign, false, unlinked(slots[0].links)}; }
   // the label kernel ran on the slot's cloud; written = false: in the fused geometry without per-point labels (mot_time_stage)
   void labels_written(int slot, bool written = true) { slots[slot].labels = written ? kLabelsReady : kLabelsFromCells; }
   // the box stage (label kernel included) ran on the slot's cloud: mot_box_markers / mot_get_boxes / mot_get_clusters may read its products
@@ -74,6 +87,11 @@ struct Residency {
   void compaction_rerun(int batch, bool packed, bool ground_and_mask) {
     for (int b = 0; b < batch; b++) { slots[b].packed = packed; if (slots[b].ground != kGroundForeign) slots[b].ground = ground_and_mask ? kGroundResident : kGroundNone; }
   }
+  // a tracker step fed from outside the fused path ran on the slot (links on): its owner row is that step's, over the caller's box list
+  void tracker_fed(int slot) { slots[slot].links = kLinksBoxes; }
+  void links_switched() { for (auto& s : slots) s.links = kLinksNone; }
+  bool box_tracks_valid(int slot) const { return slots[slot].links != kLinksNone; }
+  bool point_tracks_valid(int slot) const { return slots[slot].links == kLinksPoints; }
   bool elev_packed_at(int slot) const { return slots[slot].packed; }
   bool labels_ready(int slot) const { return slots[slot].labels == kLabelsReady; }
   bool cells_usable(int slot) const { return slots[slot].labels == kLabelsFromCells; }
@@ -177,6 +195,11 @@ struct mot_ctx {
   int max_tracks_ever = 0;             // E: capacity of the per-ever-track arrays (positions, slot map, tombstones)
   char* h_pin = nullptr;               // page-locked scratch of the getters' small read-backs (mot_get_tracks: counters, slot bitmap, slot records, per-ever-track
   size_t h_pin_bytes = 0;              // arrays): a copy into pageable memory is staged by the runtime and costs ~10 us apiece whatever its size
+  // mot_set_track_links: allocated at the first request, kept until mot_destroy
+  int track_links = 0;
+  int* d_owner = nullptr;              // [batch][kMaxBoxesPerFrame] box owners of every slot's last tracker step (TrackBuffers::owner)
+  int* d_owner_n = nullptr;            // [batch] boxes of that step
+  int* d_point_track = nullptr;        // [batch][cap] track id of every elevated point (link.hip)
   Vec2d* d_cp = nullptr;
   TrackItem* d_items = nullptr;
   int* d_nitems = nullptr;
@@ -425,7 +448,7 @@ extern "C" void mot_destroy(mot_ctx* c) {
   if (c->h_argring) (void)hipHostFree(c->h_argring);
   void* bufs[] = {c->d_in, c->d_argblk, c->d_ecell, c->d_pairs, c->d_pair_count, c->d_hg, c->d_cell, c->d_desc, c->d_ticket, c->d_elev, c->d_ground, c->d_mask, c->d_counts,
                   c->d_plane_a, c->d_plane_b, c->d_ccl_parent, c->d_occ_list, c->d_occ_count, c->d_grid, c->d_label, c->d_stats, c->d_cand, c->d_boxes, c->d_box_cluster, c->d_rng, c->d_poly, c->d_groups, c->d_cluster_start, c->d_cluster_gstart, c->d_order, c->d_gsorted, c->d_pix, c->d_wgtab, c->d_rg_key, c->d_rg_tmp, c->d_rg_hist, c->d_rg_xyz, c->d_rg_cell, c->d_rg_groups, c->d_rg_gsorted, c->d_rg_gscratch, c->d_side_cell, c->d_side_cloud, c->d_side_obs, c->d_side_cost, c->d_side_counts, c->d_side_chunks, c->d_markers, c->d_raw,
-                  c->d_tracks, c->d_nt, c->d_tboxes, c->d_gate, c->d_prog, c->d_live, c->d_tout, c->d_tflags, c->d_nlive, c->d_pos, c->d_slot_of, c->d_tomb, c->d_used, c->d_zomb, c->d_nzomb, c->d_cp, c->d_items, c->d_nitems};
+                  c->d_tracks, c->d_nt, c->d_tboxes, c->d_gate, c->d_prog, c->d_live, c->d_tout, c->d_tflags, c->d_nlive, c->d_pos, c->d_slot_of, c->d_tomb, c->d_used, c->d_zomb, c->d_nzomb, c->d_cp, c->d_items, c->d_nitems, c->d_owner, c->d_owner_n, c->d_point_track};
   for (void* b : bufs) if (b) (void)hipFree(b);
   if (c->h_counts) (void)hipHostFree(c->h_counts);
   if (c->h_pin) (void)hipHostFree(c->h_pin);
@@ -938,6 +961,7 @@ static void issue_frame_kernels(mot_ctx* c, int batch, int max_n, int run_tracke
   for (int k = 0; k < ((c->dbg_skip >> 8) & 15); k++) mot_launch_noop(batch, c->stream);
   if (!(c->dbg_skip & 2)) { RangeScope rs(c, "mot:cluster"); ProfScope ps(c, kC2); mot_launch_cluster(c->dp, cb, batch, max_n, c->stream, true); }
   RangeScope rb(c, "mot:box");
+  const ClusterBuffers cb_input = cb;   // the frame in input order: what the per-point track ids follow in either point order
   if (c->point_order == MOT_ORDER_ANY) {   // the points into cluster order first; the box stage runs on the copy
     const RegroupBuffers rg = fused_regroup_buffers(c);
     { ProfScope ps(c, kR1); mot_launch_regroup(0, c->dp, cb, rg, batch, max_n, c->stream); }
@@ -954,6 +978,7 @@ static void issue_frame_kernels(mot_ctx* c, int batch, int max_n, int run_tracke
     if (!(c->dbg_skip & 8)) { ProfScope ps(c, kB3); mot_launch_box_finalize_prep(c->dp, cb, tb, batch, c->stream); }
     if (rb.on) { (void)g_roctx.pop(); rb.on = false; }
     if (!(c->dbg_skip & 32)) { RangeScope rt(c, "mot:tracker"); ProfScope ps(c, kT1); mot_launch_track(tb, batch, c->stream, true); }
+    if (c->track_links) { RangeScope rl(c, "mot:links"); mot_launch_point_tracks(c->dp, cb_input, c->d_owner, batch, max_n, c->d_point_track, c->cap, nullptr, c->stream); }
   } else {
     ProfScope ps(c, kB3); mot_launch_box_kernel(2, c->dp, cb, batch, max_n, c->stream);
   }
@@ -989,7 +1014,7 @@ static int launch_frames(mot_ctx* c, int batch, int run_tracker, const double* t
   if ((rc = next_epoch(c))) return rc;
   const int max_n = c->res.last_max_n;
   if ((rc = send_frame_args(c, batch, run_tracker, false, timestamps, ego_v, ego_yaw))) return rc;
-  c->res.fused_batch(batch, c->fused_outputs, c->point_order == MOT_ORDER_ANY);
+  c->res.fused_batch(batch, c->fused_outputs, c->point_order == MOT_ORDER_ANY, run_tracker && c->track_links);
 #ifndef MOT_HIPEMU
   // Few streams per launch = somebody waits for every frame: the sequence's 10-13 launches go out as ONE hipGraph launch, captured
   // once per launch geometry. What differs from call to call without changing the geometry (the cloud's address, the look-back
@@ -1062,7 +1087,7 @@ extern "C" int mot_sequence_dev(mot_ctx* c, const float* d_xyzw, long frame_stri
   if ((rc = next_epoch(c))) return rc;
   const int K = frames, max_n = c->res.last_max_n;
   if ((rc = send_frame_args(c, K, 1, true, timestamps, ego_v, ego_yaw))) return rc;   // one argument block for the whole sequence
-  c->res.fused_batch(K, c->fused_outputs, c->point_order == MOT_ORDER_ANY);
+  c->res.fused_batch(K, c->fused_outputs, c->point_order == MOT_ORDER_ANY, c->track_links != 0);   // (links: row k / the ids of slot k = frame k)
   issue_frame_kernels(c, K, max_n, 0, false);   // slots = frames; ends with the plain box_finalize_kernel
   const TrackBuffers base = track_buffers(c, true);
   RangeScope rt(c, "mot:tracker (sequence)");
@@ -1070,8 +1095,14 @@ extern "C" int mot_sequence_dev(mot_ctx* c, const float* d_xyzw, long frame_stri
     TrackBuffers tb = base;
     tb.args += k; tb.ego += k; tb.m_dev += (long)k * kCountsStride; tb.cp += (long)k * kMaxBoxesPerFrame;
     tb.boxes_sensor += (long)k * kMaxBoxesPerFrame * 24; tb.boxes += (long)k * tb.box_stride; tb.boxes_out += (long)k * tb.box_stride;
+    if (tb.owner) { tb.owner += (long)k * kMaxBoxesPerFrame; tb.owner_n += k; }
     mot_launch_track(tb, 1, c->stream, false);
     if (d_tracks) mot_launch_export_tracks(tb, 1, reinterpret_cast<mot_track*>(d_tracks) + (long)k * max_per_frame, max_per_frame, reinterpret_cast<int*>(d_counts) + k, c->stream);
+  }
+  if (c->track_links) {   // every frame's points against its own owner row, in one launch behind the last step
+    GroundBuffers g; ClusterBuffers cb;
+    fused_buffers(c, &g, &cb);
+    mot_launch_point_tracks(c->dp, cb, c->d_owner, K, max_n, c->d_point_track, c->cap, nullptr, c->stream);
   }
   MOT_HIP(c, hipGetLastError());
   return MOT_OK;
@@ -1852,6 +1883,7 @@ static TrackBuffers track_buffers(mot_ctx* c, bool fused) {
   t.live = c->d_live; t.out = c->d_tout; t.flags = c->d_tflags; t.m_dev = fused ? c->d_counts : nullptr; t.T = c->max_tracks_total;
   t.box_stride = (long)kMaxBoxesPerFrame * 24; t.step_mode = c->tracker_mode;
   t.nlive = c->d_nlive; t.pos = c->d_pos; t.cp = c->d_cp; t.items = c->d_items; t.n_items = c->d_nitems;
+  t.owner = c->track_links ? c->d_owner : nullptr; t.owner_n = c->track_links ? c->d_owner_n : nullptr;
   t.slot_of = c->d_slot_of; t.tomb = c->d_tomb; t.used = c->d_used; t.zomb = c->d_zomb; t.nzomb = c->d_nzomb; t.E = c->max_tracks_ever;
   // fused path: the box stage's boxes (sensor frame) become the tracker's input through the dead-reckoned ego pose
   t.boxes_sensor = fused ? c->d_boxes : nullptr; t.ego = fused ? c->d_ego : nullptr; t.boxes_out = fused ? c->d_tboxes : nullptr;
@@ -2029,6 +2061,100 @@ extern "C" int mot_set_point_order(mot_ctx* c, int order) {
   }
 #endif
   c->point_order = order;
+  return MOT_OK;
+}
+
+// ---------------------------------------------------------------------------------------- boxes and points linked to their tracks
+// mot_set_track_links: every tracker step from now on keeps the association it computes anyway (track.hip "box owners") as a row of box owners per slot, and every
+// fused call that runs the tracker ends with the per-point composition (link.hip). Sticky; off by default, and then nothing of this is launched, written or allocated.
+static int ensure_links(mot_ctx* c) {   // a failure half-way leaves what exists for mot_destroy and the next request; the mode is not entered
+  const size_t B = c->batch;
+  if (!c->d_owner) MOT_HIP(c, hipMalloc(&c->d_owner, B * kMaxBoxesPerFrame * sizeof(int)));
+  if (!c->d_owner_n) MOT_HIP(c, hipMalloc(&c->d_owner_n, B * sizeof(int)));
+  if (!c->d_point_track) MOT_HIP(c, hipMalloc(&c->d_point_track, B * (size_t)c->cap * sizeof(int)));
+  return MOT_OK;
+}
+extern "C" int mot_set_track_links(mot_ctx* c, int on) {
+  if (!c) return MOT_E_ARG;
+  MOT_GUARD(c);
+  on = on ? 1 : 0;
+  if (on == c->track_links) return MOT_OK;
+  if (on) { const int rc = ensure_links(c); if (rc) return rc; }   // MOT_E_HIP: the mode stays as it was
+#ifndef MOT_HIPEMU
+  // the link kernel and the owner pointers are part of the launch sequence: graphs captured in the other mode go (none is running once the stream has drained)
+  if (!c->graphs.empty()) {
+    MOT_HIP(c, hipStreamSynchronize(c->stream));
+    for (auto& ge : c->graphs) if (ge.exec) (void)hipGraphExecDestroy((hipGraphExec_t)ge.exec);
+    c->graphs.clear();
+  }
+#endif
+  c->track_links = on;
+  c->res.links_switched();
+  return MOT_OK;
+}
+
+extern "C" int mot_get_box_tracks(mot_ctx* c, int slot, int32_t* box_track, int max_boxes, int* n_boxes) {
+  if (!c) return MOT_E_ARG;
+  MOT_GUARD(c);
+  if (slot < 0 || slot >= c->batch || max_boxes < 0 || !n_boxes) return fail(c, MOT_E_ARG, "mot_get_box_tracks: slot or max_boxes out of range, or null n_boxes");
+  if (!c->track_links) return fail(c, MOT_E_STATE, "mot_get_box_tracks: track links are off (mot_set_track_links)");
+  if (!c->res.box_tracks_valid(slot)) return fail(c, MOT_E_STATE, "mot_get_box_tracks: no tracker step on this slot since the links were turned on");
+  int rc;
+  if (c->res.point_tracks_valid(slot) && (rc = fetch_counts(c, slot))) return rc;   // the step's boxes came from the slot's own frame: a refused frame says so
+  char* pin;
+  if ((rc = pinned_scratch(c, (size_t)(kMaxBoxesPerFrame + 4) * sizeof(int), &pin))) return rc;
+  int* h = reinterpret_cast<int*>(pin);
+  MOT_HIP(c, hipMemcpyAsync(h, c->d_owner_n + slot, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  MOT_HIP(c, hipMemcpyAsync(h + 4, c->d_owner + (size_t)slot * kMaxBoxesPerFrame, (size_t)kMaxBoxesPerFrame * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  MOT_HIP(c, hipStreamSynchronize(c->stream));
+  const int n = h[0];
+  if (n < 0 || n > kMaxBoxesPerFrame) return fail(c, MOT_E_STATE, "mot_get_box_tracks: inconsistent box count");
+  *n_boxes = n;
+  if (n > max_boxes) return fail(c, MOT_E_CAPACITY, "more boxes than the caller's buffer holds");
+  if (box_track && n > 0) memcpy(box_track, h + 4, (size_t)n * sizeof(int));
+  return MOT_OK;
+}
+
+static int check_point_tracks(mot_ctx* c, int slot, const char* who) {
+  if (!c->track_links) { c->err = std::string(who) + ": track links are off (mot_set_track_links)"; return MOT_E_STATE; }
+  if (!c->res.point_tracks_valid(slot)) {
+    c->err = std::string(who) + ": the slot's cloud, boxes and tracker step do not come from one fused call (a stage-wise call took the slot, the tracker was fed from outside, "
+                                "or no fused call ran the tracker since the links were turned on)";
+    return MOT_E_STATE;
+  }
+  return MOT_OK;
+}
+
+extern "C" int mot_get_point_tracks(mot_ctx* c, int slot, int32_t* ids, int capacity, int* n_elevated) {
+  if (!c) return MOT_E_ARG;
+  MOT_GUARD(c);
+  if (slot < 0 || slot >= c->batch || capacity < 0 || !n_elevated) return fail(c, MOT_E_ARG, "mot_get_point_tracks: slot or capacity out of range, or null n_elevated");
+  int rc;
+  if ((rc = check_point_tracks(c, slot, "mot_get_point_tracks"))) return rc;
+  if ((rc = fetch_counts(c, slot))) return rc;
+  const int ne = c->h_counts[slot * kCountsStride + kCntElev];
+  *n_elevated = ne;
+  if (ne > capacity) return fail(c, MOT_E_CAPACITY, "more elevated points than the caller's id buffer holds");
+  if (ids && ne > 0) {
+    MOT_HIP(c, hipMemcpyAsync(ids, c->d_point_track + (size_t)slot * c->cap, (size_t)ne * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    MOT_HIP(c, hipStreamSynchronize(c->stream));
+  }
+  return MOT_OK;
+}
+
+// the ids of slots 0..batch-1 into the caller's device block, d_ids[b * stride + i], and every slot's elevated count into d_counts[b]: the link kernel again, on what the
+// slots hold, writing there instead of into the library's buffer (the same reads, the same values). Asynchronous on the context stream; a slot with more elevated
+// points than `stride` gets the first `stride` ids (d_counts carries the true count). A frame refused for capacity cannot answer MOT_E_CAPACITY here — nothing is
+// read back — and reads -1 throughout; mot_get_point_tracks on that slot tells.
+extern "C" int mot_export_point_tracks_dev(mot_ctx* c, int batch, int32_t* d_ids, long stride, int32_t* d_counts) {
+  if (!c) return MOT_E_ARG;
+  MOT_GUARD(c);
+  if (!d_ids || !d_counts || batch < 1 || batch > c->batch || stride < 0 || ((size_t)d_ids & 3)) return fail(c, MOT_E_ARG, "mot_export_point_tracks_dev: bad argument");
+  for (int b = 0; b < batch; b++) { const int rc = check_point_tracks(c, b, "mot_export_point_tracks_dev"); if (rc) return rc; }
+  ClusterBuffers cb = cluster_buffers(c, 0);
+  cb.ecell = c->params.num_grid < MOT_MAX_GRID ? c->d_ecell : nullptr;   // (as the fused compaction left them: ground_buffers)
+  mot_launch_point_tracks(c->dp, cb, c->d_owner, batch, c->max_points, reinterpret_cast<int*>(d_ids), stride, reinterpret_cast<int*>(d_counts), c->stream);
+  MOT_HIP(c, hipGetLastError());
   return MOT_OK;
 }
 
@@ -2247,6 +2373,7 @@ extern "C" int mot_track_step(mot_ctx* c, int slot, const float* boxes_global, i
   }
   if (m > 0) MOT_HIP(c, hipMemcpyAsync(c->d_tboxes + (size_t)slot * kMaxBoxesPerFrame * 24, boxes_global, (size_t)m * 24 * sizeof(float), hipMemcpyHostToDevice, c->stream));
   mot_launch_track(track_buffers(c, false), c->batch, c->stream);
+  if (c->track_links) c->res.tracker_fed(slot);
   MOT_HIP(c, hipGetLastError());
   return mot_get_tracks(c, slot, tracks, max_tracks, n_tracks);
 }
@@ -2274,6 +2401,7 @@ extern "C" int mot_track_steps_dev(mot_ctx* c, const float* d_boxes_global, long
   TrackBuffers t = track_buffers(c, false);
   t.boxes = d_boxes_global; t.box_stride = box_stride_floats;
   { ProfScope ps(c, kT1); mot_launch_track(t, batch, c->stream); }
+  if (c->track_links) for (int b = 0; b < batch; b++) c->res.tracker_fed(b);
   MOT_HIP(c, hipGetLastError());
   return MOT_OK;
 }
@@ -2406,6 +2534,7 @@ extern "C" int mot_tracking_node_frame(mot_ctx* c, int slot, const float* boxes_
   t.boxes_sensor = reinterpret_cast<const float*>(reinterpret_cast<uintptr_t>(c->d_node_boxes) - (uintptr_t)slot * kMaxBoxesPerFrame * 24 * sizeof(float));
   t.ego = c->d_ego; t.boxes_out = c->d_tboxes;
   mot_launch_track(t, c->batch, c->stream);
+  if (c->track_links) c->res.tracker_fed(slot);
   const EgoTf* tf;
   if ((rc = send_sensor_tf(c, slot, 1, &tf))) return rc;
   int* d_meta = reinterpret_cast<int*>(c->d_node_out + o_meta);

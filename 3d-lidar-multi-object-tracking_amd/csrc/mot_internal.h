@@ -342,6 +342,10 @@ struct TrackBuffers {
   mot_track* out;               // [B][T] by slot
   int* flags;                   // [B] capacity flags
   const int* m_dev;             // optional: boxes per frame read from counts[b*kCountsStride + kCntBoxes] (fused path)
+  int* owner;                   // [B][kMaxBoxesPerFrame] or null (mot_set_track_links off: nothing is written): reference index of the track that owns box i of
+                                // this step's box list — the track that claimed it (the first live one, in index order, whose claim mask holds it), the
+                                // track born from it, or -1 (the birth was dropped; first frame: every box but the seeded one). A per-frame output, not state.
+  int* owner_n;                 // [B] boxes of the step that wrote the row
   int T;
   int step_mode;                // host only: MOT_TRACKER_AUTO / _SPLIT / _STREAM (mot_set_tracker_mode) — how mot_launch_track launches the step
   MotTrackParams tp;
@@ -355,6 +359,14 @@ void mot_launch_export_tracks_packed(const TrackBuffers& t, int batch, int* head
 // the same blocks in the SENSOR frame: tf[k] = the global -> sensor matrix of the k-th stream of the launch (streams first .. first + batch - 1; the packed block always starts at stream 0)
 void mot_launch_export_tracks_sensor(const TrackBuffers& t, int first, int batch, const EgoTf* tf, mot_track* dst, int max_per_slot, int* dst_counts, hipStream_t stream);
 void mot_launch_export_tracks_packed_sensor(const TrackBuffers& t, int batch, const EgoTf* tf, int* header, mot_track* dst, int capacity, hipStream_t stream);
+
+// ---- per-point track ids (link.hip) ------------------------------------------------------------
+// elevated point -> cell -> cluster label -> box -> owning track, for frames 0..batch-1 of a fused call: ids[b * id_stride + i] = the reference index of the track
+// that owns the box of point i's cluster, -1 where the point has no cluster, the cluster no box, the box no owner, or the frame was refused for capacity. Points
+// at and beyond id_stride are not written; n_out[b] (or null) receives the frame's elevated count. `c` is the frame as the cluster stage left it (input order:
+// never the regrouped view), `owner` the tracker's rows ([batch][kMaxBoxesPerFrame]).
+constexpr int kLinkChunk = 2048;                  // points per workgroup
+void mot_launch_point_tracks(const MotDevParams& p, const ClusterBuffers& c, const int* owner, int batch, int max_n, int* ids, long id_stride, int* n_out, hipStream_t stream);
 
 #ifdef MOT_HIPEMU
 #define MOT_WAVE_SYNC() ((void)__ballot(1))

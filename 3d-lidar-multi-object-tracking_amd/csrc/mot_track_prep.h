@@ -91,6 +91,12 @@ static __device__ void track_prep_body_t(const TrackBuffers& tb, const int b) {
   for (int k = tid; k < M; k += kThreads) { double x, y; cp_from_bbox(boxes + (long)k * 24, &x, &y); cp[k].x = x; cp[k].y = y; }
   if (args.first_frame) {  // :741-795 — seed exactly one track at a hard-coded position; nothing else happens in this frame
     // (also the start of a stream after mot_reset / mot_reset_slot / mot_reset_tracks_slot: every slot is free again)
+    if (tb.owner) {   // box owners: the box at seed_box_index is what makes the reference create track 0 (`if(i == 1)`, :749); no other box is looked at
+      const bool seeded = M > tp.seed_box_index && tb.T >= 1 && tb.E >= 1;
+      int* __restrict__ owner = tb.owner + (long)b * kMaxBoxesPerFrame;
+      for (int k = tid; k < M; k += kThreads) owner[k] = (seeded && k == tp.seed_box_index) ? 0 : -1;
+      if (tid == 0) tb.owner_n[b] = M;
+    }
     unsigned long long* __restrict__ used = tb.used + (long)b * ((tb.T + 63) / 64);
     for (int w = tid; w < (tb.T + 63) / 64; w += kThreads) used[w] = 0ull;
     __syncthreads();

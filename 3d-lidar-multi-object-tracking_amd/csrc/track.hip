@@ -993,6 +993,38 @@ static __device__ void track_finish_body(const TrackBuffers& tb, const int b, co
       if (lane == 0) s_matched[w] = m;
     }
   }
+  // ---- box owners (mot_set_track_links; tb.owner is null otherwise and nothing here runs): WHICH track turned matchingVec[k] from 0 to 1 (:232-250). The
+  // reference walks the tracks in index order, so it is the first track of the live list — which is in that order — whose claim holds box k: its gate mask, its
+  // progressive minima in second initialisation, nothing if a guard skipped it. The same words the lines above OR together, read from global memory in both forms
+  // of the step (the one-launch form's LDS cache holds a copy of word 0 of the same masks), before the merge phase below reuses them. A wave per mask word, a lane
+  // per box; the live tracks are fetched 64 at a time, a lane each, and those that claim anything are handed round in index order. A box nobody claimed keeps -1
+  // here and gets the track born from it in the birth phase. The owner is the track that CLAIMED the box, whatever becomes of it later in the step (the state
+  // machine or the merge phase may leave it dead: track_manage says so).
+  if (tb.owner) {
+    int* __restrict__ owner = tb.owner + (long)b * kMaxBoxesPerFrame;
+    for (int w = wave; w < nW; w += kTrackWaves) {
+      int own = -1;
+      for (int j0 = 0; j0 < nlive; j0 += 64) {
+        const int lj = j0 + lane;
+        unsigned long long m = 0ull;
+        int ref = -1;
+        if (lj < nlive) {
+          const int f = liveok[lj], tj = live[lj];
+          if (f) { m = f == 2 ? prog[(long)tj * kGateWords + w] : gate[(long)tj * kGateWords + w]; ref = tracks[tj].ref_id; }
+        }
+        unsigned long long any = __ballot(m != 0ull);
+        while (any) {   // (uniform over the wave)
+          const int j = __ffsll(any) - 1;
+          any &= any - 1ull;
+          const unsigned long long mj = __shfl(m, j, 64);
+          const int rj = __shfl(ref, j, 64);
+          if (own < 0 && ((mj >> lane) & 1ull)) own = rj;
+        }
+      }
+      if (w * 64 + lane < M) owner[w * 64 + lane] = own;
+    }
+    if (tid == 0) tb.owner_n[b] = M;
+  }
   __syncthreads();
   FIN_T(0);
 
@@ -1115,13 +1147,15 @@ static __device__ void track_finish_body(const TrackBuffers& tb, const int b, co
       if (un) {
         const int r = born + __popcll(um & ((1ull << lane) - 1ull));   // rank among this frame's births
         const int ref = nt0 + r;
-        if (r < nfree && ref < E) {
+        const bool fits = r < nfree && ref < E;
+        if (fits) {
           const int sl = s_free[r];
           const Vec2d c = cp[k];
           s_bbox[r] = (unsigned short)k;   // UKF::UKF + Initialize (track_init): written by the whole workgroup after the barrier
           pos[ref] = c; slot_of[ref] = sl;
           atomicOr(&used[sl >> 6], 1ull << (sl & 63));
         }
+        if (tb.owner) tb.owner[(long)b * kMaxBoxesPerFrame + k] = fits ? ref : -1;   // the box owns the track born from it; a dropped birth leaves it without owner
       }
       born += __popcll(um);
     }

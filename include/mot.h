@@ -382,6 +382,46 @@ int mot_set_fused_outputs(mot_ctx* ctx, int flags);
  * the mode stays as it was. Switching leaves every resident result readable, and drops the captured launch graphs. Unknown order: MOT_E_ARG. */
 int mot_set_point_order(mot_ctx* ctx, int order);
 
+/* ---------------------------------------------------------------- boxes and points linked to their tracks (additions within ABI v6)
+ * Which track does a box — and every elevated point of its cluster — belong to? The tracker decides that itself: the reference's matchingVec
+ * (OT/tracking/imm_ukf_jpda.cpp:205-257, 806, 974-989). on != 0: every tracker step keeps that association as a row of BOX OWNERS per slot, and every
+ * fused call that runs the tracker (mot_frames_*, mot_frame_pointcloud2 with the tracker, mot_sequence_dev) ends with one more streaming kernel that
+ * composes elevated point -> cell -> cluster label -> box -> owner on the device. Default off: nothing is launched, written or allocated, and every other
+ * output is byte-identical either way. Sticky per context. The buffers (4 bytes x max_points + 4 KB per slot) are allocated by the first request:
+ * MOT_E_HIP if that fails, and the mode stays as it was. Switching drops the captured launch graphs (the kernel is part of the captured sequence) and
+ * forgets the rows: the getters below answer MOT_E_STATE until the next step. Not stream state: mot_stream_save / _load do not carry it.
+ * Cost (profiles/track_links.md; 512 streams x 120 k points per launch): on, 0.93 x the frames/s of off; the kernel alone 59 us per 512 frames. Off: 0.999 x a library without it.
+ *
+ * OWNER of box i of a step's box list = the id (mot_track.id, the reference's index into targets_) of
+ *   - the track that turned matchingVec[i] from 0 to 1: tracks are walked in id order; a track skipped by a guard (dead, diverged: :826-851) claims
+ *     nothing; a track in its second initialisation (trackManage 1) marks only its progressive NIS minima (:238-245) and owns those nobody claimed
+ *     before; every other track claims every box inside its gate that nobody claimed before. A box inside two gates belongs to the lower id.
+ *   - or, for a box nobody claimed, the track born from it (:974-989): ids n_ever_before, n_ever_before + 1, ... in box order; -1 if the birth was
+ *     dropped (no free track slot, or max_tracks_ever reached).
+ *   - first frame of a stream (:741-795): the box at seed_box_index owns track 0 (the reference looks at no other box, and seeds nothing when the
+ *     frame has no such box); every other box -1.
+ * The owner is the track that CLAIMED the box, also when that track ends the same step dead (the state machine, or mergeOverSegmentation): consumers
+ * check track_manage of the id, as for every other use of a track. Identical in every tracker mode (mot_set_tracker_mode). */
+int mot_set_track_links(mot_ctx* ctx, int on);
+/* owners of the slot's LAST tracker step, in the order of that step's box list (fused calls: mot_get_boxes' order): box_track[0 .. *n_boxes - 1]. Valid
+ * after mot_frames_*, mot_sequence_dev (slot k = frame k), mot_track_step, mot_track_steps_dev and mot_tracking_node_frame. MOT_E_STATE when links are
+ * off or no step was taken on the slot since they were turned on; MOT_E_CAPACITY (n_boxes delivered, nothing copied) when max_boxes is too small,
+ * and with the limit's message when the step's boxes came from a fused frame that was refused (the per-frame limits under mot_get_ground). */
+int mot_get_box_tracks(mot_ctx* ctx, int slot, int32_t* box_track, int max_boxes, int* n_boxes);
+/* track id of every elevated point of the slot, in the elevated cloud's INPUT order (mot_get_ground's, mot_get_clusters' point_label order; the same in
+ * MOT_ORDER_ANY): ids[i] = owner of the box of point i's cluster; -1 when the point lies in no cluster, the cluster was not kept as a box (min_points, the
+ * rule-based filter, an undefined fit) or the box has no owner. Equals the composition of mot_get_clusters(point_label), mot_get_boxes(box_cluster) and
+ * mot_get_box_tracks. Valid only while the slot's cloud, boxes and tracker step come from ONE fused call: MOT_E_STATE after a stage-wise call took the slot
+ * (mot_cluster, mot_box_fit, mot_ground_remove, ...: slot 0; the other slots stay readable), after a fused call without the tracker, or after a tracker step
+ * fed from outside (mot_track_step, mot_track_steps_dev, mot_tracking_node_frame). MOT_E_CAPACITY with the limit's message on a refused frame, and
+ * (n_elevated delivered, nothing copied) when `capacity` is too small. */
+int mot_get_point_tracks(mot_ctx* ctx, int slot, int32_t* ids, int capacity, int* n_elevated);
+/* the same ids of slots 0..batch-1 into a caller-owned DEVICE block: d_ids[b * stride + i] (int32, 4-byte aligned; 16-byte aligned slots are written
+ * 16 bytes at a time), and every slot's elevated count into d_counts[b]. A slot with more elevated points than `stride` gets the first `stride` ids
+ * (d_counts carries the true count). Asynchronous on the context stream, nothing is read back: a refused frame reads -1 throughout here (mot_get_point_tracks
+ * tells). Same validity rule, for every slot of the batch. */
+int mot_export_point_tracks_dev(mot_ctx* ctx, int batch, int32_t* d_ids, long stride, int32_t* d_counts);
+
 /* on != 0: the fused entry points send their launch sequence (13 kernels with the tracker) as ONE hipGraph launch, captured once per launch geometry
  * (batch, chunks of the largest frame, tracker on / off, outputs); what changes per call without changing the geometry travels in the
  * device-resident argument block. For contexts somebody waits on frame by frame (one or a few streams): the host's part of a frame

@@ -62,6 +62,7 @@ struct Config {
   int max_tracks_total = 16384;   // track SLOTS: tracks alive at the same time
   int max_tracks_ever = 0;        // tracks a stream may create before it is restarted (0 = 64 x max_tracks_total); see immUkfJpdaf below
   int point_order = MOT_ORDER_SCAN;   // MOT_ORDER_ANY: clouds in no point order (merged / filtered clouds): mot_set_point_order
+  bool track_links = false;           // keep every tracker step's box -> track association (mot_set_track_links): mot_adapters::boxTracks()
 };
 inline Config& config() { static Config c; return c; }
 inline void configure(const Config& c) { config() = c; }
@@ -75,6 +76,7 @@ inline mot_ctx* context() {
     if (mot_create(&p, config().device, config().max_points, 1, config().max_tracks_total, &ctx) != MOT_OK)
       throw std::runtime_error("mot_create failed (no MI355X / HIP device?) — this library has no CPU fallback");
     if (mot_set_point_order(ctx, config().point_order) != MOT_OK) throw std::runtime_error(std::string("mot_set_point_order: ") + mot_last_error(ctx));
+    if (config().track_links && mot_set_track_links(ctx, 1) != MOT_OK) throw std::runtime_error(std::string("mot_set_track_links: ") + mot_last_error(ctx));
   }
   return ctx;
 }
@@ -340,6 +342,17 @@ inline TrackingFrame trackingNodeFrame(const std::vector<pcl::PointCloud<pcl::Po
     check(mot_reset_tracks_slot(context(), 0));
   }
   return out;
+}
+
+// With config().track_links: the id (index into the reference's targets_) of the track that owns every box handed to the LAST immUkfJpdaf / trackingNodeFrame
+// call, in the order of that call's boxes; -1 where a box has no owner (mot_get_box_tracks in include/mot.h defines "owner"). The node shells feed the tracker
+// stage by stage, so the per-point ids (mot_get_point_tracks) belong to the fused entry points, not to these adapters: a consumer that wants them per point
+// indexes this vector with the box of each point's cluster.
+inline std::vector<int> boxTracks() {
+  std::vector<int32_t> own(MOT_MAX_BOXES_PER_FRAME);
+  int n = 0;
+  check(mot_get_box_tracks(context(), 0, own.data(), (int)own.size(), &n));
+  return std::vector<int>(own.begin(), own.begin() + n);
 }
 }  // namespace mot_adapters
 
