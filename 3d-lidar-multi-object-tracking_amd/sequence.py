@@ -65,7 +65,7 @@ def play(ctx, frames, dt_us: float = 1.0e5, t0: float = 1.0e9):
 def play_fused(ctx, frames, dt_us: float = 1.0e5, t0: float = 1.0e9, slot_count: int = 1, frame: str = "global"):
     """The same sequence on the THROUGHPUT path: one `frames_host` call per frame (pipelined upload from a page-locked staging
     block, ground -> cluster -> box -> tf -> tracker in one launch sequence, nothing but the results comes back). The change of
-    frame is the tracking node's own tf chain (mot_api.hip: tf_velodyne_to_global), not the numpy transform of `play`.
+    frame is the tracking node's own tf chain (mot_api_tracks.hip: tf_velodyne_to_global), not the numpy transform of `play`.
 
     frames: iterable of (cloud, v, yaw) — or of lists of `slot_count` such triples, one per stream. Yields per frame a list of
     per-stream dicts (boxes in the sensor frame, tracks).

@@ -4,7 +4,7 @@
 //
 // The whole callback is one library call (mot_tracking_node_frame): the ego dead reckoning, the boxes' change of frame velodyne -> global, the IMM-UKF-PDA
 // step over all tracks of the stream and the live tracks' way back into the sensor frame run on the GPU — the frame changes in the arithmetic of the tf /
-// pcl_ros calls the reference makes, bit for bit (csrc/mot_api.hip: tf_velodyne_to_global, tf_global_to_velodyne). The node broadcasts the tf from the
+// pcl_ros calls the reference makes, bit for bit (csrc/mot_api_tracks.hip: tf_velodyne_to_global, tf_global_to_velodyne). The node broadcasts the tf from the
 // origin it gets back and draws from sensor-frame records; it has no listener.
 #include <cmath>
 

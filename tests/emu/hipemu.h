@@ -364,15 +364,29 @@ static inline hipError_t hipGetDeviceCount(int* n) { *n = 1; return hipSuccess; 
 static inline hipError_t hipSetDevice(int) { return hipSuccess; }
 static inline hipError_t hipGetDevice(int* d) { *d = 0; return hipSuccess; }
 static inline hipError_t hipGetDeviceProperties(hipDeviceProp_t* p, int) { memset(p, 0, sizeof *p); strcpy(p->name, "hipemu"); strcpy(p->gcnArchName, "gfx950:emulated"); p->multiProcessorCount = 256; return hipSuccess; }
+// What is allocated / created and not yet freed / destroyed, and an injected failure: lets a CPU test see that a context gives back everything it took, whichever
+// lazy path took it, and walk an allocating call through a failure at each of its allocations (tests/test_emu_lifecycle.py). Emulator-only accessors, like
+// hipemu_launch_count: hipemu_live_allocs(), hipemu_live_events(); hipemu_fail_alloc_at(k): the k-th hipMalloc / hipHostMalloc / hipEventCreate* from now on
+// returns an error, once (0: off).
+namespace hipemu {
+struct Ledger { long allocs = 0, events = 0, fail_at = 0; std::mutex mu; };
+inline Ledger& ledger() { static Ledger l; return l; }
+inline bool refuse_alloc() { Ledger& l = ledger(); std::lock_guard<std::mutex> g(l.mu); return l.fail_at > 0 && --l.fail_at == 0; }
+inline void count_live(long Ledger::*what, long by) { Ledger& l = ledger(); std::lock_guard<std::mutex> g(l.mu); l.*what += by; }
+}  // namespace hipemu
+extern "C" __attribute__((weak, used, visibility("default"))) long hipemu_live_allocs() { std::lock_guard<std::mutex> g(hipemu::ledger().mu); return hipemu::ledger().allocs; }
+extern "C" __attribute__((weak, used, visibility("default"))) long hipemu_live_events() { std::lock_guard<std::mutex> g(hipemu::ledger().mu); return hipemu::ledger().events; }
+extern "C" __attribute__((weak, used, visibility("default"))) void hipemu_fail_alloc_at(long k) { std::lock_guard<std::mutex> g(hipemu::ledger().mu); hipemu::ledger().fail_at = k; }
 // device memory arrives poisoned (0xFF: NaN floats, -1 ints) so that reads of never-written memory show up in the tests
 static inline hipError_t hipMalloc(void** p, size_t n) {   // 256-byte aligned like the device allocator (types with alignas(64) live in these buffers)
+  if (hipemu::refuse_alloc()) { *p = nullptr; return 2; }
   const size_t m = ((n ? n : 1) + 255) & ~(size_t)255;
-  *p = aligned_alloc(256, m); if (*p) memset(*p, 0xFF, m); return *p ? hipSuccess : 2; }
+  *p = aligned_alloc(256, m); if (*p) { memset(*p, 0xFF, m); hipemu::count_live(&hipemu::Ledger::allocs, 1); } return *p ? hipSuccess : 2; }
 template <typename T> static inline hipError_t hipMalloc(T** p, size_t n) { return hipMalloc((void**)p, n); }
 static inline hipError_t hipHostMalloc(void** p, size_t n, unsigned = 0) { return hipMalloc(p, n); }
 template <typename T> static inline hipError_t hipHostMalloc(T** p, size_t n, unsigned f = 0) { return hipHostMalloc((void**)p, n, f); }
-static inline hipError_t hipFree(void* p) { free(p); return hipSuccess; }
-static inline hipError_t hipHostFree(void* p) { free(p); return hipSuccess; }
+static inline hipError_t hipFree(void* p) { if (p) hipemu::count_live(&hipemu::Ledger::allocs, -1); free(p); return hipSuccess; }
+static inline hipError_t hipHostFree(void* p) { return hipFree(p); }
 static inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { if (n) memmove(d, s, n); return hipSuccess; }
 static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind k, hipStream_t) { return hipMemcpy(d, s, n, k); }
 static inline hipError_t hipMemset(void* d, int v, size_t n) { if (n) memset(d, v, n); return hipSuccess; }
@@ -391,11 +405,13 @@ static inline hipError_t hipDeviceSynchronize() { return hipSuccess; }
 static inline long long hipemu_now_ns();
 static inline double hipemu_now() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; }
 static inline long long hipemu_now_ns() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1000000000ll + ts.tv_nsec; }
-static inline hipError_t hipEventCreate(hipEvent_t* e) { *e = new hipemu_event{0}; return hipSuccess; }
+static inline hipError_t hipEventCreate(hipEvent_t* e) {
+  if (hipemu::refuse_alloc()) { *e = nullptr; return 2; }
+  *e = new hipemu_event{0}; hipemu::count_live(&hipemu::Ledger::events, 1); return hipSuccess; }
 constexpr unsigned hipEventDisableTiming = 2;
-static inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = new hipemu_event{0}; return hipSuccess; }
+static inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { return hipEventCreate(e); }
 static inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }  // the emulator is synchronous
-static inline hipError_t hipEventDestroy(hipEvent_t e) { delete e; return hipSuccess; }
+static inline hipError_t hipEventDestroy(hipEvent_t e) { if (e) hipemu::count_live(&hipemu::Ledger::events, -1); delete e; return hipSuccess; }
 static inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t) { e->t = hipemu_now(); return hipSuccess; }
 static inline hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
 static inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) { *ms = (float)(b->t - a->t); return hipSuccess; }

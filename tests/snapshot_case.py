@@ -27,7 +27,7 @@ def _same(a: dict, b: dict):
 
 
 def _meta(blob: bytes):
-    """(header, slot bitmap) of a snapshot — mot_api.hip's SnapshotHeader: five uint32 (magic, abi, header bytes, track bytes, record bytes),
+    """(header, slot bitmap) of a snapshot — mot_api_tracks.hip's SnapshotHeader: five uint32 (magic, abi, header bytes, track bytes, record bytes),
     then int32 T, nt, nlive, nzomb, flags; the bitmap follows the T track records and the two T-int lists"""
     u = np.frombuffer(blob[:40], np.uint32)
     hb, tb, T = int(u[2]), int(u[3]), int(u[5])

@@ -1,4 +1,4 @@
-"""What every slot holds after every call that changes it (the transition table above `struct Residency` in csrc/mot_api.hip), walked on
+"""What every slot holds after every call that changes it (the transition table above `struct Residency` in csrc/mot_host.h), walked on
 the emulator build in two-step pairs: a fused batch over slots 0 and 1, then ONE call that changes what slot 0 holds, then ONE getter on
 slot 0 or on slot 1 (the other slot of the earlier batch) — a fresh context per cell, since a getter may itself materialise something.
 

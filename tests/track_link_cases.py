@@ -473,7 +473,7 @@ def state_error(env, fn, what):
 
 
 def snapshot_items(blob):
-    """what a snapshot DEFINES, by name (csrc/mot_api.hip mot_stream_save: header, T track records, the live and just-died lists, the slot bitmap, T output records, then
+    """what a snapshot DEFINES, by name (csrc/mot_api_tracks.hip mot_stream_save: header, T track records, the live and just-died lists, the slot bitmap, T output records, then
     the per-ever-track arrays): the records of slots not in use and the tails of the two lists are whatever the context's memory held — two contexts differ there"""
     u = np.frombuffer(blob[:40], np.uint32)
     hb, tb, rb, T, nt, nlive, nzomb = int(u[2]), int(u[3]), int(u[4]), int(u[5]), int(u[6]), int(u[7]), int(u[8])

@@ -13,7 +13,7 @@ B = importlib.util.module_from_spec(spec); spec.loader.exec_module(B)
 
 rows = []
 for src in B.SOURCES:
-    if src == "mot_api.hip":
+    if src in B.HOST_SOURCES:
         continue
     flags = [f for f in B.HIPCC_FLAGS if f not in ("-shared", "-fPIC")]
     r = subprocess.run([B.hipcc()] + flags + ["-c", os.path.join(B.CSRC, src), "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"],
