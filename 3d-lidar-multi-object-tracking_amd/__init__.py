@@ -20,7 +20,8 @@ MOT_OK, MOT_E_ARG, MOT_E_CAPACITY, MOT_E_HIP, MOT_E_STATE = 0, 1, 2, 3, 4
 MOT_MAX_BOXES_PER_FRAME = 1024   # include/mot.h
 MOT_TRACKER_AUTO, MOT_TRACKER_SPLIT, MOT_TRACKER_STREAM = 0, 1, 2   # mot_set_tracker_mode (include/mot.h)
 MOT_ORDER_SCAN, MOT_ORDER_ANY = 0, 1   # mot_set_point_order (include/mot.h)
-MOT_FRAME_GLOBAL, MOT_FRAME_SENSOR = 0, 1   # mot_export_tracks*_frame_dev, mot_fetch_tracks_frame_async (include/mot.h)
+MOT_FRAME_GLOBAL, MOT_FRAME_SENSOR = 0, 1   # mot_export_tracks*_frame_dev, mot_fetch_tracks_frame_async, mot_*_track_points* (include/mot.h)
+MOT_TRACK_POINTS_REST = 1   # mot_export_track_points_dev / mot_get_track_points flags (include/mot.h)
 PRESET_OBJECT_TRACKING, PRESET_OBJECT_TRACKING0 = 0, 1
 MASK_DROPPED, MASK_GROUND, MASK_ELEVATED = 0, 1, 2
 NUM_CHANNEL, NUM_BIN = 80, 120
@@ -65,6 +66,22 @@ class MotTrackState(C.Structure):
                 ("has_best_box", C.c_int32), ("_pad", C.c_int32), ("bbox", C.c_float * 24), ("best_bbox", C.c_float * 24)]
 
 
+class MotTrackSegment(C.Structure):
+    """struct mot_track_segment"""
+    _fields_ = [("track_id", C.c_int32), ("first", C.c_int32), ("count", C.c_int32), ("n_boxes", C.c_int32)]
+
+
+class MotTrackPoint(C.Structure):
+    """struct mot_track_point"""
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("index", C.c_int32)]
+
+
+assert C.sizeof(MotTrackSegment) == 16 and C.sizeof(MotTrackPoint) == 16
+# the same two records as numpy dtypes
+TRACK_SEGMENT_DTYPE = np.dtype([("track_id", "i4"), ("first", "i4"), ("count", "i4"), ("n_boxes", "i4")])
+TRACK_POINT_DTYPE = np.dtype([("xyz", "f4", 3), ("index", "i4")])
+
+
 class MotError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"mot error {code}: {msg}")
@@ -82,6 +99,7 @@ EXPORTS = (
     "mot_cluster_node_frame", "mot_ground_node_frame",
     "mot_sensor_pose", "mot_export_tracks_frame_dev", "mot_export_tracks_packed_frame_dev", "mot_fetch_tracks_frame_async", "mot_tracking_node_frame",
     "mot_set_track_links", "mot_get_box_tracks", "mot_get_point_tracks", "mot_export_point_tracks_dev",
+    "mot_export_track_points_dev", "mot_get_track_points",
     "mot_gather_unique_id", "mot_gather_create", "mot_gather_contribute", "mot_gather_result", "mot_gather_synchronize", "mot_gather_destroy", "mot_gather_last_error",
 )
 ABI_VERSION = 6
@@ -271,6 +289,23 @@ class Context:
     def export_point_tracks_dev(self, batch: int, d_ids_ptr: int, stride: int, d_counts_ptr: int):
         """the per-point track ids of slots 0..batch-1 -> caller's device block d_ids[b * stride + i] and d_counts[b] (asynchronous)"""
         self._ck(self.lib.mot_export_point_tracks_dev(self._h, batch, C.c_void_p(d_ids_ptr), C.c_long(stride), C.c_void_p(d_counts_ptr)))
+
+    def get_track_points(self, slot: int = 0, rest: bool = False, frame=MOT_FRAME_SENSOR, point_capacity: int | None = None, max_segments: int = MOT_MAX_BOXES_PER_FRAME + 1):
+        """the slot's elevated points stably partitioned by owning track (mot_get_track_points): xyz [n, 3] (sensor frame: the elevated points' bits; "global":
+        under the matrix the slot's boxes took), index [n] (position in the elevated cloud's input order), and per segment track_id (ascending; -1: the rest
+        segment, with rest=True), first, count, n_boxes"""
+        cap = self.max_points if point_capacity is None else point_capacity
+        pts = np.zeros(max(cap, 1), TRACK_POINT_DTYPE); seg = np.zeros(max(max_segments, 1), TRACK_SEGMENT_DTYPE); npts, nseg = C.c_int(0), C.c_int(0)
+        self._ck(self.lib.mot_get_track_points(self._h, slot, MOT_TRACK_POINTS_REST if rest else 0, _frame(frame), _vp(pts), cap, _vp(seg), max_segments, C.byref(npts), C.byref(nseg)))
+        pts, seg = pts[: npts.value], seg[: nseg.value]
+        return dict(xyz=pts["xyz"].copy(), index=pts["index"].copy(), track_id=seg["track_id"].copy(), first=seg["first"].copy(), count=seg["count"].copy(), n_boxes=seg["n_boxes"].copy())
+
+    def export_track_points_dev(self, batch: int, d_points_ptr: int, point_stride: int, d_segments_ptr: int, max_segments: int, d_counts_ptr: int, rest: bool = False,
+                                frame=MOT_FRAME_SENSOR):
+        """the same for slots 0..batch-1 -> caller's device blocks: 16-byte records d_points[b * point_stride + i] and d_segments[b * max_segments + k], the true
+        numbers of segments and records in d_counts[2 b], d_counts[2 b + 1] (asynchronous)"""
+        self._ck(self.lib.mot_export_track_points_dev(self._h, batch, MOT_TRACK_POINTS_REST if rest else 0, _frame(frame), C.c_void_p(d_points_ptr), C.c_long(point_stride),
+                                                      C.c_void_p(d_segments_ptr), int(max_segments), C.c_void_p(d_counts_ptr)))
 
     def _track_buffer(self, slot, max_tracks):
         """records a call can deliver: one per track EVER created on the stream, which outgrows the number of slots on a long run"""

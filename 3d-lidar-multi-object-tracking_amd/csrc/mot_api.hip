@@ -613,6 +613,7 @@ static int send_frame_args(mot_ctx* c, int batch, int run_tracker, bool one_stre
       const int s = one_stream ? 0 : b;   // the stream whose ego / tracker state entry b advances
       MOT_TRY(mot_ego_update(c, s, timestamps[b], ego_v[b], ego_yaw[b], nullptr));
       tf_velodyne_to_global(c->ego[s].egoPoint[0], c->ego[s].egoPoint[1], c->ego[s].egoPoint[2], ego[b].m);
+      if (c->track_links) c->link_tf[b] = ego[b];   // what mot_export_track_points_dev applies to slot b's points (the argument block is rewritten by every later call)
       TrackFrameArgs one[1];
       prepare_track_args(c, one_stream ? one : targs, s, 0, timestamps[b], true);   // (fills entry s of the array it is given)
       if (one_stream) targs[b] = one[0];
@@ -915,6 +916,7 @@ static int ensure_links(mot_ctx* c) {   // a failure half-way leaves what exists
   MOT_TRY(dev_alloc(c, &c->d_owner, B * kMaxBoxesPerFrame * sizeof(int)));
   MOT_TRY(dev_alloc(c, &c->d_owner_n, B * sizeof(int)));
   MOT_TRY(dev_alloc(c, &c->d_point_track, B * (size_t)c->cap * sizeof(int)));
+  c->link_tf.resize(B);
   return MOT_OK;
 }
 extern "C" int mot_set_track_links(mot_ctx* c, int on) {

@@ -306,6 +306,98 @@ extern "C" int mot_export_point_tracks_dev(mot_ctx* c, int batch, int32_t* d_ids
   return MOT_OK;
 }
 
+// ---------------------------------------------------------------------------------------- per-track point clouds (track_points.hip)
+// Scratch of the feature's own, at its first call; a failure half-way leaves what exists for mot_destroy and the next call, which resumes. Sized from max_points
+// (c->cap is max_points rounded up to 64). Nothing here aliases what a getter reads: the kernels read the ids, the input-order cloud, the counters and the owner
+// rows, and write only these buffers and the caller's blocks — MOT_ORDER_ANY's cluster-ordered copy (mot_box_markers reads it later) is not touched.
+static int ensure_track_points(mot_ctx* c, bool host_stage) {
+  const size_t B = c->batch;
+  c->tp_chunks = (c->cap + kTrackPointChunk - 1) / kTrackPointChunk;
+  MOT_TRY(dev_alloc(c, &c->d_tp_seg_id, B * kMaxBoxesPerFrame * sizeof(int)));
+  MOT_TRY(dev_alloc(c, &c->d_tp_seg_boxes, B * kMaxBoxesPerFrame * sizeof(int)));
+  MOT_TRY(dev_alloc(c, &c->d_tp_seg_n, B * sizeof(int)));
+  MOT_TRY(dev_alloc(c, &c->d_tp_rows, B * (size_t)c->tp_chunks * kTrackPointKeys * sizeof(int)));
+  MOT_TRY(dev_alloc(c, &c->d_tp_tf, B * sizeof(EgoTf)));
+  MOT_TRY(c->tp_tf_ring.create(c, B * sizeof(EgoTf)));
+  if (host_stage) MOT_TRY(dev_alloc(c, &c->d_tp_stage, (size_t)c->cap * sizeof(mot_track_point) + (size_t)kTrackPointKeys * sizeof(mot_track_segment) + 16));
+  return MOT_OK;
+}
+static int check_track_points_args(mot_ctx* c, const char* who, int flags, int frame) {
+  if (flags & ~MOT_TRACK_POINTS_REST) return fail(c, MOT_E_ARG, who, ": unknown flag bits");
+  if (frame != MOT_FRAME_GLOBAL && frame != MOT_FRAME_SENSOR) return fail(c, MOT_E_ARG, who, ": frame must be MOT_FRAME_GLOBAL or MOT_FRAME_SENSOR");
+  return MOT_OK;
+}
+// the four kernels over slots first .. first + n - 1, block k of the caller's buffers for slot first + k. The slots of one launch share the layout of their clouds (12- or
+// 16-byte points: slots filled by fused calls under different mot_set_fused_outputs may differ), so a batch goes out as one launch per run of slots of one layout — one, as a rule.
+static int launch_track_points(mot_ctx* c, int first, int n, int flags, int frame, mot_track_point* d_points, long point_stride, mot_track_segment* d_segments, int max_segments,
+                               int* d_counts) {
+  const EgoTf* tf = nullptr;
+  if (frame == MOT_FRAME_GLOBAL) {   // the matrices the slots' boxes took, in one stream-ordered copy ahead of the kernels
+    char* raw;
+    MOT_TRY(c->tp_tf_ring.acquire(c, &raw));
+    memcpy(raw, c->link_tf.data() + first, (size_t)n * sizeof(EgoTf));
+    MOT_TRY(c->tp_tf_ring.commit(c, c->d_tp_tf, 0, (size_t)n * sizeof(EgoTf), c->stream));
+    tf = c->d_tp_tf;
+  }
+  TrackPointBuffers t;
+  t.ids = c->d_point_track; t.elevated = c->d_elev; t.cap = c->cap; t.counts = c->d_counts; t.owner = c->d_owner;
+  t.seg_id = c->d_tp_seg_id; t.seg_boxes = c->d_tp_seg_boxes; t.seg_n = c->d_tp_seg_n; t.rows = c->d_tp_rows; t.max_chunks = c->tp_chunks;
+  for (int k0 = 0; k0 < n;) {
+    int k1 = k0 + 1;
+    while (k1 < n && c->res.elev_packed_at(first + k1) == c->res.elev_packed_at(first + k0)) k1++;
+    t.elevated_packed = c->res.elev_packed_at(first + k0) ? 1 : 0;
+    mot_launch_track_points(t, first + k0, k1 - k0, c->max_points, flags & MOT_TRACK_POINTS_REST, tf ? tf + k0 : nullptr, d_points + (long)k0 * point_stride, point_stride,
+                            d_segments + (long)k0 * max_segments, max_segments, d_counts + 2 * k0, c->stream);
+    k0 = k1;
+  }
+  MOT_HIP(c, hipGetLastError());
+  return MOT_OK;
+}
+
+extern "C" int mot_export_track_points_dev(mot_ctx* c, int batch, int flags, int frame, mot_track_point* d_points, long point_stride, mot_track_segment* d_segments, int max_segments,
+                                           int32_t* d_counts) {
+  if (!c) return MOT_E_ARG;
+  MOT_GUARD(c);
+  const char* who = "mot_export_track_points_dev";
+  MOT_TRY(check_track_points_args(c, who, flags, frame));
+  if (!d_points || !d_segments || !d_counts || batch < 1 || batch > c->batch || point_stride < 0 || max_segments < 0 || (((size_t)d_points | (size_t)d_segments | (size_t)d_counts) & 3))
+    return fail(c, MOT_E_ARG, who, ": bad argument");
+  for (int b = 0; b < batch; b++) MOT_TRY(check_point_tracks(c, b, who));
+  MOT_TRY(ensure_track_points(c, false));
+  return launch_track_points(c, 0, batch, flags, frame, d_points, point_stride, d_segments, max_segments, reinterpret_cast<int*>(d_counts));
+}
+
+extern "C" int mot_get_track_points(mot_ctx* c, int slot, int flags, int frame, mot_track_point* points, int point_capacity, mot_track_segment* segments, int max_segments,
+                                    int* n_points, int* n_segments) {
+  if (!c) return MOT_E_ARG;
+  MOT_GUARD(c);
+  const char* who = "mot_get_track_points";
+  MOT_TRY(check_track_points_args(c, who, flags, frame));
+  if (slot < 0 || slot >= c->batch || point_capacity < 0 || max_segments < 0 || !n_points || !n_segments) return fail(c, MOT_E_ARG, who, ": slot or a capacity out of range, or a null count");
+  MOT_TRY(check_point_tracks(c, slot, who));
+  MOT_TRY(ensure_track_points(c, true));
+  MOT_TRY(fetch_counts(c, slot));   // a refused frame says so
+  // the slot alone into the staging block — [cap records][1025 segments][2 counts] — with the block's own capacities; what fits the caller's buffers is decided here
+  mot_track_point* d_pts = reinterpret_cast<mot_track_point*>(c->d_tp_stage);
+  mot_track_segment* d_seg = reinterpret_cast<mot_track_segment*>(c->d_tp_stage + (size_t)c->cap * sizeof(mot_track_point));
+  int* d_cnt = reinterpret_cast<int*>(d_seg + kTrackPointKeys);
+  MOT_TRY(launch_track_points(c, slot, 1, flags, frame, d_pts, c->cap, d_seg, kTrackPointKeys, d_cnt));
+  char* pin;
+  MOT_TRY(pinned_scratch(c, 16, &pin));
+  int* h = reinterpret_cast<int*>(pin);
+  MOT_HIP(c, hipMemcpyAsync(h, d_cnt, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  MOT_HIP(c, hipStreamSynchronize(c->stream));
+  const int ns = h[0], np = h[1];
+  if (ns < 0 || ns > kTrackPointKeys || np < 0 || np > c->cap) return fail(c, MOT_E_STATE, who, ": inconsistent counts");
+  *n_segments = ns; *n_points = np;
+  if (np > point_capacity) return fail(c, MOT_E_CAPACITY, "more points than the caller's point buffer holds");
+  if (ns > max_segments) return fail(c, MOT_E_CAPACITY, "more segments than the caller's segment buffer holds");
+  if (points && np > 0) MOT_HIP(c, hipMemcpyAsync(points, d_pts, (size_t)np * sizeof(mot_track_point), hipMemcpyDeviceToHost, c->stream));
+  if (segments && ns > 0) MOT_HIP(c, hipMemcpyAsync(segments, d_seg, (size_t)ns * sizeof(mot_track_segment), hipMemcpyDeviceToHost, c->stream));
+  MOT_HIP(c, hipStreamSynchronize(c->stream));
+  return MOT_OK;
+}
+
 // the track counters of one stream back to zero (stream-ordered: after the steps already queued, before the next one)
 static int clear_tracks(mot_ctx* c, int slot) {
   if (!c) return MOT_E_ARG;

@@ -216,6 +216,17 @@ struct mot_ctx {
   int* d_owner = nullptr;              // [batch][kMaxBoxesPerFrame] box owners of every slot's last tracker step (TrackBuffers::owner)
   int* d_owner_n = nullptr;            // [batch] boxes of that step
   int* d_point_track = nullptr;        // [batch][cap] track id of every elevated point (link.hip)
+  // mot_export_track_points_dev / mot_get_track_points (track_points.hip): allocated at the first call, kept until mot_destroy. Nothing here is read by any other
+  // entry point, and the kernels write nothing else of the context's
+  int* d_tp_seg_id = nullptr;          // [batch][kMaxBoxesPerFrame] distinct owners of every slot's row
+  int* d_tp_seg_boxes = nullptr;       // [batch][kMaxBoxesPerFrame]
+  int* d_tp_seg_n = nullptr;           // [batch]
+  int* d_tp_rows = nullptr;            // [batch][tp_chunks][kTrackPointKeys]
+  int tp_chunks = 0;                   // max_points / kTrackPointChunk rounded up
+  EgoTf* d_tp_tf = nullptr;            // [batch] sensor -> global matrices of the slots of an export (MOT_FRAME_GLOBAL)
+  PinnedRing tp_tf_ring;               // blocks of `batch` matrices
+  char* d_tp_stage = nullptr;          // mot_get_track_points: one slot's records, segments and counts before they go to the host (allocated at ITS first call)
+  std::vector<EgoTf> link_tf;          // [batch] the matrix every slot's boxes took in its last fused call with the tracker, kept while links are on (host side)
   Vec2d* d_cp = nullptr;
   TrackItem* d_items = nullptr;
   int* d_nitems = nullptr;

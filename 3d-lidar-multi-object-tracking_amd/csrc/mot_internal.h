@@ -368,6 +368,30 @@ void mot_launch_export_tracks_packed_sensor(const TrackBuffers& t, int batch, co
 constexpr int kLinkChunk = 2048;                  // points per workgroup
 void mot_launch_point_tracks(const MotDevParams& p, const ClusterBuffers& c, const int* owner, int batch, int max_n, int* ids, long id_stride, int* n_out, hipStream_t stream);
 
+// ---- per-track point clouds (track_points.hip) ---------------------------------------------------
+// The elevated points of frames first .. first + batch - 1, stably partitioned by owning track: the per-point ids above, the input-order cloud and the owner
+// rows in; records and segments (include/mot.h: mot_track_point, mot_track_segment) out, into block k = 0 .. batch - 1 of the caller's buffers. Scratch of the
+// feature's own: the frame's distinct owners and their boxes, and one row of kTrackPointKeys ints per 1024-point chunk (points per key, then where they go).
+constexpr int kTrackPointChunk = 1024;                      // points per workgroup: 16 tiles of 64, four per step
+constexpr int kTrackPointKeys = kMaxBoxesPerFrame + 1;      // a frame's distinct owners, and the rest
+struct TrackPointBuffers {
+  const int* ids;              // [B][cap] track id of every elevated point (link.hip)
+  const float4* elevated;      // [B][cap] the elevated cloud in INPUT order (never the regrouped copy)
+  int elevated_packed;
+  long cap;
+  const int* counts;           // [B][kCountsStride]
+  const int* owner;            // [B][kMaxBoxesPerFrame] the tracker's owner rows
+  int* seg_id;                 // [B][kMaxBoxesPerFrame] the row's distinct ids >= 0, ascending
+  int* seg_boxes;              // [B][kMaxBoxesPerFrame] boxes of the row that carry each
+  int* seg_n;                  // [B] how many
+  int* rows;                   // [B][max_chunks][kTrackPointKeys]
+  int max_chunks;              // cap / kTrackPointChunk rounded up
+};
+// rest != 0: the points without owner form a last segment; tf: null (sensor frame) or the sensor -> global matrix of every frame of the launch ([batch]).
+// points / segs / counts_out: block 0 of the launch (point_stride / max_segments records and 2 ints per frame)
+void mot_launch_track_points(const TrackPointBuffers& t, int first, int batch, int max_n, int rest, const EgoTf* tf, mot_track_point* points, long point_stride,
+                             mot_track_segment* segs, int max_segments, int* counts_out, hipStream_t stream);
+
 #ifdef MOT_HIPEMU
 #define MOT_WAVE_SYNC() ((void)__ballot(1))
 #else

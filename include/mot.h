@@ -422,6 +422,51 @@ int mot_get_point_tracks(mot_ctx* ctx, int slot, int32_t* ids, int capacity, int
  * tells). Same validity rule, for every slot of the batch. */
 int mot_export_point_tracks_dev(mot_ctx* ctx, int batch, int32_t* d_ids, long stride, int32_t* d_counts);
 
+/* ---------------------------------------------------------------- per-track point clouds (additions within ABI v6)
+ * "Which track" turned into "that track's points": the slot's elevated points STABLY PARTITIONED by owning track, on the device — what accumulating an
+ * object's points over frames and cutting dynamic objects out of a map start from (INTEGRATION.md has a recipe for each). For a slot whose point chain is
+ * valid (the rule of mot_get_point_tracks: cloud, boxes and tracker step from ONE fused call, links on).
+ *
+ * SEGMENTS: one per distinct id >= 0 in the step's owner row (mot_get_box_tracks), in ascending id, whether or not a point carries the id; a track that
+ * claimed several boxes gets ONE segment with the points of all its clusters and n_boxes > 1. With MOT_TRACK_POINTS_REST a last segment, track_id -1,
+ * n_boxes 0, holds every point whose id is -1 (no cluster, a cluster not kept as a box, a box nobody owns); the segment is there even when it is empty.
+ * Without the flag those points are left out. Segments lie back to back: first of segment k + 1 = first + count of segment k, the first one starts at 0.
+ * POINTS of a segment keep the elevated cloud's INPUT order (index strictly ascending), also in MOT_ORDER_ANY. index = the point's position in that order:
+ * mot_get_ground's elevated cloud, mot_get_clusters' point_label, mot_get_point_tracks — what a caller fetches intensity, or anything it keeps per point, by.
+ * frame = MOT_FRAME_SENSOR: x, y, z are the elevated point's bits, untouched. MOT_FRAME_GLOBAL: its image under the float 3 x 4 matrix the slot's boxes took
+ * in that fused call — global_from_sensor of mot_sensor_pose read right after the call, applied as that comment states (fp32, left to right, no contraction);
+ * in mot_sequence_dev slot k has frame k's matrix. The library keeps the 48 bytes per slot on the host while links are on and sends them ahead of the
+ * kernels in one stream-ordered copy (page-locked ring: no host synchronisation). Any other frame, or unknown flag bits: MOT_E_ARG.
+ *
+ * mot_export_track_points_dev: slots 0..batch-1 into caller-owned DEVICE blocks, d_points[b * point_stride + i] and d_segments[b * max_segments + k] (4-byte
+ * aligned; a slot that starts on 16 bytes is written one 16-byte store per record), d_counts[2 b] = the slot's segments, d_counts[2 b + 1] = its records — the
+ * TRUE numbers: a slot with more records than point_stride gets the first point_stride, one with more segments than max_segments the first max_segments,
+ * nothing beyond a slot's own records is written. Asynchronous on the context stream, nothing is read back: a frame refused for capacity has no owners here
+ * (as in mot_export_point_tracks_dev) — one rest segment with all its points under MOT_TRACK_POINTS_REST, nothing otherwise. MOT_E_STATE under exactly the
+ * conditions of mot_export_point_tracks_dev, tested for every slot of the batch before anything is launched.
+ * mot_get_track_points: one slot to the host (synchronises). *n_points / *n_segments are always delivered; MOT_E_CAPACITY with nothing copied when either
+ * buffer is too small, and with the limit's message on a refused frame. MOT_E_STATE as mot_get_point_tracks.
+ *
+ * Four kernels per call (csrc/track_points.hip), none in any other call: 36 bytes moved per elevated point plus 12 bytes per (1024-point chunk, segment)
+ * against the 32 of a plain copy into such records. Scratch, allocated at the first call and kept until mot_destroy (MOT_E_HIP if that fails; the next call
+ * resumes): per slot 4100 bytes per 1024 points of max_points (rounded up) + 8 KB + 52 bytes, and 768 bytes x max_batch page-locked; mot_get_track_points adds one
+ * block of 16 bytes x max_points + 17 KB per context at ITS first call. Cost (profiles/track_points.md; 512 streams x 120 k points per call): 202 - 266 us, 1.6 - 2.1 x a device-to-device copy of the same bytes. */
+enum { MOT_TRACK_POINTS_REST = 1 };            /* flags */
+typedef struct mot_track_segment {             /* 16 bytes */
+  int32_t track_id;   /* mot_track.id; -1: the rest segment */
+  int32_t first;      /* index of the segment's first record in the slot's point block */
+  int32_t count;      /* its records */
+  int32_t n_boxes;    /* boxes of the step's owner row that carry this id (0 for the rest segment) */
+} mot_track_segment;
+typedef struct mot_track_point { float x, y, z; int32_t index; } mot_track_point;   /* 16 bytes */
+int mot_export_track_points_dev(mot_ctx* ctx, int batch, int flags, int frame,
+        mot_track_point* d_points, long point_stride,          /* records per slot */
+        mot_track_segment* d_segments, int max_segments,       /* records per slot */
+        int32_t* d_counts /* [batch][2]: segments, points - the TRUE numbers */);
+int mot_get_track_points(mot_ctx* ctx, int slot, int flags, int frame,
+        mot_track_point* points, int point_capacity, mot_track_segment* segments, int max_segments,
+        int* n_points, int* n_segments);
+
 /* on != 0: the fused entry points send their launch sequence (13 kernels with the tracker) as ONE hipGraph launch, captured once per launch geometry
  * (batch, chunks of the largest frame, tracker on / off, outputs); what changes per call without changing the geometry travels in the
  * device-resident argument block. For contexts somebody waits on frame by frame (one or a few streams): the host's part of a frame
