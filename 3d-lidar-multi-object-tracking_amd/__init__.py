@@ -80,6 +80,17 @@ assert C.sizeof(MotTrackSegment) == 16 and C.sizeof(MotTrackPoint) == 16
 # the same two records as numpy dtypes
 TRACK_SEGMENT_DTYPE = np.dtype([("track_id", "i4"), ("first", "i4"), ("count", "i4"), ("n_boxes", "i4")])
 TRACK_POINT_DTYPE = np.dtype([("xyz", "f4", 3), ("index", "i4")])
+# struct mot_accum_row / mot_accum_point / mot_accum_obs (per-track accumulators, include/mot.h)
+ACCUM_ROW_DTYPE = np.dtype([("track_id", "i4"), ("first_step", "i4"), ("last_step", "i4"), ("obs_total", "i4"), ("total", "u8"), ("reserved", "u8")])
+ACCUM_POINT_DTYPE = np.dtype([("xyz", "f4", 3), ("step", "i4")])
+ACCUM_OBS_DTYPE = np.dtype([("step", "i4"), ("count", "i4"), ("n_boxes", "i4"), ("track_manage", "i4"), ("px", "f4"), ("py", "f4"), ("is_static", "i4"), ("lifetime", "i4"),
+                            ("v", "f8"), ("yaw", "f8")])
+
+
+class MotAccumView(C.Structure):
+    """mirror of struct mot_accum_view (include/mot.h)"""
+    _fields_ = [("d_rows", C.c_void_p), ("d_points", C.c_void_p), ("d_obs", C.c_void_p), ("tracks_per_slot", C.c_int32), ("points_per_track", C.c_int32),
+                ("obs_per_track", C.c_int32), ("max_batch", C.c_int32)]
 
 
 class MotError(RuntimeError):
@@ -100,6 +111,7 @@ EXPORTS = (
     "mot_sensor_pose", "mot_export_tracks_frame_dev", "mot_export_tracks_packed_frame_dev", "mot_fetch_tracks_frame_async", "mot_tracking_node_frame",
     "mot_set_track_links", "mot_get_box_tracks", "mot_get_point_tracks", "mot_export_point_tracks_dev",
     "mot_export_track_points_dev", "mot_get_track_points",
+    "mot_set_track_accumulation", "mot_accumulate_track_points", "mot_track_accumulators_dev", "mot_get_accum_rows", "mot_get_track_accumulated",
     "mot_gather_unique_id", "mot_gather_create", "mot_gather_contribute", "mot_gather_result", "mot_gather_synchronize", "mot_gather_destroy", "mot_gather_last_error",
 )
 ABI_VERSION = 6
@@ -306,6 +318,39 @@ class Context:
         numbers of segments and records in d_counts[2 b], d_counts[2 b + 1] (asynchronous)"""
         self._ck(self.lib.mot_export_track_points_dev(self._h, batch, MOT_TRACK_POINTS_REST if rest else 0, _frame(frame), C.c_void_p(d_points_ptr), C.c_long(point_stride),
                                                       C.c_void_p(d_segments_ptr), int(max_segments), C.c_void_p(d_counts_ptr)))
+
+    def set_track_accumulation(self, points_per_track: int, obs_per_track: int = 0):
+        """per-track accumulators (mot_set_track_accumulation): a ring of points_per_track points (a power of two in [64, 2^20]; 0: off) and of obs_per_track
+        observations (0 or a power of two up to 4096) per track slot of every stream; needs set_track_links"""
+        self._ck(self.lib.mot_set_track_accumulation(self._h, int(points_per_track), int(obs_per_track)))
+
+    def accumulate_track_points(self, batch: int):
+        """append the latest fused step of slots 0..batch-1 to the tracks' accumulators (asynchronous; once per step)"""
+        self._ck(self.lib.mot_accumulate_track_points(self._h, int(batch)))
+
+    def track_accumulators_dev(self) -> dict:
+        """the accumulators' device pointers and geometry (mot_track_accumulators_dev): d_rows, d_points, d_obs (0 when obs_per_track is 0), tracks_per_slot,
+        points_per_track, obs_per_track, max_batch"""
+        v = MotAccumView()
+        self._ck(self.lib.mot_track_accumulators_dev(self._h, C.byref(v)))
+        return dict(d_rows=v.d_rows or 0, d_points=v.d_points or 0, d_obs=v.d_obs or 0, tracks_per_slot=v.tracks_per_slot, points_per_track=v.points_per_track,
+                    obs_per_track=v.obs_per_track, max_batch=v.max_batch)
+
+    def get_accum_rows(self, slot: int = 0) -> np.ndarray:
+        """the slot's accumulator rows, one per track slot (ACCUM_ROW_DTYPE; track_id -1: empty)"""
+        rows = np.zeros(self.max_tracks_total, ACCUM_ROW_DTYPE); n = C.c_int(0)
+        self._ck(self.lib.mot_get_accum_rows(self._h, slot, _vp(rows), len(rows), C.byref(n)))
+        return rows[: n.value]
+
+    def get_track_accumulated(self, slot: int, track_id: int) -> dict:
+        """what the slot's accumulator holds of one track, oldest first (mot_get_track_accumulated): row (an ACCUM_ROW_DTYPE record), xyz [n, 3] (global frame),
+        step [n], obs (ACCUM_OBS_DTYPE records)"""
+        v = self.track_accumulators_dev()
+        row = np.zeros(1, ACCUM_ROW_DTYPE); pts = np.zeros(v["points_per_track"], ACCUM_POINT_DTYPE); obs = np.zeros(max(v["obs_per_track"], 1), ACCUM_OBS_DTYPE)
+        npts, nobs = C.c_int(0), C.c_int(0)
+        self._ck(self.lib.mot_get_track_accumulated(self._h, slot, int(track_id), _vp(row), _vp(pts), len(pts), C.byref(npts), _vp(obs), len(obs), C.byref(nobs)))
+        pts = pts[: npts.value]
+        return dict(row=row[0].copy(), xyz=pts["xyz"].copy(), step=pts["step"].copy(), obs=obs[: nobs.value].copy())
 
     def _track_buffer(self, slot, max_tracks):
         """records a call can deliver: one per track EVER created on the stream, which outgrows the number of slots on a long run"""

@@ -437,6 +437,7 @@ extern "C" int mot_reset(mot_ctx* c) {
   MOT_HIP(c, hipMemsetAsync(c->d_nt, 0, c->batch * sizeof(int), c->stream));
   MOT_HIP(c, hipMemsetAsync(c->d_nlive, 0, c->batch * sizeof(int), c->stream));
   MOT_HIP(c, hipMemsetAsync(c->d_tflags, 0, c->batch * sizeof(int), c->stream));
+  MOT_TRY(accum_restart_slots(c, 0, c->batch));
   c->ego.assign(c->batch, mot_ctx::SlotEgo());
   return MOT_OK;
 }
@@ -698,7 +699,7 @@ extern "C" int mot_sequence_dev(mot_ctx* c, const float* d_xyzw, long frame_stri
   MOT_TRY(next_epoch(c));
   const int K = frames, max_n = c->res.last_max_n;
   MOT_TRY(send_frame_args(c, K, 1, true, timestamps, ego_v, ego_yaw));   // one argument block for the whole sequence
-  c->res.fused_batch(K, c->fused_outputs, c->point_order == MOT_ORDER_ANY, c->track_links != 0);   // (links: row k / the ids of slot k = frame k)
+  c->res.fused_batch(K, c->fused_outputs, c->point_order == MOT_ORDER_ANY, c->track_links != 0, true);   // (links: row k / the ids of slot k = frame k)
   issue_frame_kernels(c, K, max_n, 0, false);   // slots = frames; ends with the plain box_finalize_kernel
   const TrackBuffers base = track_buffers(c, true);
   RangeScope rt(c, "mot:tracker (sequence)");
@@ -924,6 +925,7 @@ extern "C" int mot_set_track_links(mot_ctx* c, int on) {
   MOT_GUARD(c);
   on = on ? 1 : 0;
   if (on == c->track_links) return MOT_OK;
+  if (!on && c->accum_K) return fail(c, MOT_E_STATE, "mot_set_track_links: the per-track accumulators are on (mot_set_track_accumulation(ctx, 0, 0) first)");
   if (on) MOT_TRY(ensure_links(c));   // MOT_E_HIP: the mode stays as it was
   MOT_TRY(drop_graphs(c));   // the link kernel and the owner pointers are part of the launch sequence: graphs captured in the other mode go
   c->track_links = on;

@@ -1,5 +1,5 @@
 // mot_api_tracks.hip — host side of the C-ABI (include/mot.h), everything about tracks: the tf chain's matrices, ego dead reckoning, the tracker step and its getters, the box /
-// point links' getters, stream resets and snapshots, the exports (global and sensor frame) and the tracking node's callback. Context and helpers: mot_host.h.
+// point links' getters, the per-track point clouds and accumulators, stream resets and snapshots, the exports (global and sensor frame) and the tracking node's callback. Context and helpers: mot_host.h.
 #include "mot_host.h"
 
 // The sensor -> global change of frame the tracking node asks tf for (OT/tracking/main.cpp:76-83 broadcast, :143-158
@@ -317,8 +317,8 @@ static int ensure_track_points(mot_ctx* c, bool host_stage) {
   MOT_TRY(dev_alloc(c, &c->d_tp_seg_boxes, B * kMaxBoxesPerFrame * sizeof(int)));
   MOT_TRY(dev_alloc(c, &c->d_tp_seg_n, B * sizeof(int)));
   MOT_TRY(dev_alloc(c, &c->d_tp_rows, B * (size_t)c->tp_chunks * kTrackPointKeys * sizeof(int)));
-  MOT_TRY(dev_alloc(c, &c->d_tp_tf, B * sizeof(EgoTf)));
-  MOT_TRY(c->tp_tf_ring.create(c, B * sizeof(EgoTf)));
+  MOT_TRY(dev_alloc(c, &c->d_tp_tf, B * (sizeof(EgoTf) + sizeof(int))));   // (the matrices, and behind them the step stamps of mot_accumulate_track_points)
+  MOT_TRY(c->tp_tf_ring.create(c, B * (sizeof(EgoTf) + sizeof(int))));
   if (host_stage) MOT_TRY(dev_alloc(c, &c->d_tp_stage, (size_t)c->cap * sizeof(mot_track_point) + (size_t)kTrackPointKeys * sizeof(mot_track_segment) + 16));
   return MOT_OK;
 }
@@ -398,6 +398,165 @@ extern "C" int mot_get_track_points(mot_ctx* c, int slot, int flags, int frame, 
   return MOT_OK;
 }
 
+// ---------------------------------------------------------------------------------------- per-track accumulators (track_accum.hip)
+// The setter owns the feature's memory: rows, the two rings and the plan are allocated together and released together (off, or another geometry). The scratch
+// the kernels share with the per-track point clouds (distinct owners, per-chunk rows, matrices + step stamps) is ensure_track_points', at the first accumulate call.
+static bool pow2_in(int v, int lo, int hi) { return v >= lo && v <= hi && (v & (v - 1)) == 0; }
+static int accum_release(mot_ctx* c, mot_accum_row** rows, mot_accum_point** points, mot_accum_obs** obs, TrackAccumPlan** plan) {
+  MOT_TRY(release(c, rows)); MOT_TRY(release(c, points)); MOT_TRY(release(c, obs));
+  return release(c, plan);
+}
+int accum_restart_slots(mot_ctx* c, int first, int n) {
+  if (!c->accum_K) return MOT_OK;
+  mot_launch_track_accum_clear(c->d_ta_rows, (long)first * c->max_tracks_total, (long)n * c->max_tracks_total, c->stream);
+  MOT_HIP(c, hipGetLastError());
+  for (int b = first; b < first + n; b++) { c->accum_step[b] = 0; c->res.step_accumulated(b); }
+  return MOT_OK;
+}
+extern "C" int mot_set_track_accumulation(mot_ctx* c, int points_per_track, int obs_per_track) {
+  if (!c) return MOT_E_ARG;
+  MOT_GUARD(c);
+  const char* who = "mot_set_track_accumulation";
+  const int K = points_per_track, O = obs_per_track;
+  if (K == 0) {   // off: nothing may still read the tables
+    if (!c->accum_K) return MOT_OK;
+    MOT_HIP(c, hipStreamSynchronize(c->stream));
+    c->accum_K = c->accum_O = 0;
+    return accum_release(c, &c->d_ta_rows, &c->d_ta_points, &c->d_ta_obs, &c->d_ta_plan);
+  }
+  if (!pow2_in(K, 64, 1 << 20)) return fail(c, MOT_E_ARG, who, ": points_per_track must be 0 (off) or a power of two in [64, 2^20]");
+  if (O != 0 && !pow2_in(O, 1, 4096)) return fail(c, MOT_E_ARG, who, ": obs_per_track must be 0 or a power of two in [1, 4096]");
+  if (!c->track_links) return fail(c, MOT_E_STATE, who, ": track links are off (mot_set_track_links)");
+  if (K == c->accum_K && O == c->accum_O) return MOT_OK;
+  // the new tables first: a failure leaves the mode, an earlier geometry included, as it was
+  const size_t rows_n = (size_t)c->batch * c->max_tracks_total;
+  mot_accum_row* d_accum_rows = nullptr; mot_accum_point* d_accum_points = nullptr; mot_accum_obs* d_accum_obs = nullptr; TrackAccumPlan* d_accum_plan = nullptr;
+  int rc = dev_alloc(c, &d_accum_rows, rows_n * sizeof(mot_accum_row));
+  if (!rc) rc = dev_alloc(c, &d_accum_points, rows_n * (size_t)K * sizeof(mot_accum_point));
+  if (!rc && O) rc = dev_alloc(c, &d_accum_obs, rows_n * (size_t)O * sizeof(mot_accum_obs));
+  if (!rc) rc = dev_alloc(c, &d_accum_plan, (size_t)c->batch * kMaxBoxesPerFrame * sizeof(TrackAccumPlan));
+  if (rc) {
+    const std::string why = c->err;
+    (void)accum_release(c, &d_accum_rows, &d_accum_points, &d_accum_obs, &d_accum_plan);
+    c->err = why;
+    return rc;
+  }
+  if (c->accum_K) {
+    MOT_HIP(c, hipStreamSynchronize(c->stream));
+    MOT_TRY(accum_release(c, &c->d_ta_rows, &c->d_ta_points, &c->d_ta_obs, &c->d_ta_plan));
+  }
+  c->d_ta_rows = d_accum_rows; c->d_ta_points = d_accum_points; c->d_ta_obs = d_accum_obs; c->d_ta_plan = d_accum_plan;
+  c->accum_K = K; c->accum_O = O;
+  c->accum_step.assign(c->batch, 0);
+  return accum_restart_slots(c, 0, c->batch);   // every row empty; the steps the slots hold were taken without the feature: the next fused call is the first to append
+}
+
+static int check_accum_on(mot_ctx* c, const char* who) { return c->accum_K ? MOT_OK : fail(c, MOT_E_STATE, who, ": the per-track accumulators are off (mot_set_track_accumulation)"); }
+
+extern "C" int mot_accumulate_track_points(mot_ctx* c, int batch) {
+  if (!c) return MOT_E_ARG;
+  MOT_GUARD(c);
+  const char* who = "mot_accumulate_track_points";
+  MOT_TRY(check_accum_on(c, who));
+  if (batch < 1 || batch > c->batch) return fail(c, MOT_E_ARG, who, ": batch out of range");
+  for (int b = 0; b < batch; b++) {   // every slot before anything is launched or counted
+    MOT_TRY(check_point_tracks(c, b, who));
+    if (c->res.sequence_frame(b)) return fail(c, MOT_E_STATE, who, ": the slots hold the frames of ONE stream (mot_sequence_dev); the accumulators do not support sequence mode");
+    if (c->res.accumulated(b)) return fail(c, MOT_E_STATE, who, ": a slot of the batch was already accumulated for its current step, or was reset / loaded since that step");
+  }
+  MOT_TRY(ensure_track_points(c, false));
+  // the matrices the slots' boxes took and the slots' step stamps, in one stream-ordered copy ahead of the kernels
+  char* raw;
+  MOT_TRY(c->tp_tf_ring.acquire(c, &raw));
+  memcpy(raw, c->link_tf.data(), (size_t)batch * sizeof(EgoTf));
+  memcpy(raw + (size_t)batch * sizeof(EgoTf), c->accum_step.data(), (size_t)batch * sizeof(int));
+  MOT_TRY(c->tp_tf_ring.commit(c, c->d_tp_tf, 0, (size_t)batch * (sizeof(EgoTf) + sizeof(int)), c->stream));
+  TrackPointBuffers t;
+  t.ids = c->d_point_track; t.elevated = c->d_elev; t.cap = c->cap; t.counts = c->d_counts; t.owner = c->d_owner;
+  t.seg_id = c->d_tp_seg_id; t.seg_boxes = c->d_tp_seg_boxes; t.seg_n = c->d_tp_seg_n; t.rows = c->d_tp_rows; t.max_chunks = c->tp_chunks;
+  TrackAccumBuffers a;
+  a.rows = c->d_ta_rows; a.points = c->d_ta_points; a.obs = c->d_ta_obs; a.plan = c->d_ta_plan; a.slot_of = c->d_slot_of; a.out = c->d_tout;
+  a.T = c->max_tracks_total; a.E = c->max_tracks_ever; a.K = c->accum_K; a.O = c->accum_O;
+  const int* d_steps = reinterpret_cast<const int*>(c->d_tp_tf + batch);
+  for (int k0 = 0; k0 < batch;) {   // one launch per run of slots of one cloud layout (launch_track_points)
+    int k1 = k0 + 1;
+    while (k1 < batch && c->res.elev_packed_at(k1) == c->res.elev_packed_at(k0)) k1++;
+    t.elevated_packed = c->res.elev_packed_at(k0) ? 1 : 0;
+    a.steps = d_steps + k0;
+    mot_launch_track_accum(t, a, k0, k1 - k0, c->max_points, c->d_tp_tf + k0, c->stream);
+    k0 = k1;
+  }
+  MOT_HIP(c, hipGetLastError());
+  for (int b = 0; b < batch; b++) { c->accum_step[b]++; c->res.step_accumulated(b); }
+  return MOT_OK;
+}
+
+extern "C" int mot_track_accumulators_dev(mot_ctx* c, mot_accum_view* out) {
+  if (!c) return MOT_E_ARG;
+  if (!out) return fail(c, MOT_E_ARG, "mot_track_accumulators_dev: null result");
+  MOT_TRY(check_accum_on(c, "mot_track_accumulators_dev"));
+  out->d_rows = c->d_ta_rows; out->d_points = c->d_ta_points; out->d_obs = c->d_ta_obs;
+  out->tracks_per_slot = c->max_tracks_total; out->points_per_track = c->accum_K; out->obs_per_track = c->accum_O; out->max_batch = c->batch;
+  return MOT_OK;
+}
+
+extern "C" int mot_get_accum_rows(mot_ctx* c, int slot, mot_accum_row* rows, int max_rows, int* n_rows) {
+  if (!c) return MOT_E_ARG;
+  MOT_GUARD(c);
+  const char* who = "mot_get_accum_rows";
+  if (slot < 0 || slot >= c->batch || max_rows < 0 || !n_rows) return fail(c, MOT_E_ARG, who, ": slot or max_rows out of range, or null n_rows");
+  MOT_TRY(check_accum_on(c, who));
+  const int T = c->max_tracks_total;
+  *n_rows = T;
+  if (T > max_rows) return fail(c, MOT_E_CAPACITY, "more rows (max_tracks_total) than the caller's buffer holds");
+  if (rows) {
+    MOT_HIP(c, hipMemcpyAsync(rows, c->d_ta_rows + (size_t)slot * T, (size_t)T * sizeof(mot_accum_row), hipMemcpyDeviceToHost, c->stream));
+    MOT_HIP(c, hipStreamSynchronize(c->stream));
+  }
+  return MOT_OK;
+}
+
+extern "C" int mot_get_track_accumulated(mot_ctx* c, int slot, int track_id, mot_accum_row* row, mot_accum_point* points, int point_capacity, int* n_points,
+                                         mot_accum_obs* obs, int obs_capacity, int* n_obs) {
+  if (!c) return MOT_E_ARG;
+  MOT_GUARD(c);
+  const char* who = "mot_get_track_accumulated";
+  if (slot < 0 || slot >= c->batch || track_id < 0 || point_capacity < 0 || obs_capacity < 0 || !n_points || !n_obs)
+    return fail(c, MOT_E_ARG, who, ": slot, track_id or a capacity out of range, or a null count");
+  MOT_TRY(check_accum_on(c, who));
+  const size_t T = c->max_tracks_total, K = c->accum_K, O = c->accum_O;
+  char* pin;
+  MOT_TRY(pinned_scratch(c, T * sizeof(mot_accum_row), &pin));
+  MOT_HIP(c, hipMemcpyAsync(pin, c->d_ta_rows + (size_t)slot * T, T * sizeof(mot_accum_row), hipMemcpyDeviceToHost, c->stream));
+  MOT_HIP(c, hipStreamSynchronize(c->stream));
+  const mot_accum_row* rows = reinterpret_cast<const mot_accum_row*>(pin);
+  size_t r = 0;
+  while (r < T && rows[r].track_id != track_id) r++;
+  if (r == T) return fail(c, MOT_E_STATE, who, ": no accumulator holds this track (never accumulated, or its track slot went to another track)");
+  const mot_accum_row found = rows[r];
+  const size_t np = found.total < K ? (size_t)found.total : K, no = O ? ((size_t)found.obs_total < O ? (size_t)found.obs_total : O) : 0;
+  *n_points = (int)np; *n_obs = (int)no;
+  if (points && np > (size_t)point_capacity) return fail(c, MOT_E_CAPACITY, "more accumulated points than the caller's point buffer holds");
+  if (obs && no > (size_t)obs_capacity) return fail(c, MOT_E_CAPACITY, "more observations than the caller's observation buffer holds");
+  if (row) *row = found;
+  // the ring unrolled, oldest first: [oldest, kept) then [0, oldest)
+  const size_t at = (size_t)slot * T + r;
+  if (points && np) {
+    const size_t oldest = found.total > K ? (size_t)(found.total & (K - 1)) : 0;
+    const mot_accum_point* ring = c->d_ta_points + at * K;
+    MOT_HIP(c, hipMemcpyAsync(points, ring + oldest, (np - oldest) * sizeof(mot_accum_point), hipMemcpyDeviceToHost, c->stream));
+    if (oldest) MOT_HIP(c, hipMemcpyAsync(points + (np - oldest), ring, oldest * sizeof(mot_accum_point), hipMemcpyDeviceToHost, c->stream));
+  }
+  if (obs && no) {
+    const size_t oldest = (size_t)found.obs_total > O ? ((size_t)found.obs_total & (O - 1)) : 0;
+    const mot_accum_obs* ring = c->d_ta_obs + at * O;
+    MOT_HIP(c, hipMemcpyAsync(obs, ring + oldest, (no - oldest) * sizeof(mot_accum_obs), hipMemcpyDeviceToHost, c->stream));
+    if (oldest) MOT_HIP(c, hipMemcpyAsync(obs + (no - oldest), ring, oldest * sizeof(mot_accum_obs), hipMemcpyDeviceToHost, c->stream));
+  }
+  MOT_HIP(c, hipStreamSynchronize(c->stream));
+  return MOT_OK;
+}
+
 // the track counters of one stream back to zero (stream-ordered: after the steps already queued, before the next one)
 static int clear_tracks(mot_ctx* c, int slot) {
   if (!c) return MOT_E_ARG;
@@ -406,7 +565,7 @@ static int clear_tracks(mot_ctx* c, int slot) {
   MOT_HIP(c, hipMemsetAsync(c->d_nt + slot, 0, sizeof(int), c->stream));
   MOT_HIP(c, hipMemsetAsync(c->d_nlive + slot, 0, sizeof(int), c->stream));
   MOT_HIP(c, hipMemsetAsync(c->d_tflags + slot, 0, sizeof(int), c->stream));
-  return MOT_OK;
+  return accum_restart_slots(c, slot, 1);
 }
 // forget the TRACKS of one stream, keep its ego dead reckoning (the origin of its global frame)
 extern "C" int mot_reset_tracks_slot(mot_ctx* c, int slot) {
@@ -582,7 +741,7 @@ extern "C" int mot_stream_load(mot_ctx* c, int slot, const void* blob, size_t by
   e.step_ego_yaw = h.step_ego_yaw;
   e.nt = h.nt;
   c->ego[slot] = e;
-  return MOT_OK;
+  return accum_restart_slots(c, slot, 1);   // (the accumulators are not stream state: the loaded stream's ids start with empty rows)
 }
 
 // immUkfJpdaf(), OT/tracking/imm_ukf_jpda.cpp:704

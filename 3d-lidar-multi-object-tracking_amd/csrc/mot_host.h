@@ -48,6 +48,8 @@ struct SlotState {
   bool regrouped = false;                 // the box stage ran in MOT_ORDER_ANY: its products (groups, cluster order, first / extreme point indices) index the slot's
                                           // cluster-ordered COPY of the cloud, not the cloud itself. Meaningful while `boxes`; every reader that walks clusters asks.
   LinkState links = kLinksNone;
+  bool sequence = false;                  // the slot holds FRAME k of one stream (mot_sequence_dev), not stream k's frame: the per-track accumulators refuse it
+  bool accumulated = false;               // mot_accumulate_track_points has appended the step the slot holds (or a reset / load has put it out of reach): not again
 };
 struct Residency {
   std::vector<SlotState> slots;
@@ -61,11 +63,12 @@ struct Residency {
   // a fused call over slots 0..batch-1 was issued: what those slots hold from now on (the slots beyond keep what an earlier, larger batch left). Host
   // state, so it also holds when a captured graph is replayed: every reader built from cluster_buffers afterwards is told the layout
   // linked: the call runs the tracker with mot_set_track_links on
-  void fused_batch(int batch, int outputs, bool regrouped, bool linked) {
+  // one_stream: mot_sequence_dev. Every fused call gives the slot a new step: `accumulated` starts over
+  void fused_batch(int batch, int outputs, bool regrouped, bool linked, bool one_stream = false) {
     last_fused = true;
     for (int b = 0; b < batch; b++)
       slots[b] = {fused_packs(outputs), (outputs & MOT_OUT_LABELS) ? kLabelsReady : kLabelsFromCells, true, fused_keeps_ground(outputs) ? kGroundResident : kGroundNone, regrouped,
-                  linked ? kLinksPoints : unlinked(slots[b].links)};
+                  linked ? kLinksPoints : unlinked(slots[b].links), one_stream, false};
   }
   static LinkState unlinked(LinkState l) { return l == kLinksPoints ? kLinksBoxes : l; }   // the slot's cloud or boxes are being replaced: its owner row stays the last tracker step's
   // a stage-wise ground stage ran on slot 0 (float4 records); without a mask a later mot_get_ground that asks for one answers MOT_E_STATE
@@ -87,6 +90,9 @@ struct Residency {
   void links_switched() { for (auto& s : slots) s.links = kLinksNone; }
   bool box_tracks_valid(int slot) const { return slots[slot].links != kLinksNone; }
   bool point_tracks_valid(int slot) const { return slots[slot].links == kLinksPoints; }
+  bool sequence_frame(int slot) const { return slots[slot].sequence; }
+  bool accumulated(int slot) const { return slots[slot].accumulated; }
+  void step_accumulated(int slot) { slots[slot].accumulated = true; }   // (also: the slot's stream was reset or loaded — the step it holds belongs to ids that are gone)
   bool elev_packed_at(int slot) const { return slots[slot].packed; }
   bool labels_ready(int slot) const { return slots[slot].labels == kLabelsReady; }
   bool cells_usable(int slot) const { return slots[slot].labels == kLabelsFromCells; }
@@ -216,16 +222,24 @@ struct mot_ctx {
   int* d_owner = nullptr;              // [batch][kMaxBoxesPerFrame] box owners of every slot's last tracker step (TrackBuffers::owner)
   int* d_owner_n = nullptr;            // [batch] boxes of that step
   int* d_point_track = nullptr;        // [batch][cap] track id of every elevated point (link.hip)
-  // mot_export_track_points_dev / mot_get_track_points (track_points.hip): allocated at the first call, kept until mot_destroy. Nothing here is read by any other
-  // entry point, and the kernels write nothing else of the context's
+  // mot_export_track_points_dev / mot_get_track_points (track_points.hip): allocated at the first call, kept until mot_destroy. Only mot_accumulate_track_points shares it
+  // (same kernels, same meaning); no other entry point reads it, and the kernels write nothing else of the context's
   int* d_tp_seg_id = nullptr;          // [batch][kMaxBoxesPerFrame] distinct owners of every slot's row
   int* d_tp_seg_boxes = nullptr;       // [batch][kMaxBoxesPerFrame]
   int* d_tp_seg_n = nullptr;           // [batch]
   int* d_tp_rows = nullptr;            // [batch][tp_chunks][kTrackPointKeys]
   int tp_chunks = 0;                   // max_points / kTrackPointChunk rounded up
-  EgoTf* d_tp_tf = nullptr;            // [batch] sensor -> global matrices of the slots of an export (MOT_FRAME_GLOBAL)
-  PinnedRing tp_tf_ring;               // blocks of `batch` matrices
+  EgoTf* d_tp_tf = nullptr;            // [batch] sensor -> global matrices of the slots of an export (MOT_FRAME_GLOBAL), then [batch] ints: the step stamps of an accumulate call
+  PinnedRing tp_tf_ring;               // blocks of `batch` matrices and `batch` ints
   char* d_tp_stage = nullptr;          // mot_get_track_points: one slot's records, segments and counts before they go to the host (allocated at ITS first call)
+  // mot_set_track_accumulation (track_accum.hip): allocated by the setter, released when it turns the feature off or changes its geometry. The scratch of the
+  // per-track point clouds above is shared (distinct owners, per-chunk rows, matrices); the plan is the feature's own
+  int accum_K = 0, accum_O = 0;        // points / observations per track; K == 0: off
+  mot_accum_row* d_ta_rows = nullptr;      // [batch][max_tracks_total]
+  mot_accum_point* d_ta_points = nullptr;  // [batch][max_tracks_total][K]
+  mot_accum_obs* d_ta_obs = nullptr;       // [batch][max_tracks_total][O], null when O == 0
+  TrackAccumPlan* d_ta_plan = nullptr;     // [batch][kMaxBoxesPerFrame]
+  std::vector<int> accum_step;             // [batch] accepted accumulate calls that covered the slot (the next step stamp)
   std::vector<EgoTf> link_tf;          // [batch] the matrix every slot's boxes took in its last fused call with the tracker, kept while links are on (host side)
   Vec2d* d_cp = nullptr;
   TrackItem* d_items = nullptr;
@@ -370,6 +384,7 @@ void tf_velodyne_to_global(double x, double y, double yaw, float m[12]);
 TrackBuffers track_buffers(mot_ctx* c, bool fused);
 void prepare_track_args(mot_ctx* c, TrackFrameArgs* targs, int slot, int m, double timestamp, bool run);
 int pinned_scratch(mot_ctx* c, size_t bytes, char** out);
+int accum_restart_slots(mot_ctx* c, int first, int n);   // the accumulators of those streams back to empty, stream-ordered (nothing while the feature is off)
 // head of a packed live-track block: one count per slot, padded to 16 bytes; the records follow (mot_export_tracks_packed_dev, mot_gather)
 inline long mot_packed_head_bytes(int batch) { return ((long)batch * 4 + 15) & ~15l; }
 #endif  // MOT_HOST_H_

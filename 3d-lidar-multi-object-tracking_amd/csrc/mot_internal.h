@@ -392,6 +392,24 @@ struct TrackPointBuffers {
 void mot_launch_track_points(const TrackPointBuffers& t, int first, int batch, int max_n, int rest, const EgoTf* tf, mot_track_point* points, long point_stride,
                              mot_track_segment* segs, int max_segments, int* counts_out, hipStream_t stream);
 
+// Per-track accumulators (track_accum.hip, mot_set_track_accumulation): one row, one ring of K points and one ring of O observations per TRACK SLOT of a stream —
+// the tracker's own bounded set of objects alive at once (TrackBuffers::slot_of, ::out), eviction included. K and O are powers of two (O may be 0).
+struct TrackAccumPlan { int row, at; };   // per segment of a step: the row it appends to (-1: none) and the ring position of its first KEPT point
+struct TrackAccumBuffers {
+  mot_accum_row* rows;         // [B][T]
+  mot_accum_point* points;     // [B][T][K]
+  mot_accum_obs* obs;          // [B][T][O], null when O == 0
+  TrackAccumPlan* plan;        // [B][kMaxBoxesPerFrame] scratch between the two kernels
+  const int* slot_of;          // [B][E] TrackBuffers::slot_of
+  const mot_track* out;        // [B][T] TrackBuffers::out
+  const int* steps;            // [batch] of the launch: every frame's step stamp
+  int T, E, K, O;
+};
+// appends the step of slots first .. first + batch - 1 (t.seg_* and t.rows hold what mot_launch_track_point_counts left); tf: every frame's sensor -> global matrix
+void mot_launch_track_accum(const TrackPointBuffers& t, const TrackAccumBuffers& a, int first, int batch, int max_n, const EgoTf* tf, hipStream_t stream);
+// rows [first, first + n) of the context's row table back to empty
+void mot_launch_track_accum_clear(mot_accum_row* rows, long first, long n, hipStream_t stream);
+
 #ifdef MOT_HIPEMU
 #define MOT_WAVE_SYNC() ((void)__ballot(1))
 #else

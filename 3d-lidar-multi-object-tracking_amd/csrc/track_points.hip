@@ -20,36 +20,7 @@
 // touched, in LDS and in memory.
 // Bytes per elevated point: P1 4 read (id); P3 4 (id) + 12 (point) read, 16 written: 20 read + 16 written = 36, plus 3 x 4 (keys + 1) bytes per 1024-point
 // chunk for the rows (about 0.5 bytes a point at 40 tracks, 12 at the limit of 1024). A plain copy of ids and points into such records moves 32.
-#include "mot_internal.h"
-#include "mot_wave.h"
-
-#ifndef MOT_HIPEMU
-#define MOT_TP_BOUNDS(n) __launch_bounds__(n)
-#else
-#define MOT_TP_BOUNDS(n)
-#endif
-
-constexpr int kTpBlock = 256, kTpItems = kTrackPointChunk / kTpBlock;
-constexpr int kTpTiles = kTrackPointChunk / 64;
-static_assert(kTrackPointChunk % kTpBlock == 0 && kTpItems * (kTpBlock / 64) == kTpTiles, "a wave takes one 64-point tile per item");
-static_assert(sizeof(mot_track_point) == 16 && sizeof(mot_track_segment) == 16, "one 16-byte store per record");
-
-// the frame's elevated points and boxes as every kernel here sees them (never beyond the slot: the counts are the device's)
-__device__ __forceinline__ int tp_count(const TrackPointBuffers& t, int b) {
-  const int n = t.counts[b * kCountsStride + kCntElev];
-  return n < 0 ? 0 : (n < (int)t.cap ? n : (int)t.cap);
-}
-__device__ __forceinline__ int tp_segments(const TrackPointBuffers& t, int b) {
-  const int r = t.seg_n[b];
-  return r < 0 ? 0 : (r < kMaxBoxesPerFrame ? r : kMaxBoxesPerFrame);
-}
-// rank of `id` among the frame's R distinct owners (ascending in s_ids); R for a point without owner
-__device__ __forceinline__ int tp_key(int id, const int* s_ids, int R) {
-  if (id < 0) return R;
-  int lo = 0, hi = R;
-  while (lo < hi) { const int mid = (lo + hi) >> 1; if (s_ids[mid] < id) lo = mid + 1; else hi = mid; }
-  return (lo < R && s_ids[lo] == id) ? lo : R;   // (every id >= 0 the link kernel wrote is in the row it read)
-}
+#include "mot_track_place.h"   // the chunk geometry, the key of a point and P3's placement body (shared with track_accum.hip)
 
 // ------------------------------------------------------------------------------------------ P0
 __global__ void MOT_TP_BOUNDS(kTpBlock)
@@ -166,90 +137,43 @@ track_points_scan_kernel(TrackPointBuffers t, int b0, int rest, mot_track_segmen
 }
 
 // ------------------------------------------------------------------------------------------ P3
-// A chunk is 16 tiles of 64 consecutive points; the workgroup's four waves take four consecutive tiles per step, in index order. s_base[key] is where the next
-// point of a key goes; within a step a point's place is s_base[key] + (points of the key in the step's lower tiles, s_cnt) + (lower lanes of its own tile that
-// hold the key). After every step the lowest lane of each (tile, key) moves s_base on by its tile's count — LDS integer adds of one step, complete before the
-// next step reads — and clears its entry. Ids and points of all four steps are loaded up front.
-__global__ void MOT_TP_BOUNDS(kTpBlock)
-track_points_scatter_kernel(TrackPointBuffers t, int b0, int rest, const EgoTf* __restrict__ tf, mot_track_point* __restrict__ points, long point_stride) {
-  constexpr int kWaves = kTpBlock / 64;
-  __shared__ unsigned short s_cnt[kWaves][kTrackPointKeys];   // points of (tile of this step, key); zero between steps
-  __shared__ int s_base[kTrackPointKeys];
-  __shared__ int s_ids[kMaxBoxesPerFrame];
-  __shared__ float s_m[12];
-  const int kb = blockIdx.y, b = b0 + kb, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int n = tp_count(t, b);
-  const long base = (long)blockIdx.x * kTrackPointChunk;
-  if (base >= n || (int)blockIdx.x >= t.max_chunks) return;
-  const int R = tp_segments(t, b);
-  const int* __restrict__ row = t.rows + ((long)b * t.max_chunks + blockIdx.x) * kTrackPointKeys;
-  for (int j = tid; j <= R; j += kTpBlock) {
-    s_base[j] = row[j];
-    if (j < R) s_ids[j] = t.seg_id[(long)b * kMaxBoxesPerFrame + j];
-#pragma unroll
-    for (int w = 0; w < kWaves; w++) s_cnt[w][j] = 0;
-  }
-  if (tf && tid < 12) s_m[tid] = tf[kb].m[tid];
-  const int* __restrict__ ids = t.ids + (long)b * t.cap;
-  int id[kTpItems];
-  float4 q[kTpItems];
-#pragma unroll
-  for (int k = 0; k < kTpItems; k++) {
-    const long i = base + k * kTpBlock + tid;
-    id[k] = i < n ? ids[i] : -1;
-    q[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (i < n && (rest || id[k] >= 0)) q[k] = mot_load_xyz(t.elevated + (long)b * t.cap, i, t.elevated_packed);
-  }
-  __syncthreads();
-  int bits = 0;
-  while ((R >> bits) != 0) bits++;   // keys 0 .. R
-  const unsigned long long below = (1ull << lane) - 1ull;
-  const long lim = n < point_stride ? n : point_stride;   // records beyond the caller's stride are not written
-  mot_track_point* __restrict__ out = points + (long)kb * point_stride;
-  const bool vec_out = ((reinterpret_cast<uintptr_t>(out) & 15) == 0);
-#pragma unroll
-  for (int k = 0; k < kTpItems; k++) {
-    const long i = base + k * kTpBlock + tid;   // tile k * 4 + wave of the chunk: points 64 * tile .. 64 * tile + 63
-    const bool valid = i < n;
-    const int key = valid ? tp_key(id[k], s_ids, R) : 0;
-    unsigned long long same = __ballot(valid);   // the lanes of this tile that hold my key
-    for (int bit = 0; bit < bits; bit++) {
-      const unsigned long long set = __ballot((key >> bit) & 1);
-      same &= ((key >> bit) & 1) ? set : ~set;
-    }
-    const int rank = __popcll(same & below), mine = __popcll(same);
-    const bool leader = valid && rank == 0;   // the lowest lane of each key present in the tile
-    if (leader) s_cnt[wave][key] = (unsigned short)mine;
-    __syncthreads();
-    long dst = -1;
-    if (valid && (key < R || rest)) {
-      dst = s_base[key] + rank;
-      for (int w = 0; w < wave; w++) dst += s_cnt[w][key];
-    }
-    __syncthreads();
-    if (leader) { atomicAdd(&s_base[key], mine); s_cnt[wave][key] = 0; }
-    if (dst < 0 || dst >= lim) continue;   // (dst < n while the rows are this frame's; never a store outside the slot's records)
-    float4 o;
-    if (tf) {   // fp32, left to right; the build has -ffp-contract=off (mot_track_prep.h's sensor -> global step, track.hip's way back)
-      o.x = s_m[0] * q[k].x + s_m[1] * q[k].y + s_m[2] * q[k].z + s_m[3];
-      o.y = s_m[4] * q[k].x + s_m[5] * q[k].y + s_m[6] * q[k].z + s_m[7];
-      o.z = s_m[8] * q[k].x + s_m[9] * q[k].y + s_m[10] * q[k].z + s_m[11];
-    } else { o.x = q[k].x; o.y = q[k].y; o.z = q[k].z; }
+// The placement is tp_place_chunk (mot_track_place.h); the sink here is the caller's block: place = the record's index in the slot's block.
+struct TpExportSink {
+  mot_track_point* __restrict__ out;
+  long lim;       // records beyond the caller's stride are not written
+  bool vec_out;
+  __device__ __forceinline__ bool takes(int, long dst) const { return dst < lim; }   // (dst < n while the rows are this frame's; never a store outside the slot's records)
+  __device__ __forceinline__ void put(int, long dst, float4 o, long i) const {
     o.w = __int_as_float((int)i);
     if (vec_out) *reinterpret_cast<float4*>(out + dst) = o;
     else { float* p = reinterpret_cast<float*>(out + dst); p[0] = o.x; p[1] = o.y; p[2] = o.z; p[3] = o.w; }
   }
+};
+__global__ void MOT_TP_BOUNDS(kTpBlock)
+track_points_scatter_kernel(TrackPointBuffers t, int b0, int rest, const EgoTf* __restrict__ tf, mot_track_point* __restrict__ points, long point_stride) {
+  MOT_TP_PLACE_LDS(s);
+  const int kb = blockIdx.y, b = b0 + kb;
+  const int n = tp_count(t, b);
+  mot_track_point* out = points + (long)kb * point_stride;
+  const TpExportSink sink = {out, n < point_stride ? n : point_stride, (reinterpret_cast<uintptr_t>(out) & 15) == 0};
+  tp_place_chunk(t, b, kb, rest, tf, s, sink);
 }
 
 // ------------------------------------------------------------------------------------------ host
+void mot_launch_track_point_counts(const TrackPointBuffers& t, int first, int batch, int max_n, hipStream_t stream) {
+  int chunks = (max_n + kTrackPointChunk - 1) / kTrackPointChunk;
+  if (chunks < 1) chunks = 1;
+  if (chunks > t.max_chunks) chunks = t.max_chunks;
+  hipLaunchKernelGGL(track_points_table_kernel, dim3(batch), dim3(kTpBlock), 0, stream, t, first);
+  hipLaunchKernelGGL(track_points_count_kernel, dim3(chunks, batch), dim3(kTpBlock), 0, stream, t, first);
+}
 void mot_launch_track_points(const TrackPointBuffers& t, int first, int batch, int max_n, int rest, const EgoTf* tf, mot_track_point* points, long point_stride,
                              mot_track_segment* segs, int max_segments, int* counts_out, hipStream_t stream) {
   int chunks = (max_n + kTrackPointChunk - 1) / kTrackPointChunk;
   if (chunks < 1) chunks = 1;
   if (chunks > t.max_chunks) chunks = t.max_chunks;
   const dim3 grid(chunks, batch);
-  hipLaunchKernelGGL(track_points_table_kernel, dim3(batch), dim3(kTpBlock), 0, stream, t, first);
-  hipLaunchKernelGGL(track_points_count_kernel, grid, dim3(kTpBlock), 0, stream, t, first);
+  mot_launch_track_point_counts(t, first, batch, max_n, stream);
   hipLaunchKernelGGL(track_points_scan_kernel, dim3(batch), dim3(kTpBlock), 0, stream, t, first, rest, segs, max_segments, counts_out);
   hipLaunchKernelGGL(track_points_scatter_kernel, grid, dim3(kTpBlock), 0, stream, t, first, rest, tf, points, point_stride);
 }

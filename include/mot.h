@@ -449,7 +449,7 @@ int mot_export_point_tracks_dev(mot_ctx* ctx, int batch, int32_t* d_ids, long st
  *
  * Four kernels per call (csrc/track_points.hip), none in any other call: 36 bytes moved per elevated point plus 12 bytes per (1024-point chunk, segment)
  * against the 32 of a plain copy into such records. Scratch, allocated at the first call and kept until mot_destroy (MOT_E_HIP if that fails; the next call
- * resumes): per slot 4100 bytes per 1024 points of max_points (rounded up) + 8 KB + 52 bytes, and 768 bytes x max_batch page-locked; mot_get_track_points adds one
+ * resumes): per slot 4100 bytes per 1024 points of max_points (rounded up) + 8 KB + 56 bytes, and 832 bytes x max_batch page-locked; mot_get_track_points adds one
  * block of 16 bytes x max_points + 17 KB per context at ITS first call. Cost (profiles/track_points.md; 512 streams x 120 k points per call): 202 - 266 us, 1.6 - 2.1 x a device-to-device copy of the same bytes. */
 enum { MOT_TRACK_POINTS_REST = 1 };            /* flags */
 typedef struct mot_track_segment {             /* 16 bytes */
@@ -466,6 +466,78 @@ int mot_export_track_points_dev(mot_ctx* ctx, int batch, int flags, int frame,
 int mot_get_track_points(mot_ctx* ctx, int slot, int flags, int frame,
         mot_track_point* points, int point_capacity, mot_track_segment* segments, int max_segments,
         int* n_points, int* n_segments);
+
+/* ---------------------------------------------------------------- per-track accumulators (additions within ABI v6)
+ * The last step of the chain above, on the device: every track's points ACCUMULATED OVER FRAMES, in the tracker's global frame, with a log of the track's pose
+ * at each contributing step beside them (so a consumer can re-centre the points on the object: INTEGRATION.md, "object-centred cloud"). One call after a fused
+ * step appends that step; nothing is launched, written or allocated unless the feature is turned on and called.
+ *
+ * LAYOUT. One accumulator per TRACK SLOT of a stream — max_tracks_total of them, the tracker's own bounded set of objects alive (or dead since the last step) at
+ * once; a slot freed by a dead track goes to a later birth, and the accumulator goes with it. Per slot: a ROW (below), a ring of points_per_track = K points and
+ * a ring of obs_per_track = O observations. The row of the track that holds slot r of stream b is d_rows[b * T + r]; its rings start at d_points[(b * T + r) * K]
+ * and d_obs[(b * T + r) * O]. RING RULE: the record appended as number t (0-based, row.total / row.obs_total count them) lies at position t & (K - 1) resp.
+ * t & (O - 1); kept = min(total, K) points, the oldest of them at position total & (K - 1) once the ring has wrapped, at 0 before.
+ *
+ * mot_set_track_accumulation(K, O): K a power of two in [64, 2^20], O 0 (no log, d_obs null) or a power of two in [1, 4096], else MOT_E_ARG. K = 0 turns the
+ * feature off and frees its memory (draining the context stream). Needs mot_set_track_links on (MOT_E_STATE otherwise), and while accumulation is on
+ * mot_set_track_links(0) answers MOT_E_STATE. Allocates max_batch x max_tracks_total x (16 K + 48 O + 32) bytes plus 8 KB of scratch per slot; MOT_E_HIP when
+ * that fails, and the mode (an earlier geometry included) stays as it was. All rows start empty (track_id -1, everything else 0) and every slot's step counter
+ * at 0, also when the geometry changes; the same geometry again changes nothing. The accumulators are NOT stream state: mot_stream_save / mot_stream_load do not
+ * carry them. mot_reset, mot_reset_slot, mot_reset_tracks_slot and mot_stream_load empty the rows of the slots they touch and restart those slots' step counters
+ * (ids restart there, so the rows must), stream-ordered and without a host synchronisation; the step those slots hold can then no longer be appended.
+ *
+ * mot_accumulate_track_points(batch): appends the latest fused step of slots 0..batch-1. Asynchronous on the context stream, nothing is read back. Validity is
+ * tested for every slot before anything is launched, and a refused call appends nothing and counts no step: MOT_E_STATE under the conditions of
+ * mot_export_point_tracks_dev (cloud, boxes and tracker step from ONE fused call, links on), and also
+ *   - after mot_sequence_dev: there slot k is frame k of ONE stream, and the id -> slot map of the intermediate frames is gone when the call returns.
+ *     Sequence mode is not supported by the accumulators.
+ *   - when a slot of the batch was already accumulated for its current step (a step is appended at most once), or was reset / loaded since that step.
+ * STEP STAMP of a slot = the number of accepted accumulate calls that covered the slot before this one (0, 1, ...; counted on the host, it travels with the
+ * slots' matrices in one stream-ordered copy). A frame refused for capacity has no owners: it appends nothing, its step still counts.
+ * APPENDING: every segment of the step as mot_export_track_points_dev defines it without MOT_TRACK_POINTS_REST (the distinct ids >= 0 of the owner row, points
+ * in input order; points without owner are not accumulated). Segment of id with n points: the row is that of the track's slot; when the row holds another id
+ * it restarts (total 0, obs_total 0, first_step = this step, track_id = id) — this is how a slot taken by a new track drops the old track's points; a dead
+ * track's row stays readable until then. Point j of the segment goes to ring position (total + j) & (K - 1), for j >= n - K only (one frame with more than K
+ * points of a track keeps the last K), as {x, y, z, step}: x, y, z the very bits the MOT_FRAME_GLOBAL export writes. Then total += n, last_step = this step,
+ * and when O > 0 one observation goes to position obs_total & (O - 1) and obs_total counts it (with O = 0 obs_total stays 0). A segment of 0 points still
+ * leaves its observation. OBSERVATION: copied, not recomputed, from the mot_track record the same step wrote for the id — what mot_get_tracks returns for it
+ * right after the fused call; count = n, n_boxes = the segment's.
+ *
+ * READERS (MOT_E_STATE while the feature is off). mot_track_accumulators_dev: the device pointers, no copy — for consumers on the context stream (or behind
+ * an event on it). mot_get_accum_rows: the slot's max_tracks_total rows to the host (synchronises); *n_rows is delivered, MOT_E_CAPACITY with nothing copied
+ * when max_rows is smaller. mot_get_track_accumulated: the row that holds track_id — MOT_E_STATE with a message when none does (never accumulated, or its slot
+ * went to another track) — its kept points and observations in CHRONOLOGICAL order, the ring unrolled, oldest first (synchronises). *n_points / *n_obs are
+ * always delivered; a null buffer is not filled and not tested; MOT_E_CAPACITY with nothing copied when a buffer that was given is too small.
+ *
+ * Kernels (csrc/track_accum.hip): the table and count kernels of the per-track point clouds, a plan kernel (one workgroup per frame) and a scatter kernel —
+ * 36 bytes moved per owned point, as mot_export_track_points_dev, nothing staged in between. Cost: unmeasured (profiles/track_accum.md; tools/time_track_accum.py
+ * measures it against that export and a device-to-device copy). */
+typedef struct mot_accum_row {      /* 32 bytes; one per TRACK SLOT of a stream */
+  int32_t  track_id;                /* mot_track.id of the track the row holds; -1: empty */
+  int32_t  first_step, last_step;   /* the slot's accumulation steps of the first / latest append */
+  int32_t  obs_total;               /* observations ever logged for this track */
+  uint64_t total;                   /* points ever appended for this track; kept = min(total, points_per_track) */
+  uint64_t reserved;                /* 0 */
+} mot_accum_row;
+typedef struct mot_accum_point { float x, y, z; int32_t step; } mot_accum_point;   /* 16 bytes, MOT_FRAME_GLOBAL */
+typedef struct mot_accum_obs {      /* 48 bytes: the track as the step that contributed left it */
+  int32_t step, count, n_boxes, track_manage;   /* the step stamp, the segment's points and boxes, mot_track.track_manage */
+  float   px, py;  int32_t is_static, lifetime; /* mot_track.px, .py (global frame), .is_static, .lifetime */
+  double  v, yaw;                               /* mot_track.v, .yaw */
+} mot_accum_obs;
+typedef struct mot_accum_view {     /* device pointers of the context's accumulators, valid until they are turned off (or their geometry changes) or the context is destroyed */
+  const mot_accum_row* d_rows;      /* [max_batch][tracks_per_slot] */
+  const mot_accum_point* d_points;  /* [max_batch][tracks_per_slot][points_per_track], a ring per row */
+  const mot_accum_obs* d_obs;       /* [max_batch][tracks_per_slot][obs_per_track], a ring per row; null when obs_per_track == 0 */
+  int32_t tracks_per_slot, points_per_track, obs_per_track, max_batch;
+} mot_accum_view;
+int mot_set_track_accumulation(mot_ctx* ctx, int points_per_track, int obs_per_track);
+int mot_accumulate_track_points(mot_ctx* ctx, int batch);
+int mot_track_accumulators_dev(mot_ctx* ctx, mot_accum_view* out);
+int mot_get_accum_rows(mot_ctx* ctx, int slot, mot_accum_row* rows, int max_rows, int* n_rows);
+int mot_get_track_accumulated(mot_ctx* ctx, int slot, int track_id, mot_accum_row* row,
+        mot_accum_point* points, int point_capacity, int* n_points,
+        mot_accum_obs* obs, int obs_capacity, int* n_obs);
 
 /* on != 0: the fused entry points send their launch sequence (13 kernels with the tracker) as ONE hipGraph launch, captured once per launch geometry
  * (batch, chunks of the largest frame, tracker on / off, outputs); what changes per call without changing the geometry travels in the
