@@ -85,6 +85,10 @@ ACCUM_ROW_DTYPE = np.dtype([("track_id", "i4"), ("first_step", "i4"), ("last_ste
 ACCUM_POINT_DTYPE = np.dtype([("xyz", "f4", 3), ("step", "i4")])
 ACCUM_OBS_DTYPE = np.dtype([("step", "i4"), ("count", "i4"), ("n_boxes", "i4"), ("track_manage", "i4"), ("px", "f4"), ("py", "f4"), ("is_static", "i4"), ("lifetime", "i4"),
                             ("v", "f8"), ("yaw", "f8")])
+# struct mot_track_model and the flags of mot_export_track_models_dev / mot_get_track_models (object-centred track models, include/mot.h)
+MOT_MODEL_AXES, MOT_MODEL_CURRENT = 1, 2
+TRACK_MODEL_DTYPE = np.dtype([("track_id", "i4"), ("first", "i4"), ("count", "i4"), ("n_obs", "i4"), ("first_step", "i4"), ("last_step", "i4"),
+                              ("min", "f4", 3), ("max", "f4", 3)])
 
 
 class MotAccumView(C.Structure):
@@ -112,6 +116,7 @@ EXPORTS = (
     "mot_set_track_links", "mot_get_box_tracks", "mot_get_point_tracks", "mot_export_point_tracks_dev",
     "mot_export_track_points_dev", "mot_get_track_points",
     "mot_set_track_accumulation", "mot_accumulate_track_points", "mot_track_accumulators_dev", "mot_get_accum_rows", "mot_get_track_accumulated",
+    "mot_export_track_models_dev", "mot_get_track_models",
     "mot_gather_unique_id", "mot_gather_create", "mot_gather_contribute", "mot_gather_result", "mot_gather_synchronize", "mot_gather_destroy", "mot_gather_last_error",
 )
 ABI_VERSION = 6
@@ -351,6 +356,25 @@ class Context:
         self._ck(self.lib.mot_get_track_accumulated(self._h, slot, int(track_id), _vp(row), _vp(pts), len(pts), C.byref(npts), _vp(obs), len(obs), C.byref(nobs)))
         pts = pts[: npts.value]
         return dict(row=row[0].copy(), xyz=pts["xyz"].copy(), step=pts["step"].copy(), obs=obs[: nobs.value].copy())
+
+    def export_track_models_dev(self, batch: int, d_points_ptr: int, point_stride: int, d_models_ptr: int, d_counts_ptr: int, axes: bool = False, current: bool = False):
+        """object-centred track models of slots 0..batch-1 from the accumulators -> caller's device blocks (mot_export_track_models_dev): 16-byte records
+        d_points[b * point_stride + i] (x', y' relative to the track's position of the point's step — axes: in the object's axes of that step — z and step as
+        accumulated), 48-byte headers d_models[b * max_tracks_total + r] (TRACK_MODEL_DTYPE) and the true numbers d_counts[b] = (non-empty models, records).
+        current: only the tracks the latest accumulate call appended to. Asynchronous on the context stream"""
+        flags = (MOT_MODEL_AXES if axes else 0) | (MOT_MODEL_CURRENT if current else 0)
+        self._ck(self.lib.mot_export_track_models_dev(self._h, int(batch), flags, C.c_void_p(d_points_ptr), C.c_long(point_stride), C.c_void_p(d_models_ptr), C.c_void_p(d_counts_ptr)))
+
+    def get_track_models(self, slot: int, axes: bool = False, current: bool = False) -> dict:
+        """the same for one slot, on the host (mot_get_track_models): models (TRACK_MODEL_DTYPE, one per track slot; track_id -1: none), xyz [n, 3] and step [n]
+        (the models' records back to back: model m owns [m.first, m.first + m.count))"""
+        flags = (MOT_MODEL_AXES if axes else 0) | (MOT_MODEL_CURRENT if current else 0)
+        models = np.zeros(self.max_tracks_total, TRACK_MODEL_DTYPE); nm, npts = C.c_int(0), C.c_int(0)
+        self._ck(self.lib.mot_get_track_models(self._h, int(slot), flags, None, 0, C.byref(nm), None, 0, C.byref(npts)))   # the counts alone
+        pts = np.zeros(max(npts.value, 1), ACCUM_POINT_DTYPE)
+        self._ck(self.lib.mot_get_track_models(self._h, int(slot), flags, _vp(models), len(models), C.byref(nm), _vp(pts), len(pts), C.byref(npts)))
+        pts = pts[: npts.value]
+        return dict(models=models[: nm.value].copy(), xyz=pts["xyz"].copy(), step=pts["step"].copy())
 
     def _track_buffer(self, slot, max_tracks):
         """records a call can deliver: one per track EVER created on the stream, which outgrows the number of slots on a long run"""

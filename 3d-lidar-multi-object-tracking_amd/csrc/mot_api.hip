@@ -368,7 +368,9 @@ static int create_impl(mot_ctx* c) {
   const size_t E = c->max_tracks_ever;
   MOT_TRY(dev_alloc(c, &c->d_pos, B * E * sizeof(Vec2d)));
   MOT_TRY(dev_alloc(c, &c->d_slot_of, B * E * sizeof(int)));
-  MOT_TRY(dev_alloc(c, &c->d_tomb, B * E * sizeof(TrackTomb)));
+  // zeroed: the tracker writes a tombstone when it EVICTS a track, and mot_stream_save copies the tombstones of every id so far — those of the live ones must not be
+  // whatever the allocator handed out (two contexts with one history then give the same snapshot bytes)
+  MOT_TRY(dev_zeroed(c, &c->d_tomb, B * E * sizeof(TrackTomb)));
   MOT_TRY(dev_zeroed(c, &c->d_used, B * ((T + 63) / 64) * sizeof(unsigned long long)));
   MOT_TRY(dev_alloc(c, &c->d_zomb, B * T * sizeof(int)));
   MOT_TRY(dev_zeroed(c, &c->d_nzomb, B * sizeof(int)));

@@ -406,6 +406,13 @@ static int accum_release(mot_ctx* c, mot_accum_row** rows, mot_accum_point** poi
   MOT_TRY(release(c, rows)); MOT_TRY(release(c, points)); MOT_TRY(release(c, obs));
   return release(c, plan);
 }
+// what the track models took at their first call goes with the tables it was sized for (the caller has drained the stream)
+static int track_models_release(mot_ctx* c) {
+  MOT_TRY(release(c, &c->d_tm_latest)); MOT_TRY(release(c, &c->tm_ring.base)); MOT_TRY(release(c, &c->d_tm_stage)); MOT_TRY(release(c, &c->d_tm_points));
+  for (bool& u : c->tm_ring.used) u = false;
+  c->tm_points_cap = 0;
+  return MOT_OK;
+}
 int accum_restart_slots(mot_ctx* c, int first, int n) {
   if (!c->accum_K) return MOT_OK;
   mot_launch_track_accum_clear(c->d_ta_rows, (long)first * c->max_tracks_total, (long)n * c->max_tracks_total, c->stream);
@@ -422,6 +429,7 @@ extern "C" int mot_set_track_accumulation(mot_ctx* c, int points_per_track, int 
     if (!c->accum_K) return MOT_OK;
     MOT_HIP(c, hipStreamSynchronize(c->stream));
     c->accum_K = c->accum_O = 0;
+    MOT_TRY(track_models_release(c));
     return accum_release(c, &c->d_ta_rows, &c->d_ta_points, &c->d_ta_obs, &c->d_ta_plan);
   }
   if (!pow2_in(K, 64, 1 << 20)) return fail(c, MOT_E_ARG, who, ": points_per_track must be 0 (off) or a power of two in [64, 2^20]");
@@ -443,6 +451,7 @@ extern "C" int mot_set_track_accumulation(mot_ctx* c, int points_per_track, int 
   }
   if (c->accum_K) {
     MOT_HIP(c, hipStreamSynchronize(c->stream));
+    MOT_TRY(track_models_release(c));
     MOT_TRY(accum_release(c, &c->d_ta_rows, &c->d_ta_points, &c->d_ta_obs, &c->d_ta_plan));
   }
   c->d_ta_rows = d_accum_rows; c->d_ta_points = d_accum_points; c->d_ta_obs = d_accum_obs; c->d_ta_plan = d_accum_plan;
@@ -553,6 +562,98 @@ extern "C" int mot_get_track_accumulated(mot_ctx* c, int slot, int track_id, mot
     MOT_HIP(c, hipMemcpyAsync(obs, ring + oldest, (no - oldest) * sizeof(mot_accum_obs), hipMemcpyDeviceToHost, c->stream));
     if (oldest) MOT_HIP(c, hipMemcpyAsync(obs + (no - oldest), ring, oldest * sizeof(mot_accum_obs), hipMemcpyDeviceToHost, c->stream));
   }
+  MOT_HIP(c, hipStreamSynchronize(c->stream));
+  return MOT_OK;
+}
+
+// ---------------------------------------------------------------------------------------- object-centred track models (track_models.hip)
+// Scratch of the feature's own at its first call (a failure half-way leaves what exists for the next call, which resumes), released by the accumulators' setter:
+// track_models_release, above. The kernels read the accumulators alone: no slot state is asked.
+static int check_track_models(mot_ctx* c, const char* who, int flags) {
+  if (flags & ~(MOT_MODEL_AXES | MOT_MODEL_CURRENT)) return fail(c, MOT_E_ARG, who, ": unknown flag bits");
+  return MOT_OK;
+}
+static int check_track_models_on(mot_ctx* c, const char* who) {
+  MOT_TRY(check_accum_on(c, who));
+  return c->accum_O ? MOT_OK : fail(c, MOT_E_STATE, who, ": the accumulators keep no observations (mot_set_track_accumulation with obs_per_track > 0)");
+}
+static int ensure_track_models(mot_ctx* c, bool host_stage) {
+  MOT_TRY(dev_alloc(c, &c->d_tm_latest, (size_t)c->batch * sizeof(int)));
+  MOT_TRY(c->tm_ring.create(c, (size_t)c->batch * sizeof(int)));
+  if (host_stage) MOT_TRY(dev_alloc(c, &c->d_tm_stage, (size_t)c->max_tracks_total * sizeof(mot_track_model) + 16));
+  return MOT_OK;
+}
+// the tables as the kernels see them; with MOT_MODEL_CURRENT every slot's latest accumulated step goes ahead of them in one stream-ordered copy
+static int track_model_buffers(mot_ctx* c, int flags, TrackModelBuffers* a) {
+  if (flags & MOT_MODEL_CURRENT) {
+    char* raw;
+    MOT_TRY(c->tm_ring.acquire(c, &raw));
+    int* latest = reinterpret_cast<int*>(raw);
+    for (int b = 0; b < c->batch; b++) latest[b] = c->accum_step[b] - 1;
+    MOT_TRY(c->tm_ring.commit(c, c->d_tm_latest, 0, (size_t)c->batch * sizeof(int), c->stream));
+  }
+  a->rows = c->d_ta_rows; a->points = c->d_ta_points; a->obs = c->d_ta_obs; a->latest = c->d_tm_latest;
+  a->T = c->max_tracks_total; a->K = c->accum_K; a->O = c->accum_O;
+  return MOT_OK;
+}
+
+extern "C" int mot_export_track_models_dev(mot_ctx* c, int batch, int flags, mot_accum_point* d_points, long point_stride, mot_track_model* d_models, int32_t* d_counts) {
+  if (!c) return MOT_E_ARG;
+  MOT_GUARD(c);
+  const char* who = "mot_export_track_models_dev";
+  MOT_TRY(check_track_models(c, who, flags));
+  if (!d_models || !d_counts || batch < 1 || batch > c->batch || point_stride < 0 || (!d_points && point_stride > 0) || ((size_t)d_points & 15) ||
+      (((size_t)d_models | (size_t)d_counts) & 3))
+    return fail(c, MOT_E_ARG, who, ": bad argument");
+  MOT_TRY(check_track_models_on(c, who));
+  MOT_TRY(ensure_track_models(c, false));
+  TrackModelBuffers a;
+  MOT_TRY(track_model_buffers(c, flags, &a));
+  mot_launch_track_models_plan(a, 0, batch, flags, d_models, reinterpret_cast<int*>(d_counts), c->stream);
+  mot_launch_track_models_transform(a, 0, batch, flags, d_points, point_stride, d_models, c->stream);
+  MOT_HIP(c, hipGetLastError());
+  return MOT_OK;
+}
+
+extern "C" int mot_get_track_models(mot_ctx* c, int slot, int flags, mot_track_model* models, int max_models, int* n_models, mot_accum_point* points, int point_capacity,
+                                    int* n_points) {
+  if (!c) return MOT_E_ARG;
+  MOT_GUARD(c);
+  const char* who = "mot_get_track_models";
+  MOT_TRY(check_track_models(c, who, flags));
+  if (slot < 0 || slot >= c->batch || max_models < 0 || point_capacity < 0 || !n_models || !n_points) return fail(c, MOT_E_ARG, who, ": slot or a capacity out of range, or a null count");
+  MOT_TRY(check_track_models_on(c, who));
+  MOT_TRY(ensure_track_models(c, true));
+  const int T = c->max_tracks_total;
+  TrackModelBuffers a;
+  MOT_TRY(track_model_buffers(c, flags, &a));
+  // the slot's headers and counts into the staging block; the counts decide what fits the caller's buffers before a record moves
+  mot_track_model* d_mod = reinterpret_cast<mot_track_model*>(c->d_tm_stage);
+  int* d_cnt = reinterpret_cast<int*>(d_mod + T);
+  mot_launch_track_models_plan(a, slot, 1, flags, d_mod, d_cnt, c->stream);
+  MOT_HIP(c, hipGetLastError());
+  char* pin;
+  MOT_TRY(pinned_scratch(c, 16, &pin));
+  int* h = reinterpret_cast<int*>(pin);
+  MOT_HIP(c, hipMemcpyAsync(h, d_cnt, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  MOT_HIP(c, hipStreamSynchronize(c->stream));
+  const int np = h[1];
+  if (h[0] < 0 || h[0] > T || np < 0) return fail(c, MOT_E_STATE, who, ": inconsistent counts");
+  *n_models = T; *n_points = np;
+  if (models && T > max_models) return fail(c, MOT_E_CAPACITY, "more models (max_tracks_total) than the caller's buffer holds");
+  if (points && np > point_capacity) return fail(c, MOT_E_CAPACITY, "more records than the caller's point buffer holds");
+  const bool want_points = points && np > 0;
+  if (want_points && c->tm_points_cap < (size_t)np) {   // (the stream is drained: nothing reads the old block)
+    MOT_TRY(release(c, &c->d_tm_points));
+    c->tm_points_cap = 0;
+    const size_t want = ((size_t)np + 65535) & ~(size_t)65535;
+    MOT_TRY(dev_alloc(c, &c->d_tm_points, want * sizeof(mot_accum_point)));
+    c->tm_points_cap = want;
+  }
+  mot_launch_track_models_transform(a, slot, 1, flags, want_points ? c->d_tm_points : nullptr, want_points ? (long)np : 0, d_mod, c->stream);   // (the extents, with or without records)
+  MOT_HIP(c, hipGetLastError());
+  if (models) MOT_HIP(c, hipMemcpyAsync(models, d_mod, (size_t)T * sizeof(mot_track_model), hipMemcpyDeviceToHost, c->stream));
+  if (want_points) MOT_HIP(c, hipMemcpyAsync(points, c->d_tm_points, (size_t)np * sizeof(mot_accum_point), hipMemcpyDeviceToHost, c->stream));
   MOT_HIP(c, hipStreamSynchronize(c->stream));
   return MOT_OK;
 }

@@ -240,6 +240,13 @@ struct mot_ctx {
   mot_accum_obs* d_ta_obs = nullptr;       // [batch][max_tracks_total][O], null when O == 0
   TrackAccumPlan* d_ta_plan = nullptr;     // [batch][kMaxBoxesPerFrame]
   std::vector<int> accum_step;             // [batch] accepted accumulate calls that covered the slot (the next step stamp)
+  // mot_export_track_models_dev / mot_get_track_models (track_models.hip): allocated at the first call, released WITH the accumulators (the setter: off, or another
+  // geometry); the ring's events stay in the registry until mot_destroy. The kernels read the accumulators and write only the caller's blocks or the staging blocks
+  int* d_tm_latest = nullptr;              // [batch] every slot's latest accumulated step (accum_step - 1), sent ahead of a MOT_MODEL_CURRENT call
+  PinnedRing tm_ring;                      // blocks of `batch` ints
+  char* d_tm_stage = nullptr;              // mot_get_track_models: one slot's [T headers][2 counts] before they go to the host (allocated at ITS first call)
+  mot_accum_point* d_tm_points = nullptr;  // ... and its records: tm_points_cap of them, grown to what a call needs
+  size_t tm_points_cap = 0;
   std::vector<EgoTf> link_tf;          // [batch] the matrix every slot's boxes took in its last fused call with the tracker, kept while links are on (host side)
   Vec2d* d_cp = nullptr;
   TrackItem* d_items = nullptr;

@@ -410,6 +410,21 @@ void mot_launch_track_accum(const TrackPointBuffers& t, const TrackAccumBuffers&
 // rows [first, first + n) of the context's row table back to empty
 void mot_launch_track_accum_clear(mot_accum_row* rows, long first, long n, hipStream_t stream);
 
+// Object-centred track models (track_models.hip, mot_export_track_models_dev): the accumulators' rings joined with their pose logs. Read-only views of the tables above.
+constexpr int kTrackModelTile = 128;   // records a workgroup (one wave) of the transform kernel takes per round
+struct TrackModelBuffers {
+  const mot_accum_row* rows;       // [B][T]
+  const mot_accum_point* points;   // [B][T][K]
+  const mot_accum_obs* obs;        // [B][T][O], O > 0
+  const int* latest;               // [B] every slot's latest accumulated step (-1: none yet); read with MOT_MODEL_CURRENT only
+  int T, K, O;
+};
+// slots first .. first + batch - 1 into block k = 0 .. batch - 1 of the caller's buffers: the headers (extent 0) and the two counts per slot, then the records and the extents
+// (points may be null with point_stride 0: extents only). The second launch reads the headers the first one wrote.
+void mot_launch_track_models_plan(const TrackModelBuffers& a, int first, int batch, int flags, mot_track_model* models, int* counts, hipStream_t stream);
+void mot_launch_track_models_transform(const TrackModelBuffers& a, int first, int batch, int flags, mot_accum_point* points, long point_stride, mot_track_model* models,
+                                       hipStream_t stream);
+
 #ifdef MOT_HIPEMU
 #define MOT_WAVE_SYNC() ((void)__ballot(1))
 #else

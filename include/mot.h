@@ -539,6 +539,55 @@ int mot_get_track_accumulated(mot_ctx* ctx, int slot, int track_id, mot_accum_ro
         mot_accum_point* points, int point_capacity, int* n_points,
         mot_accum_obs* obs, int obs_capacity, int* n_obs);
 
+/* ---------------------------------------------------------------- object-centred track models (additions within ABI v6)
+ * What the accumulators exist for, computed where they live: every track's accumulated points RE-CENTRED ON THE OBJECT — each point minus the track's position
+ * at the step that brought it, optionally turned into the object's axes of that step — dense over frames, packed per stream, with the cloud's extent. The calls
+ * only READ the accumulators; nothing is launched or allocated outside them. Valid whenever accumulation is on with obs_per_track > 0 (MOT_E_STATE otherwise),
+ * whatever the slots' frame chain holds: after a stage-wise call, after a reset or mot_stream_load (the touched slots' models are then empty), before the first
+ * accumulate call (all empty).
+ *
+ * mot_export_track_models_dev(batch, flags, ...): rows r = 0 .. T-1 (T = max_tracks_total, indexed as mot_accum_row is) of slots 0 .. batch-1, into block b of the
+ * caller's DEVICE buffers: d_models[b * T + r], d_points[b * point_stride + ...], d_counts[2 * b] = the slot's non-empty models, d_counts[2 * b + 1] = its records.
+ * Asynchronous on the context stream, nothing is read back; two calls on the same accumulators give identical bytes. flags: MOT_MODEL_AXES | MOT_MODEL_CURRENT,
+ * any other bit MOT_E_ARG. MOT_E_ARG also for batch outside [1, max_batch], point_stride < 0, null d_models / d_counts, d_points null with point_stride > 0
+ * (null with point_stride 0: headers and extents only), d_points not 16-byte or the others not 4-byte aligned.
+ *   WHICH ROWS GIVE NO MODEL ({-1, 0, ...}): a row with track_id < 0 or without a logged observation; with MOT_MODEL_CURRENT every row whose last_step is not the
+ *     slot's latest accumulated step (the tracks the latest accumulate call did not append to; the step travels in one stream-ordered copy ahead of the kernels).
+ *     A dead track's row that is still readable gives a model unless MOT_MODEL_CURRENT is set.
+ *   KEPT RECORDS: the ring's kept points in chronological order whose step is at least the OLDEST LOGGED observation's step — a contiguous suffix of the unrolled
+ *     ring (step stamps never decrease along it, the log holds one observation per contributing step). Older points, whose pose has left the log, are left out:
+ *     choose obs_per_track for the history the models should span.
+ *   RECORD {x', y', z, step}: z and step are the ring's bits; o = the logged observation whose step is the point's; dx = x - o.px, dy = y - o.py (one fp32
+ *     subtraction each). Without MOT_MODEL_AXES x' = dx, y' = dy. With it c = (float)cos(o.yaw), s = (float)sin(o.yaw) (evaluated in double, once per
+ *     observation), x' = c*dx + s*dy, y' = c*dy - s*dx in fp32, left to right, no contraction: the rotation by -yaw.
+ *   PACKING: the models of a slot lie back to back in ascending r: `first` of a model = first + count of the previous non-empty one, 0 for the first. A slot with
+ *     more records than point_stride gets the first point_stride of them and nothing beyond is written; first, count and d_counts carry the TRUE numbers.
+ *   EXTENT: min / max over the model's records whose three coordinates are all finite (all 0 when none is), over all `count` records also when the block
+ *     truncates them. A record with a non-finite coordinate (a diverged track's pose can be NaN) is still written.
+ * mot_get_track_models(slot, flags, ...): the same for ONE slot, to the host (synchronises). *n_models = T and *n_points are always delivered; a null buffer is
+ * not filled and not tested; MOT_E_CAPACITY with nothing copied when a buffer that was given is too small; MOT_E_ARG for a slot or capacity out of range,
+ * unknown flag bits or a null count.
+ * Memory: the latest-step block of the export (4 bytes per slot, device and page-locked) and the getter's staging block (48 T bytes, and the slot's records,
+ * grown on demand) are allocated at the first call and released when accumulation is turned off or its geometry changes, and by mot_destroy; MOT_E_HIP when
+ * that fails, with everything else as it was.
+ * Kernels (csrc/track_models.hip): a plan kernel (one workgroup per stream) and a transform kernel (one workgroup per model): 16 bytes read and 16 written per
+ * record. Cost (profiles/track_models.md, tools/time_track_models.py): 512 streams x 64 track slots, K = 4096, O = 16, 28 M records in 12 k models: 261 us per call,
+ * 265 with MOT_MODEL_AXES = 1.5 x a device-to-device copy of the same records. */
+enum { MOT_MODEL_AXES = 1, MOT_MODEL_CURRENT = 2 };
+typedef struct mot_track_model {    /* 48 bytes; one per TRACK SLOT of a stream, indexed as mot_accum_row is */
+  int32_t track_id;                 /* the row's id; -1: empty row, every other field 0 */
+  int32_t first, count;             /* the model's records in the slot's point block (TRUE numbers) */
+  int32_t n_obs;                    /* logged observations the model draws on = min(row.obs_total, obs_per_track) */
+  int32_t first_step, last_step;    /* step of the oldest logged observation; row.last_step */
+  float   min_x, min_y, min_z, max_x, max_y, max_z;   /* extent of the records in the model's frame; all 0 when no finite record */
+} mot_track_model;
+int mot_export_track_models_dev(mot_ctx* ctx, int batch, int flags,
+        mot_accum_point* d_points, long point_stride,      /* records per slot */
+        mot_track_model* d_models,                          /* [batch][max_tracks_total] */
+        int32_t* d_counts /* [batch][2]: non-empty models, records — the TRUE numbers */);
+int mot_get_track_models(mot_ctx* ctx, int slot, int flags, mot_track_model* models, int max_models, int* n_models,
+        mot_accum_point* points, int point_capacity, int* n_points);
+
 /* on != 0: the fused entry points send their launch sequence (13 kernels with the tracker) as ONE hipGraph launch, captured once per launch geometry
  * (batch, chunks of the largest frame, tracker on / off, outputs); what changes per call without changing the geometry travels in the
  * device-resident argument block. For contexts somebody waits on frame by frame (one or a few streams): the host's part of a frame
