@@ -115,7 +115,7 @@ EXPORTS = (
     "mot_sensor_pose", "mot_export_tracks_frame_dev", "mot_export_tracks_packed_frame_dev", "mot_fetch_tracks_frame_async", "mot_tracking_node_frame",
     "mot_set_track_links", "mot_get_box_tracks", "mot_get_point_tracks", "mot_export_point_tracks_dev",
     "mot_export_track_points_dev", "mot_get_track_points",
-    "mot_set_track_accumulation", "mot_accumulate_track_points", "mot_track_accumulators_dev", "mot_get_accum_rows", "mot_get_track_accumulated",
+    "mot_set_track_accumulation", "mot_accumulate_track_points", "mot_sequence_accumulate_dev", "mot_track_accumulators_dev", "mot_get_accum_rows", "mot_get_track_accumulated",
     "mot_export_track_models_dev", "mot_get_track_models",
     "mot_gather_unique_id", "mot_gather_create", "mot_gather_contribute", "mot_gather_result", "mot_gather_synchronize", "mot_gather_destroy", "mot_gather_last_error",
 )
@@ -491,6 +491,16 @@ class Context:
         assert len(ts) == len(ev) == len(ey) == K
         self._ck(self.lib.mot_sequence_dev(self._h, C.c_void_p(d_ptr), C.c_long(frame_stride_floats), _vp(n), K, _vp(ts), _vp(ev), _vp(ey),
                                            C.c_void_p(d_tracks_ptr or None), int(max_per_frame), C.c_void_p(d_counts_ptr or None)))
+
+    def sequence_accumulate_dev(self, d_ptr: int, frame_stride_floats: int, n_points, timestamps, ego_v, ego_yaw, d_tracks_ptr: int = 0,
+                                max_per_frame: int = 0, d_counts_ptr: int = 0):
+        """sequence_dev, and every frame appended to stream 0's per-track accumulators in the same asynchronous call (mot_sequence_accumulate_dev): what
+        len(n_points) rounds of frames_dev(batch 1) + accumulate_track_points(1) leave in slot 0, bit for bit. Needs links and accumulation on."""
+        n = np.ascontiguousarray(n_points, np.int32); K = len(n)
+        ts = np.ascontiguousarray(timestamps, np.float64); ev = np.ascontiguousarray(ego_v, np.float64); ey = np.ascontiguousarray(ego_yaw, np.float64)
+        assert len(ts) == len(ev) == len(ey) == K
+        self._ck(self.lib.mot_sequence_accumulate_dev(self._h, C.c_void_p(d_ptr), C.c_long(frame_stride_floats), _vp(n), K, _vp(ts), _vp(ev), _vp(ey),
+                                                      C.c_void_p(d_tracks_ptr or None), int(max_per_frame), C.c_void_p(d_counts_ptr or None)))
 
     def get_ground(self, slot: int = 0, n_hint: int | None = None, want_clouds: bool = True):
         """n_hint: number of input points of the frame (length of the returned mask); the buffers are sized by max_points"""

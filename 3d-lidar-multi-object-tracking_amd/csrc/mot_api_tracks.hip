@@ -413,6 +413,11 @@ static int track_models_release(mot_ctx* c) {
   c->tm_points_cap = 0;
   return MOT_OK;
 }
+// what mot_sequence_accumulate_dev took at its first call: both blocks or neither
+static int seq_accum_release(mot_ctx* c) {
+  MOT_TRY(release(c, &c->d_tas_cap));
+  return release(c, &c->d_tas_seg);
+}
 int accum_restart_slots(mot_ctx* c, int first, int n) {
   if (!c->accum_K) return MOT_OK;
   mot_launch_track_accum_clear(c->d_ta_rows, (long)first * c->max_tracks_total, (long)n * c->max_tracks_total, c->stream);
@@ -430,6 +435,7 @@ extern "C" int mot_set_track_accumulation(mot_ctx* c, int points_per_track, int 
     MOT_HIP(c, hipStreamSynchronize(c->stream));
     c->accum_K = c->accum_O = 0;
     MOT_TRY(track_models_release(c));
+    MOT_TRY(seq_accum_release(c));
     return accum_release(c, &c->d_ta_rows, &c->d_ta_points, &c->d_ta_obs, &c->d_ta_plan);
   }
   if (!pow2_in(K, 64, 1 << 20)) return fail(c, MOT_E_ARG, who, ": points_per_track must be 0 (off) or a power of two in [64, 2^20]");
@@ -452,6 +458,7 @@ extern "C" int mot_set_track_accumulation(mot_ctx* c, int points_per_track, int 
   if (c->accum_K) {
     MOT_HIP(c, hipStreamSynchronize(c->stream));
     MOT_TRY(track_models_release(c));
+    MOT_TRY(seq_accum_release(c));
     MOT_TRY(accum_release(c, &c->d_ta_rows, &c->d_ta_points, &c->d_ta_obs, &c->d_ta_plan));
   }
   c->d_ta_rows = d_accum_rows; c->d_ta_points = d_accum_points; c->d_ta_obs = d_accum_obs; c->d_ta_plan = d_accum_plan;
@@ -497,6 +504,45 @@ extern "C" int mot_accumulate_track_points(mot_ctx* c, int batch) {
   }
   MOT_HIP(c, hipGetLastError());
   for (int b = 0; b < batch; b++) { c->accum_step[b]++; c->res.step_accumulated(b); }
+  return MOT_OK;
+}
+
+// ---------------------------------------------------------------------------------------- the accumulators fed by sequence mode (track_accum_seq.hip)
+// mot_sequence_accumulate_dev is mot_sequence_dev's body (mot_api.hip) with these three hooks. The scratch of the feature's own — the capture table and the plan,
+// 72 KB per slot — is taken at the first call, both blocks or neither (a failure leaves the live allocations as they were), and goes with the accumulators.
+static TrackAccumBuffers seq_accum_buffers(const mot_ctx* c) {   // stream 0's rows, rings, slot map and records
+  TrackAccumBuffers a;
+  a.rows = c->d_ta_rows; a.points = c->d_ta_points; a.obs = c->d_ta_obs; a.plan = c->d_ta_plan; a.slot_of = c->d_slot_of; a.out = c->d_tout; a.steps = nullptr;
+  a.T = c->max_tracks_total; a.E = c->max_tracks_ever; a.K = c->accum_K; a.O = c->accum_O;
+  return a;
+}
+int seq_accum_ready(mot_ctx* c, const char* who) {
+  MOT_TRY(check_accum_on(c, who));
+  if (!c->track_links) return fail(c, MOT_E_STATE, who, ": track links are off (mot_set_track_links)");
+  MOT_TRY(ensure_track_points(c, false));
+  if (c->d_tas_cap && c->d_tas_seg) return MOT_OK;
+  const size_t n = (size_t)c->batch * kMaxBoxesPerFrame;
+  int rc = dev_alloc(c, &c->d_tas_cap, n * sizeof(TrackAccumCapture));
+  if (!rc) rc = dev_alloc(c, &c->d_tas_seg, n * sizeof(TrackAccumSeqSeg));
+  if (rc) {
+    const std::string why = c->err;
+    (void)seq_accum_release(c);
+    c->err = why;
+  }
+  return rc;
+}
+void seq_accum_capture(mot_ctx* c, int frame) { mot_launch_track_accum_capture(c->d_counts, c->d_owner, seq_accum_buffers(c), c->d_tas_cap, frame, c->stream); }
+int seq_accum_append(mot_ctx* c, int frames, int max_n) {
+  TrackPointBuffers t;
+  t.ids = c->d_point_track; t.elevated = c->d_elev; t.cap = c->cap; t.counts = c->d_counts; t.owner = c->d_owner;
+  t.seg_id = c->d_tp_seg_id; t.seg_boxes = c->d_tp_seg_boxes; t.seg_n = c->d_tp_seg_n; t.rows = c->d_tp_rows; t.max_chunks = c->tp_chunks;
+  t.elevated_packed = c->res.elev_packed_at(0) ? 1 : 0;   // (one fused call filled the slots: one layout)
+  const TrackAccumSeqBuffers s = {c->d_tas_cap, c->d_tas_seg, c->accum_step[0]};
+  // frame k's matrix is entry k of the call's own argument block (what link_tf[k] keeps on the host): later calls rewrite it behind these kernels, stream-ordered
+  mot_launch_track_accum_sequence(t, seq_accum_buffers(c), s, frames, max_n, c->d_ego, c->stream);
+  MOT_HIP(c, hipGetLastError());
+  c->accum_step[0] += frames;   // (a frame refused for capacity appended nothing and counts)
+  c->res.sequence_accumulated(frames);
   return MOT_OK;
 }
 

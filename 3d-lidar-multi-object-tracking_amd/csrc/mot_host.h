@@ -29,6 +29,7 @@
 //   tracker_fed (mot_track_step, _track_steps_dev, _tracking_node_frame: boxes from outside)  the slots stepped   links on ? Boxes : as before
 //   links_switched (mot_set_track_links)                                           all         links -> None (no step since)
 //   (fused_batch and box_stage also record `regrouped`: whether the box stage ran on the cluster-ordered copy, MOT_ORDER_ANY; every transition that clears `boxes` clears it)
+//   sequence_accumulated (mot_sequence_accumulate_dev, behind its fused_batch)      0..frames-1 `accumulated`: the frames are in stream 0's accumulators; they stay `sequence` slots
 //   compaction_rerun (mot_get_ground on demand, mot_time_stage)                    0..batch-1  as run       -                             -      as run, unless Foreign        -
 //   describe_batch (set_batch): the last_* input description. Nothing is vouched for in a slot at or beyond last_batch that needs the batch's input.
 // per-point labels: not computed, the cloud was uploaded by a stage-wise call (no cell codes: mot_get_clusters computes them from the points) / not computed, cloud and cell
@@ -48,7 +49,8 @@ struct SlotState {
   bool regrouped = false;                 // the box stage ran in MOT_ORDER_ANY: its products (groups, cluster order, first / extreme point indices) index the slot's
                                           // cluster-ordered COPY of the cloud, not the cloud itself. Meaningful while `boxes`; every reader that walks clusters asks.
   LinkState links = kLinksNone;
-  bool sequence = false;                  // the slot holds FRAME k of one stream (mot_sequence_dev), not stream k's frame: the per-track accumulators refuse it
+  bool sequence = false;                  // the slot holds FRAME k of one stream (mot_sequence_dev, mot_sequence_accumulate_dev), not stream k's frame:
+                                          // mot_accumulate_track_points refuses it
   bool accumulated = false;               // mot_accumulate_track_points has appended the step the slot holds (or a reset / load has put it out of reach): not again
 };
 struct Residency {
@@ -93,6 +95,8 @@ struct Residency {
   bool sequence_frame(int slot) const { return slots[slot].sequence; }
   bool accumulated(int slot) const { return slots[slot].accumulated; }
   void step_accumulated(int slot) { slots[slot].accumulated = true; }   // (also: the slot's stream was reset or loaded — the step it holds belongs to ids that are gone)
+  // mot_sequence_accumulate_dev has appended the frames the slots hold to stream 0's accumulators (they stay sequence slots: no call appends them again)
+  void sequence_accumulated(int frames) { for (int b = 0; b < frames; b++) slots[b].accumulated = true; }
   bool elev_packed_at(int slot) const { return slots[slot].packed; }
   bool labels_ready(int slot) const { return slots[slot].labels == kLabelsReady; }
   bool cells_usable(int slot) const { return slots[slot].labels == kLabelsFromCells; }
@@ -239,7 +243,10 @@ struct mot_ctx {
   mot_accum_point* d_ta_points = nullptr;  // [batch][max_tracks_total][K]
   mot_accum_obs* d_ta_obs = nullptr;       // [batch][max_tracks_total][O], null when O == 0
   TrackAccumPlan* d_ta_plan = nullptr;     // [batch][kMaxBoxesPerFrame]
-  std::vector<int> accum_step;             // [batch] accepted accumulate calls that covered the slot (the next step stamp)
+  std::vector<int> accum_step;             // [batch] accepted accumulate calls that covered the slot (the next step stamp); a sequence call counts its frames on slot 0
+  // mot_sequence_accumulate_dev (track_accum_seq.hip): allocated together at its first call, released WITH the accumulators (the setter: off, or another geometry)
+  TrackAccumCapture* d_tas_cap = nullptr;  // [batch][kMaxBoxesPerFrame] what every step of the chain leaves for the append behind it
+  TrackAccumSeqSeg* d_tas_seg = nullptr;   // [batch][kMaxBoxesPerFrame] the plan of every (frame, segment)
   // mot_export_track_models_dev / mot_get_track_models (track_models.hip): allocated at the first call, released WITH the accumulators (the setter: off, or another
   // geometry); the ring's events stay in the registry until mot_destroy. The kernels read the accumulators and write only the caller's blocks or the staging blocks
   int* d_tm_latest = nullptr;              // [batch] every slot's latest accumulated step (accum_step - 1), sent ahead of a MOT_MODEL_CURRENT call
@@ -392,6 +399,11 @@ TrackBuffers track_buffers(mot_ctx* c, bool fused);
 void prepare_track_args(mot_ctx* c, TrackFrameArgs* targs, int slot, int m, double timestamp, bool run);
 int pinned_scratch(mot_ctx* c, size_t bytes, char** out);
 int accum_restart_slots(mot_ctx* c, int first, int n);   // the accumulators of those streams back to empty, stream-ordered (nothing while the feature is off)
+// mot_sequence_accumulate_dev's share of the accumulators (the entry point itself is mot_sequence_dev's body, mot_api.hip): links and accumulation on and the scratch
+// there, before anything runs / the capture behind tracker step `frame` / the append of slots 0 .. frames - 1 behind the chain, with the host's bookkeeping
+int seq_accum_ready(mot_ctx* c, const char* who);
+void seq_accum_capture(mot_ctx* c, int frame);
+int seq_accum_append(mot_ctx* c, int frames, int max_n);
 // head of a packed live-track block: one count per slot, padded to 16 bytes; the records follow (mot_export_tracks_packed_dev, mot_gather)
 inline long mot_packed_head_bytes(int batch) { return ((long)batch * 4 + 15) & ~15l; }
 #endif  // MOT_HOST_H_

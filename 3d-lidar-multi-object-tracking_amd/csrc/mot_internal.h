@@ -410,6 +410,29 @@ void mot_launch_track_accum(const TrackPointBuffers& t, const TrackAccumBuffers&
 // rows [first, first + n) of the context's row table back to empty
 void mot_launch_track_accum_clear(mot_accum_row* rows, long first, long n, hipStream_t stream);
 
+// The accumulators fed by sequence mode (track_accum_seq.hip, mot_sequence_accumulate_dev): slot k = frame k of ONE stream, every frame appended to stream 0's rows.
+struct TrackAccumCapture {     // 40 bytes, per (frame, box of its owner row): what is gone a tracker step later
+  int slot;                    // slot_of[owner] right after the frame's step; -1: no owner, or an id / slot out of range
+  int track_manage, is_static, lifetime;   // the slot's mot_track record as that step left it: the fields of mot_accum_obs
+  float px, py;
+  double v, yaw;
+};
+struct TrackAccumSeqSeg {      // 32 bytes, per (frame, segment)
+  int id, row, count, box;     // the segment's id, its row of stream 0 (-1: dropped), its points, a box of the frame that carries the id
+  unsigned long long t0;       // sequence number of its first point within the track's incarnation (the row's total before the frame)
+  int u, lo;                   // ... of its observation (obs_total before the frame); first point of the segment that the call writes (0x7fffffff: none)
+};
+struct TrackAccumSeqBuffers {
+  TrackAccumCapture* cap;      // [frames][kMaxBoxesPerFrame]
+  TrackAccumSeqSeg* seg;       // [frames][kMaxBoxesPerFrame]
+  int step0;                   // step stamp of frame 0; frame k gets step0 + k
+};
+// right behind tracker step `frame` of a sequence: a's slot_of / out are stream 0's, counts / owner the context's tables ([slot]...)
+void mot_launch_track_accum_capture(const int* counts, const int* owner, const TrackAccumBuffers& a, TrackAccumCapture* cap, int frame, hipStream_t stream);
+// behind the last step and the point-link launch: slots 0 .. frames - 1 appended, in order, to the rows / rings a points at (stream 0's); tf: every frame's matrix
+void mot_launch_track_accum_sequence(const TrackPointBuffers& t, const TrackAccumBuffers& a, const TrackAccumSeqBuffers& s, int frames, int max_n, const EgoTf* tf,
+                                     hipStream_t stream);
+
 // Object-centred track models (track_models.hip, mot_export_track_models_dev): the accumulators' rings joined with their pose logs. Read-only views of the tables above.
 constexpr int kTrackModelTile = 128;   // records a workgroup (one wave) of the transform kernel takes per round
 struct TrackModelBuffers {

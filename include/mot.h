@@ -490,7 +490,7 @@ int mot_get_track_points(mot_ctx* ctx, int slot, int flags, int frame,
  * tested for every slot before anything is launched, and a refused call appends nothing and counts no step: MOT_E_STATE under the conditions of
  * mot_export_point_tracks_dev (cloud, boxes and tracker step from ONE fused call, links on), and also
  *   - after mot_sequence_dev: there slot k is frame k of ONE stream, and the id -> slot map of the intermediate frames is gone when the call returns.
- *     Sequence mode is not supported by the accumulators.
+ *     This call does not serve sequence mode; mot_sequence_accumulate_dev (below) appends a sequence's frames inside the sequence call.
  *   - when a slot of the batch was already accumulated for its current step (a step is appended at most once), or was reset / loaded since that step.
  * STEP STAMP of a slot = the number of accepted accumulate calls that covered the slot before this one (0, 1, ...; counted on the host, it travels with the
  * slots' matrices in one stream-ordered copy). A frame refused for capacity has no owners: it appends nothing, its step still counts.
@@ -538,6 +538,40 @@ int mot_get_accum_rows(mot_ctx* ctx, int slot, mot_accum_row* rows, int max_rows
 int mot_get_track_accumulated(mot_ctx* ctx, int slot, int track_id, mot_accum_row* row,
         mot_accum_point* points, int point_capacity, int* n_points,
         mot_accum_obs* obs, int obs_capacity, int* n_obs);
+
+/* ---------------------------------------------------------------- a recorded drive into the accumulators (addition within ABI v6)
+ * mot_sequence_accumulate_dev IS mot_sequence_dev — the same arguments, the same launch sequence — and appends all `frames` steps to the accumulators of stream
+ * (slot) 0 in the same asynchronous call: nothing is read back, no host synchronisation. What mot_accumulate_track_points cannot do after mot_sequence_dev
+ * (the id -> slot map of the intermediate frames is gone when that call returns) is done inside the call: a small kernel behind every tracker step keeps what
+ * the next step moves, and behind the last step all frames are appended at once.
+ *
+ * RESULT. The accumulators hold, bit for bit, what `frames` rounds of { mot_frames_dev(batch 1) on frame k; mot_accumulate_track_points(ctx, 1) } would have
+ * left in slot 0 — its rows, the kept part of their rings (RING RULE above) and the logs — from the same tracker and accumulator state. Ring and log positions
+ * outside a row's kept range are undefined, as they are after a restart. Every other result is byte-identical to mot_sequence_dev's: slot k = frame k for
+ * mot_get_ground / _clusters / _boxes / _box_tracks / _point_tracks / _track_points, the tracker state, d_tracks / d_counts.
+ * ROWS: those of slot 0, d_rows[0 * T + r], with the rings beside them; the rows of slots >= 1 are not touched. The accumulators stay sized max_batch x
+ * max_tracks_total (mot_set_track_accumulation): a context used for sequences only fills slot 0's.
+ * STEP STAMPS: frame k gets (slot 0's step counter) + k and the counter advances by `frames`; a frame refused for capacity appends nothing and still counts.
+ * Calls chain: frame-by-frame steps on slot 0 (mot_frames_dev batch 1 + mot_accumulate_track_points) before and after, several sequence calls in a row (a
+ * drive replayed in chunks) — all continue the same rows and the same counter.
+ * AFTER THE CALL the slots are sequence slots, as after mot_sequence_dev: mot_accumulate_track_points answers MOT_E_STATE on them (nothing is appended twice).
+ * mot_reset* and mot_stream_load empty slot 0's rows and restart its counter as they always do. mot_export_track_models_dev / mot_get_track_models on slot 0
+ * work unchanged on the result; MOT_MODEL_CURRENT refers to the step of the last frame.
+ * REFUSALS, each before anything has run (the tracker has not stepped): MOT_E_STATE unless mot_set_track_links and mot_set_track_accumulation are on; the
+ * argument errors of mot_sequence_dev; MOT_E_HIP when the scratch of the call's own (72 KB per slot of max_batch: what every step leaves behind and the plan of
+ * every frame's segments) cannot be had at the first call — both blocks or neither, the next call tries again. That scratch — and, at a first use, the scratch of
+ * the per-track point clouds — is all the call allocates; it is released with the accumulators (mot_set_track_accumulation(0, ...) or another geometry) and by
+ * mot_destroy. mot_sequence_dev itself launches, writes and allocates what it always did, with accumulation on or off.
+ * WITHIN ONE CALL frames meet in a ring (many frames bring more than K points of a track between them; a track slot goes to a new track in mid-call): every
+ * ring and log position is written by at most one record of the call — only the segments of a row's FINAL id contribute, only its last K points and last O
+ * observations are written — so the result does not depend on the order in which workgroups run.
+ * Kernels (csrc/track_accum_seq.hip): one capture launch per step; behind the chain the table and count kernels of the per-track point clouds over all frames,
+ * a per-frame segment kernel, ONE serial plan workgroup that walks the frames in order, a finish kernel (logs, kept ranges) and the scatter — six launches
+ * whatever `frames` is. Cost (profiles/track_accum_sequence.md, tools/time_track_accum_sequence.py; one 154-frame drive of 120 k-point frames, K = 4096, O = 16):
+ * 8.17 ms per call against 7.71 ms of mot_sequence_dev alone (+ 0.46 ms, 3.2 us per frame) and 31.1 ms of the frame-by-frame route: 0.26 x. */
+int mot_sequence_accumulate_dev(mot_ctx* ctx, const float* d_xyzw, long frame_stride, const int* n_points, int frames,
+                                const double* timestamps, const double* ego_v, const double* ego_yaw,
+                                void* d_tracks, int max_per_frame, int32_t* d_counts);
 
 /* ---------------------------------------------------------------- object-centred track models (additions within ABI v6)
  * What the accumulators exist for, computed where they live: every track's accumulated points RE-CENTRED ON THE OBJECT — each point minus the track's position
