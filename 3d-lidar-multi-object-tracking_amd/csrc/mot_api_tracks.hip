@@ -234,7 +234,7 @@ extern "C" int mot_get_tracks(mot_ctx* c, int slot, mot_track* tracks, int max_t
         // the reference goes on reporting a dead track's frozen speed, and its frozen yaw + the CURRENT ego yaw (:1012-1016)
         o.v = tomb[i].v;
         double tyaw = tomb[i].yaw + c->ego[slot].step_ego_yaw;
-        if (fabs(tyaw) > 64. * M_PI) { const double r = tyaw - trunc(tyaw / (2. * M_PI)) * (2. * M_PI); tyaw = fabs(r) <= 64. * M_PI ? r : NAN; }   // (wrap_pi of track.hip)
+        if (fabs(tyaw) > 64. * M_PI) { const double r = tyaw - trunc(tyaw / (2. * M_PI)) * (2. * M_PI); tyaw = fabs(tyaw) < 0x1p55 && fabs(r) <= 64. * M_PI ? r : NAN; }   // (wrap_pi of mot_track_prep.h)
         while (tyaw > M_PI) tyaw -= 2. * M_PI;
         while (tyaw < -M_PI) tyaw += 2. * M_PI;
         o.yaw = tyaw;

@@ -6,6 +6,70 @@
 #include <cstddef>
 #include "mot_internal.h"
 
+// ---- the tracker's scalar fp64 helpers (used by track.hip). They live in this header so that the test-only device library
+// tests/devcheck/primitives.hip can call them directly and hold them bit for bit against the oracle's own (tests/primitive_cases.py).
+#define PI_D 3.14159265358979323846
+// `while (a > M_PI) a -= 2. * M_PI; while (a < -M_PI) a += 2. * M_PI;` — the reference's angle normalisation (ukf.cpp, imm_ukf_jpda.cpp
+// passim). Its cost is |a| / 2 pi iterations: a diverging track (a failed Cholesky leaves un-rooted covariance entries in the
+// sigma-point spread, ukf.cpp:651-662) drives |a| to 1e5..1e8 and ONE such track held a whole launch for 10-160 ms on the
+// MI355X (profiles/r02_kernel_trace_B512_4ctx_before_tracker_fix.txt). Up to 32 turns the loop runs as written (bit-identical to the reference);
+// beyond that the whole turns come off in one step first — the result differs from the loop's by the roundings the loop
+// would have accumulated (< 1e-9 for |a| < 1e4), on tracks whose state is garbage already and which the reference's own
+// guards (:828-851) are about to kill. Inf, which hangs the reference, becomes NaN here; and so does an angle so large that the one-step
+// reduction cannot resolve it any more (|a| >= 2^55 = 3.6e16: a garbage timestamp makes dt astronomical) — it used to leave the loops below an
+// operand they cannot move: the reference spins for ever there, a GPU must not. (NaN, not a remainder: no digit of such an angle means
+// anything, and the NaN reaches the divergence guards of the next step.)
+__device__ __forceinline__ double wrap_pi(double a) {
+  if (fabs(a) > 64. * PI_D) {
+    const double r = a - trunc(a / (2. * PI_D)) * (2. * PI_D);
+    // from 2^55 on neighbouring doubles lie more than a turn apart. The remainder test alone does not catch that: the product rounds back to a
+    // itself (r = 0, at 1e300) or to a neighbour (r = +-128, at 1e18), and a garbage angle came back as a plausible one
+    // (tests/primitive_cases.py: wrap_pi_case). Inf fails the same test.
+    a = fabs(a) < 0x1p55 && fabs(r) <= 64. * PI_D ? r : __builtin_nan("");
+  }
+  while (a > PI_D) a -= 2. * PI_D;
+  while (a < -PI_D) a += 2. * PI_D;
+  return a;
+}
+__device__ __forceinline__ double det2(const double* m) { return m[0] * m[3] - m[1] * m[2]; }
+__device__ __forceinline__ void inv2(const double* m, double* o) { double d = det2(m); o[0] = m[3] / d; o[1] = -m[1] / d; o[2] = -m[2] / d; o[3] = m[0] / d; }
+
+// determinant of a 5x5 (partial-pivot elimination, what Eigen's PartialPivLU::determinant amounts to). Every index below
+// is a compile-time constant: the pivot row is brought up by conditional swaps against each candidate row, never by
+// indexing the register array with the pivot (a dynamically indexed array lives in scratch memory — the first version
+// of this function alone took 22-55 k cycles per track, as long as the whole IMM-UKF prediction).
+static __device__ double det5(const double* a) {
+  double m[25];
+#pragma unroll
+  for (int i = 0; i < 25; i++) m[i] = a[i];
+  double det = 1;
+  bool done = false;
+#pragma unroll
+  for (int k = 0; k < 5; k++) {
+    int piv = k; double best = fabs(m[k * 5 + k]);
+#pragma unroll
+    for (int r = k + 1; r < 5; r++) { double v = fabs(m[r * 5 + k]); if (v > best) { best = v; piv = r; } }
+#pragma unroll
+    for (int r = k + 1; r < 5; r++) {
+      const bool sw = piv == r;
+#pragma unroll
+      for (int c = 0; c < 5; c++) { const double t = m[k * 5 + c], q = m[r * 5 + c]; m[k * 5 + c] = sw ? q : t; m[r * 5 + c] = sw ? t : q; }
+    }
+    if (piv != k) det = done ? det : -det;
+    const double d = m[k * 5 + k];
+    if (!done) det *= d;
+    if (d == 0) done = true;   // the reference returns here: det is already 0 (or NaN) and stays
+#pragma unroll
+    for (int r = k + 1; r < 5; r++) {
+      const double f = m[r * 5 + k] / d;
+#pragma unroll
+      for (int c = k + 1; c < 5; c++) m[r * 5 + c] -= f * m[k * 5 + c];
+    }
+  }
+  return det;
+}
+
+
 // UKF::UKF + UKF::Initialize, ukf.cpp:20-249, 257-322
 static __device__ void track_init(DevTrack* t, double zx, double zy, int ref_id) {
   for (int a = 0; a < 4; a++) {

@@ -2,6 +2,11 @@
 // A butterfly over __shfl_xor costs six LDS-crossbar round trips per reduction on gfx950; the match loops of the
 // min-z and label kernels run one to three reductions per distinct key per wave, and rocprof showed them LDS-issue
 // bound. DPP row operations are plain VALU instructions with a lane-permute modifier.
+//
+// CONTRACT: every primitive here is called with ALL 64 LANES of the wave ACTIVE (never inside divergent control flow, never from a partial
+// last wave): a DPP move reads nothing from a disabled lane, so a partial EXEC mask silently changes the result. Each primitive has two bodies
+// — DPP for gfx950, __shfl* for the emulator — and tests/primitive_cases.py holds both, lane by lane, to one restatement of the prose below
+// (tests/devcheck/primitives.hip; full waves only, as the contract says).
 #ifndef MOT_WAVE_H_
 #define MOT_WAVE_H_
 
@@ -83,30 +88,6 @@ __device__ __forceinline__ int wave_scan_incl_i32(int v) {
 }
 __device__ __forceinline__ int wave_sum_i32(int v) { return __shfl(wave_scan_incl_i32(v), 63, 64); }
 #endif
-
-// sum of a double over the wave (all lanes receive it)
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#ifndef MOT_HIPEMU
-#define MOT_DPP_F64(x, ctrl, rmask)                                                                          \
-  __hiloint2double(__builtin_amdgcn_update_dpp(0, __double2hiint(x), (ctrl), (rmask), 0xf, true),             \
-                   __builtin_amdgcn_update_dpp(0, __double2loint(x), (ctrl), (rmask), 0xf, true))
-  // lanes without a valid source read 0 (bound_ctrl): adding 0.0 leaves the partial sums intact
-  v += MOT_DPP_F64(v, 0xB1, 0xf);
-  v += MOT_DPP_F64(v, 0x4E, 0xf);
-  v += MOT_DPP_F64(v, 0x141, 0xf);
-  v += MOT_DPP_F64(v, 0x140, 0xf);
-  // after the mirrors every lane of a 16-lane row holds the row's sum; combine the four rows through readlane
-#undef MOT_DPP_F64
-  double r0 = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 0), __builtin_amdgcn_readlane(__double2loint(v), 0));
-  double r1 = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 16), __builtin_amdgcn_readlane(__double2loint(v), 16));
-  double r2 = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 32), __builtin_amdgcn_readlane(__double2loint(v), 32));
-  double r3 = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 48), __builtin_amdgcn_readlane(__double2loint(v), 48));
-  return (r0 + r1) + (r2 + r3);
-#else
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-#endif
-}
 
 // a value every lane of the wave holds alike, moved to a scalar register: addresses and branches that depend on it stay scalar
 __device__ __forceinline__ int wave_uniform_i32(int v) {

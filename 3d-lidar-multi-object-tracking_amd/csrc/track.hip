@@ -40,7 +40,6 @@
 #define MOT_UPDATE_WAVES 2
 #endif
 
-#define PI_D 3.14159265358979323846
 #ifdef MOT_DBG_STREAM_TIMING   // absolute 100 MHz clocks of thread 0 inside the per-track bodies (tools/time_stream_kernel.py: one stream)
 __device__ long long* g_sdbg = nullptr;
 #define GRP_T(slot) do { if (threadIdx.x == 0 && g_sdbg) g_sdbg[slot] = wall_clock64(); } while (0)
@@ -49,63 +48,7 @@ __device__ long long* g_sdbg = nullptr;
 #endif
 
 __device__ __forceinline__ int tlane() { return (int)(threadIdx.x & 63); }
-// `while (a > M_PI) a -= 2. * M_PI; while (a < -M_PI) a += 2. * M_PI;` — the reference's angle normalisation (ukf.cpp, imm_ukf_jpda.cpp
-// passim). Its cost is |a| / 2 pi iterations: a diverging track (a failed Cholesky leaves un-rooted covariance entries in the
-// sigma-point spread, ukf.cpp:651-662) drives |a| to 1e5..1e8 and ONE such track held a whole launch for 10-160 ms on the
-// MI355X (profiles/r02_kernel_trace_B512_4ctx_before_tracker_fix.txt). Up to 32 turns the loop runs as written (bit-identical to the reference);
-// beyond that the whole turns come off in one step first — the result differs from the loop's by the roundings the loop
-// would have accumulated (< 1e-9 for |a| < 1e4), on tracks whose state is garbage already and which the reference's own
-// guards (:828-851) are about to kill. Inf, which hangs the reference, becomes NaN here; and so does an angle so large that the one-step
-// reduction cannot resolve it any more (|a| beyond ~1e17: a garbage timestamp makes dt astronomical) — it used to leave the loops below an
-// operand they cannot move: the reference spins for ever there, a GPU must not. (NaN, not a remainder: no digit of such an angle means
-// anything, and the NaN reaches the divergence guards of the next step.)
-__device__ __forceinline__ double wrap_pi(double a) {
-  if (fabs(a) > 64. * PI_D) {
-    const double r = a - trunc(a / (2. * PI_D)) * (2. * PI_D);
-    a = fabs(r) <= 64. * PI_D ? r : __builtin_nan("");
-  }
-  while (a > PI_D) a -= 2. * PI_D;
-  while (a < -PI_D) a += 2. * PI_D;
-  return a;
-}
-__device__ __forceinline__ double det2(const double* m) { return m[0] * m[3] - m[1] * m[2]; }
-__device__ __forceinline__ void inv2(const double* m, double* o) { double d = det2(m); o[0] = m[3] / d; o[1] = -m[1] / d; o[2] = -m[2] / d; o[3] = m[0] / d; }
-
-// determinant of a 5x5 (partial-pivot elimination, what Eigen's PartialPivLU::determinant amounts to). Every index below
-// is a compile-time constant: the pivot row is brought up by conditional swaps against each candidate row, never by
-// indexing the register array with the pivot (a dynamically indexed array lives in scratch memory — the first version
-// of this function alone took 22-55 k cycles per track, as long as the whole IMM-UKF prediction).
-__device__ double det5(const double* a) {
-  double m[25];
-#pragma unroll
-  for (int i = 0; i < 25; i++) m[i] = a[i];
-  double det = 1;
-  bool done = false;
-#pragma unroll
-  for (int k = 0; k < 5; k++) {
-    int piv = k; double best = fabs(m[k * 5 + k]);
-#pragma unroll
-    for (int r = k + 1; r < 5; r++) { double v = fabs(m[r * 5 + k]); if (v > best) { best = v; piv = r; } }
-#pragma unroll
-    for (int r = k + 1; r < 5; r++) {
-      const bool sw = piv == r;
-#pragma unroll
-      for (int c = 0; c < 5; c++) { const double t = m[k * 5 + c], q = m[r * 5 + c]; m[k * 5 + c] = sw ? q : t; m[r * 5 + c] = sw ? t : q; }
-    }
-    if (piv != k) det = done ? det : -det;
-    const double d = m[k * 5 + k];
-    if (!done) det *= d;
-    if (d == 0) done = true;   // the reference returns here: det is already 0 (or NaN) and stays
-#pragma unroll
-    for (int r = k + 1; r < 5; r++) {
-      const double f = m[r * 5 + k] / d;
-#pragma unroll
-      for (int c = k + 1; c < 5; c++) m[r * 5 + c] -= f * m[k * 5 + c];
-    }
-  }
-  return det;
-}
-
+// (wrap_pi, det2, inv2 and det5 — the scalar fp64 helpers — live in mot_track_prep.h, where tests/devcheck/primitives.hip reaches them)
 // (track_init — UKF::UKF + UKF::Initialize — and cp_from_bbox live in mot_track_prep.h)
 
 // ---------------------------------------------------------------------------------------------- lanes and tracks

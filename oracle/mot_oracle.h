@@ -83,6 +83,10 @@ int orc_track_step(orc_tracker* t, const float* boxes_global, int m, double time
                    int max_tracks, int* n_tracks);
 int orc_track_get_state(orc_tracker* t, int id, mot_track_state* out);
 int orc_track_count(orc_tracker* t);
+/* the tracker's scalar helpers as mot_oracle_track.c evaluates them (5x5 row-major / 2x2 row-major / radians) */
+double orc_det5(const double* a25);
+void orc_inv2(const double* m4, double* out4);
+double orc_wrap_pi(double a);
 
 #ifdef __cplusplus
 }

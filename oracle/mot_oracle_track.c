@@ -600,3 +600,9 @@ int orc_track_get_state(orc_tracker* t, int id, mot_track_state* o) {
   if (u->hasBest) memcpy(o->best_bbox, u->bestBBox, sizeof u->bestBBox);
   return MOT_OK;
 }
+
+/* the scalar helpers at the top of this file, exported as they are: tests/primitive_cases.py holds the device's restatements of them
+   (csrc/mot_track_prep.h: det5, inv2, wrap_pi) to these bit for bit */
+double orc_det5(const double* a) { return det5(a); }
+void orc_inv2(const double* m, double* o) { inv2(m, o); }
+double orc_wrap_pi(double a) { return wrap_pi(a); }

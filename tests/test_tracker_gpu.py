@@ -182,7 +182,7 @@ def test_64_live_tracks_vs_oracle(mot, hip_lib, oracle, spacing, min_live):
 
 
 def test_angles_beyond_32_turns(mot, hip_lib, oracle):
-    """csrc/track.hip wrap_pi's bounded path (the one documented deviation): discrete outputs equal the looping oracle's"""
+    """csrc/mot_track_prep.h wrap_pi's bounded path (the one documented deviation): discrete outputs equal the looping oracle's"""
     import tracker_cases as TC
     TC.angle_far_beyond_32_turns(mot, oracle)
 

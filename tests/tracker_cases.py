@@ -53,7 +53,7 @@ def many_live_tracks(mot, oracle, to_dev, lib_path=None, streams=3, T=64, frames
 
 
 def angle_far_beyond_32_turns(mot, oracle, lib_path=None):
-    """The one documented deviation from the reference (csrc/track.hip wrap_pi): up to 32 turns the normalisation loop runs as
+    """The one documented deviation from the reference (csrc/mot_track_prep.h wrap_pi): up to 32 turns the normalisation loop runs as
     written, beyond it whole turns come off in one step. Two ways past 32 turns: (a) an ego yaw of hundreds of radians — the
     output yaw is wrap(x_merge(3) + egoYaw), OT/tracking/imm_ukf_jpda.cpp:1010 — and (b) a time step of thousands of seconds,
     which carries every CTRV sigma point yaw + yawd * dt round and round (ukf.cpp:539-571). The oracle keeps the reference's
