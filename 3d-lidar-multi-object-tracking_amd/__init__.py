@@ -89,6 +89,23 @@ ACCUM_OBS_DTYPE = np.dtype([("step", "i4"), ("count", "i4"), ("n_boxes", "i4"), 
 MOT_MODEL_AXES, MOT_MODEL_CURRENT = 1, 2
 TRACK_MODEL_DTYPE = np.dtype([("track_id", "i4"), ("first", "i4"), ("count", "i4"), ("n_obs", "i4"), ("first_step", "i4"), ("last_step", "i4"),
                               ("min", "f4", 3), ("max", "f4", 3)])
+# struct mot_track_voxel_model / mot_model_voxel / mot_voxel_params of mot_export_track_model_voxels_dev / mot_get_track_model_voxels (voxel-thinned models, include/mot.h)
+MODEL_VOXEL_MAX_K = 4096
+VOXEL_MODEL_DTYPE = np.dtype([("track_id", "i4"), ("first", "i4"), ("count", "i4"), ("n_obs", "i4"), ("first_step", "i4"), ("last_step", "i4"),
+                              ("min", "f4", 3), ("max", "f4", 3), ("n_records", "i4"), ("n_outside", "i4"), ("n_sparse", "i4"), ("reserved", "i4")])
+MODEL_VOXEL_DTYPE = np.dtype([("xyz", "f4", 3), ("count", "i4")])
+assert VOXEL_MODEL_DTYPE.itemsize == 64 and MODEL_VOXEL_DTYPE.itemsize == 16
+
+
+class MotVoxelParams(C.Structure):
+    """struct mot_voxel_params"""
+    _fields_ = [("leaf_x", C.c_float), ("leaf_y", C.c_float), ("leaf_z", C.c_float), ("min_points", C.c_int32)]
+
+
+def voxel_params(leaf, min_points: int = 1) -> MotVoxelParams:
+    """leaf: one edge length for the three axes, or three"""
+    lx, ly, lz = (leaf, leaf, leaf) if np.isscalar(leaf) else leaf
+    return MotVoxelParams(float(lx), float(ly), float(lz), int(min_points))
 
 
 class MotAccumView(C.Structure):
@@ -116,7 +133,7 @@ EXPORTS = (
     "mot_set_track_links", "mot_get_box_tracks", "mot_get_point_tracks", "mot_export_point_tracks_dev",
     "mot_export_track_points_dev", "mot_get_track_points",
     "mot_set_track_accumulation", "mot_accumulate_track_points", "mot_sequence_accumulate_dev", "mot_track_accumulators_dev", "mot_get_accum_rows", "mot_get_track_accumulated",
-    "mot_export_track_models_dev", "mot_get_track_models",
+    "mot_export_track_models_dev", "mot_get_track_models", "mot_export_track_model_voxels_dev", "mot_get_track_model_voxels",
     "mot_gather_unique_id", "mot_gather_create", "mot_gather_contribute", "mot_gather_result", "mot_gather_synchronize", "mot_gather_destroy", "mot_gather_last_error",
 )
 ABI_VERSION = 6
@@ -375,6 +392,29 @@ class Context:
         self._ck(self.lib.mot_get_track_models(self._h, int(slot), flags, _vp(models), len(models), C.byref(nm), _vp(pts), len(pts), C.byref(npts)))
         pts = pts[: npts.value]
         return dict(models=models[: nm.value].copy(), xyz=pts["xyz"].copy(), step=pts["step"].copy())
+
+    def export_track_model_voxels_dev(self, batch: int, d_voxels_ptr: int, voxel_stride: int, d_models_ptr: int, d_counts_ptr: int, leaf, min_points: int = 1,
+                                      axes: bool = False, current: bool = False):
+        """the same models, one record per occupied voxel of edge `leaf` (a float, or three) -> caller's device blocks (mot_export_track_model_voxels_dev): 16-byte
+        voxels d_voxels[b * voxel_stride + i] (MODEL_VOXEL_DTYPE: the centroid of the cell's records and their number, in ascending (i_z, i_y, i_x)), 64-byte
+        headers d_models[b * max_tracks_total + r] (VOXEL_MODEL_DTYPE) and the true numbers d_counts[b] = (models, voxels). min_points: voxels with fewer records
+        are dropped. d_voxels_ptr 0 with voxel_stride 0: headers only. Asynchronous on the context stream"""
+        flags = (MOT_MODEL_AXES if axes else 0) | (MOT_MODEL_CURRENT if current else 0)
+        p = voxel_params(leaf, min_points)
+        self._ck(self.lib.mot_export_track_model_voxels_dev(self._h, int(batch), flags, C.byref(p), C.c_void_p(d_voxels_ptr or None), C.c_long(voxel_stride),
+                                                            C.c_void_p(d_models_ptr), C.c_void_p(d_counts_ptr)))
+
+    def get_track_model_voxels(self, slot: int, leaf, min_points: int = 1, axes: bool = False, current: bool = False) -> dict:
+        """the same for one slot, on the host (mot_get_track_model_voxels): models (VOXEL_MODEL_DTYPE, one per track slot; track_id -1: none), xyz [n, 3] and
+        count [n] (the models' voxels back to back: model m owns [m.first, m.first + m.count))"""
+        flags = (MOT_MODEL_AXES if axes else 0) | (MOT_MODEL_CURRENT if current else 0)
+        p = voxel_params(leaf, min_points)
+        models = np.zeros(self.max_tracks_total, VOXEL_MODEL_DTYPE); nm, nv = C.c_int(0), C.c_int(0)
+        self._ck(self.lib.mot_get_track_model_voxels(self._h, int(slot), flags, C.byref(p), None, 0, C.byref(nm), None, 0, C.byref(nv)))   # the counts alone
+        vox = np.zeros(max(nv.value, 1), MODEL_VOXEL_DTYPE)
+        self._ck(self.lib.mot_get_track_model_voxels(self._h, int(slot), flags, C.byref(p), _vp(models), len(models), C.byref(nm), _vp(vox), len(vox), C.byref(nv)))
+        vox = vox[: nv.value]
+        return dict(models=models[: nm.value].copy(), xyz=vox["xyz"].copy(), count=vox["count"].copy())
 
     def _track_buffer(self, slot, max_tracks):
         """records a call can deliver: one per track EVER created on the stream, which outgrows the number of slots on a long run"""

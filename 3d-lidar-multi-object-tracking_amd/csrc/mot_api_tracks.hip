@@ -409,8 +409,9 @@ static int accum_release(mot_ctx* c, mot_accum_row** rows, mot_accum_point** poi
 // what the track models took at their first call goes with the tables it was sized for (the caller has drained the stream)
 static int track_models_release(mot_ctx* c) {
   MOT_TRY(release(c, &c->d_tm_latest)); MOT_TRY(release(c, &c->tm_ring.base)); MOT_TRY(release(c, &c->d_tm_stage)); MOT_TRY(release(c, &c->d_tm_points));
+  MOT_TRY(release(c, &c->d_tv_scratch)); MOT_TRY(release(c, &c->d_tv_stage)); MOT_TRY(release(c, &c->d_tv_voxels));
   for (bool& u : c->tm_ring.used) u = false;
-  c->tm_points_cap = 0;
+  c->tm_points_cap = 0; c->tv_voxels_cap = 0;
   return MOT_OK;
 }
 // what mot_sequence_accumulate_dev took at its first call: both blocks or neither
@@ -700,6 +701,107 @@ extern "C" int mot_get_track_models(mot_ctx* c, int slot, int flags, mot_track_m
   MOT_HIP(c, hipGetLastError());
   if (models) MOT_HIP(c, hipMemcpyAsync(models, d_mod, (size_t)T * sizeof(mot_track_model), hipMemcpyDeviceToHost, c->stream));
   if (want_points) MOT_HIP(c, hipMemcpyAsync(points, c->d_tm_points, (size_t)np * sizeof(mot_accum_point), hipMemcpyDeviceToHost, c->stream));
+  MOT_HIP(c, hipStreamSynchronize(c->stream));
+  return MOT_OK;
+}
+
+// ---------------------------------------------------------------------------------------- voxel-thinned object models (track_voxels.hip)
+// The raw models' checks and latest-step block, and a scratch of the feature's own — the plan's headers and the per-model results, 96 bytes per row — taken at
+// the first call and released with the raw models' blocks (track_models_release). Everything is validated before anything is launched or allocated.
+static int check_track_voxels(mot_ctx* c, const char* who, int flags, const mot_voxel_params* p, TrackVoxelArgs* v) {
+  MOT_TRY(check_track_models(c, who, flags));
+  if (!p) return fail(c, MOT_E_ARG, who, ": null params");
+  const float leaf[3] = {p->leaf_x, p->leaf_y, p->leaf_z};
+  for (float l : leaf)
+    if (!(l >= 1e-3f && l <= 1e3f)) return fail(c, MOT_E_ARG, who, ": a leaf must be finite and in [1e-3, 1e3]");   // (NaN fails both comparisons)
+  if (p->min_points < 1 || p->min_points > MOT_MODEL_VOXEL_MAX_K) return fail(c, MOT_E_ARG, who, ": min_points must be in [1, MOT_MODEL_VOXEL_MAX_K]");
+  v->inv_x = 1.0f / leaf[0]; v->inv_y = 1.0f / leaf[1]; v->inv_z = 1.0f / leaf[2]; v->min_points = p->min_points;
+  return MOT_OK;
+}
+static int check_track_voxels_on(mot_ctx* c, const char* who) {
+  MOT_TRY(check_track_models_on(c, who));
+  if (c->accum_K > MOT_MODEL_VOXEL_MAX_K)
+    return fail(c, MOT_E_STATE, who, ": points_per_track exceeds MOT_MODEL_VOXEL_MAX_K = 4096, the longest model the voxel calls sort (mot_export_track_models_dev serves it)");
+  return MOT_OK;
+}
+struct TrackVoxelScratch { mot_track_model* plan; TrackVoxelResult* res; int* plan_counts; };
+static int ensure_track_voxels(mot_ctx* c, bool host_stage, TrackVoxelScratch* s) {
+  MOT_TRY(ensure_track_models(c, false));
+  const size_t rows_n = (size_t)c->batch * c->max_tracks_total;
+  MOT_TRY(dev_alloc(c, &c->d_tv_scratch, rows_n * (sizeof(mot_track_model) + sizeof(TrackVoxelResult)) + (size_t)c->batch * 2 * sizeof(int)));
+  if (host_stage) MOT_TRY(dev_alloc(c, &c->d_tv_stage, (size_t)c->max_tracks_total * sizeof(mot_track_voxel_model) + 16));
+  s->plan = reinterpret_cast<mot_track_model*>(c->d_tv_scratch);
+  s->res = reinterpret_cast<TrackVoxelResult*>(s->plan + rows_n);
+  s->plan_counts = reinterpret_cast<int*>(s->res + rows_n);
+  return MOT_OK;
+}
+
+extern "C" int mot_export_track_model_voxels_dev(mot_ctx* c, int batch, int flags, const mot_voxel_params* params, mot_model_voxel* d_voxels, long voxel_stride,
+                                                 mot_track_voxel_model* d_models, int32_t* d_counts) {
+  if (!c) return MOT_E_ARG;
+  MOT_GUARD(c);
+  const char* who = "mot_export_track_model_voxels_dev";
+  TrackVoxelArgs v;
+  MOT_TRY(check_track_voxels(c, who, flags, params, &v));
+  if (!d_models || !d_counts || batch < 1 || batch > c->batch || voxel_stride < 0 || (!d_voxels && voxel_stride > 0) || ((size_t)d_voxels & 15) ||
+      (((size_t)d_models | (size_t)d_counts) & 3))
+    return fail(c, MOT_E_ARG, who, ": bad argument");
+  MOT_TRY(check_track_voxels_on(c, who));
+  TrackVoxelScratch s;
+  MOT_TRY(ensure_track_voxels(c, false, &s));
+  TrackModelBuffers a;
+  MOT_TRY(track_model_buffers(c, flags, &a));
+  mot_launch_track_models_plan(a, 0, batch, flags, s.plan, s.plan_counts, c->stream);
+  mot_launch_track_voxels_count(a, 0, batch, flags, v, s.plan, s.res, d_models, reinterpret_cast<int*>(d_counts), c->stream);
+  if (d_voxels && voxel_stride > 0) mot_launch_track_voxels_write(a, 0, batch, flags, v, s.plan, d_voxels, voxel_stride, d_models, c->stream);
+  MOT_HIP(c, hipGetLastError());
+  return MOT_OK;
+}
+
+extern "C" int mot_get_track_model_voxels(mot_ctx* c, int slot, int flags, const mot_voxel_params* params, mot_track_voxel_model* models, int max_models, int* n_models,
+                                          mot_model_voxel* voxels, int voxel_capacity, int* n_voxels) {
+  if (!c) return MOT_E_ARG;
+  MOT_GUARD(c);
+  const char* who = "mot_get_track_model_voxels";
+  TrackVoxelArgs v;
+  MOT_TRY(check_track_voxels(c, who, flags, params, &v));
+  if (slot < 0 || slot >= c->batch || max_models < 0 || voxel_capacity < 0 || !n_models || !n_voxels) return fail(c, MOT_E_ARG, who, ": slot or a capacity out of range, or a null count");
+  MOT_TRY(check_track_voxels_on(c, who));
+  TrackVoxelScratch s;
+  MOT_TRY(ensure_track_voxels(c, true, &s));
+  const int T = c->max_tracks_total;
+  TrackModelBuffers a;
+  MOT_TRY(track_model_buffers(c, flags, &a));
+  // the slot's headers and counts into the staging block; the counts decide what fits the caller's buffers before a voxel moves
+  mot_track_voxel_model* d_mod = reinterpret_cast<mot_track_voxel_model*>(c->d_tv_stage);
+  int* d_cnt = reinterpret_cast<int*>(d_mod + T);
+  mot_launch_track_models_plan(a, slot, 1, flags, s.plan, s.plan_counts, c->stream);
+  mot_launch_track_voxels_count(a, slot, 1, flags, v, s.plan, s.res, d_mod, d_cnt, c->stream);
+  MOT_HIP(c, hipGetLastError());
+  char* pin;
+  MOT_TRY(pinned_scratch(c, 16, &pin));
+  int* h = reinterpret_cast<int*>(pin);
+  MOT_HIP(c, hipMemcpyAsync(h, d_cnt, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  MOT_HIP(c, hipStreamSynchronize(c->stream));
+  const int nv = h[1];
+  if (h[0] < 0 || h[0] > T || nv < 0) return fail(c, MOT_E_STATE, who, ": inconsistent counts");
+  *n_models = T; *n_voxels = nv;
+  if (models && T > max_models) return fail(c, MOT_E_CAPACITY, "more models (max_tracks_total) than the caller's buffer holds");
+  if (voxels && nv > voxel_capacity) return fail(c, MOT_E_CAPACITY, "more voxels than the caller's voxel buffer holds");
+  const bool want_voxels = voxels && nv > 0;
+  if (want_voxels && c->tv_voxels_cap < (size_t)nv) {   // (the stream is drained: nothing reads the old block)
+    MOT_TRY(release(c, &c->d_tv_voxels));
+    c->tv_voxels_cap = 0;
+    const size_t want = ((size_t)nv + 65535) & ~(size_t)65535;
+    MOT_TRY(dev_alloc(c, &c->d_tv_voxels, want * sizeof(mot_model_voxel)));
+    c->tv_voxels_cap = want;
+  }
+  if (want_voxels) {
+    mot_launch_track_voxels_write(a, slot, 1, flags, v, s.plan, c->d_tv_voxels, (long)nv, d_mod, c->stream);
+    MOT_HIP(c, hipGetLastError());
+  }
+  if (models) MOT_HIP(c, hipMemcpyAsync(models, d_mod, (size_t)T * sizeof(mot_track_voxel_model), hipMemcpyDeviceToHost, c->stream));
+  if (want_voxels) MOT_HIP(c, hipMemcpyAsync(voxels, c->d_tv_voxels, (size_t)nv * sizeof(mot_model_voxel), hipMemcpyDeviceToHost, c->stream));
   MOT_HIP(c, hipStreamSynchronize(c->stream));
   return MOT_OK;
 }

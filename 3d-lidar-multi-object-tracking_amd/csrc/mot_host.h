@@ -254,6 +254,11 @@ struct mot_ctx {
   char* d_tm_stage = nullptr;              // mot_get_track_models: one slot's [T headers][2 counts] before they go to the host (allocated at ITS first call)
   mot_accum_point* d_tm_points = nullptr;  // ... and its records: tm_points_cap of them, grown to what a call needs
   size_t tm_points_cap = 0;
+  // mot_export_track_model_voxels_dev / mot_get_track_model_voxels (track_voxels.hip): allocated at the first call, released with the blocks above
+  char* d_tv_scratch = nullptr;            // [batch][T] plan headers (48 bytes), [batch][T] per-model results (48 bytes), [batch][2] the plan's counts
+  char* d_tv_stage = nullptr;              // the getter: one slot's [T headers][2 counts] before they go to the host (allocated at ITS first call)
+  mot_model_voxel* d_tv_voxels = nullptr;  // ... and its voxels: tv_voxels_cap of them, grown to what a call needs
+  size_t tv_voxels_cap = 0;
   std::vector<EgoTf> link_tf;          // [batch] the matrix every slot's boxes took in its last fused call with the tracker, kept while links are on (host side)
   Vec2d* d_cp = nullptr;
   TrackItem* d_items = nullptr;

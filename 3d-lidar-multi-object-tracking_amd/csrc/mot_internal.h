@@ -448,6 +448,20 @@ void mot_launch_track_models_plan(const TrackModelBuffers& a, int first, int bat
 void mot_launch_track_models_transform(const TrackModelBuffers& a, int first, int batch, int flags, mot_accum_point* points, long point_stride, mot_track_model* models,
                                        hipStream_t stream);
 
+// Voxel-thinned object models (track_voxels.hip, mot_export_track_model_voxels_dev): the same rows and records, one record per occupied voxel.
+struct TrackVoxelArgs { float inv_x, inv_y, inv_z; int min_points; };   // 1.0f / leaf, computed once on the host in fp32
+struct TrackVoxelResult {      // 48 bytes, per (stream of the call, row): what the count kernel leaves for the pack kernel
+  int n_voxels, n_outside, n_sparse, n_records;
+  float min_x, min_y, min_z, max_x, max_y, max_z;   // extent of the raw records, as mot_track_model's
+  int reserved[2];
+};
+// plan: [batch][T] headers mot_launch_track_models_plan wrote for the same slots and flags; res: [batch][T] scratch. The count launches (two kernels) give the
+// 64-byte headers and the two counts per slot; the write launch reads those headers back and stores every slot's voxels below voxel_stride.
+void mot_launch_track_voxels_count(const TrackModelBuffers& a, int first, int batch, int flags, const TrackVoxelArgs& v, const mot_track_model* plan, TrackVoxelResult* res,
+                                   mot_track_voxel_model* models, int* counts, hipStream_t stream);
+void mot_launch_track_voxels_write(const TrackModelBuffers& a, int first, int batch, int flags, const TrackVoxelArgs& v, const mot_track_model* plan, mot_model_voxel* voxels,
+                                   long voxel_stride, const mot_track_voxel_model* models, hipStream_t stream);
+
 #ifdef MOT_HIPEMU
 #define MOT_WAVE_SYNC() ((void)__ballot(1))
 #else

@@ -25,10 +25,11 @@
 // back from the caller's block is clamped to what the row holds (count <= kept, first >= 0), and a record is stored only below point_stride. Garbage in a row, a
 // ring or a log cannot produce an address outside the three tables or the caller's point_stride records.
 // Bytes per record: 16 read, 16 written (M1 adds ~4 log2 K bytes per row). Per observation 48 read.
-// Resources (tools/kernel_resources.py): M1 28 VGPRs, 32 bytes of LDS, 8 waves per SIMD; M2 76 VGPRs, 1 280 bytes of LDS, 6 waves per SIMD — the double-precision
+// Resources (tools/kernel_resources.py): M1 28 VGPRs, 32 bytes of LDS, 8 waves per SIMD; M2 74 VGPRs, 1 280 bytes of LDS, 6 waves per SIMD — the double-precision
 // sincos sets M2's register count, not the streaming loop (held to 8 waves per SIMD it spills 48 bytes a lane: not taken); no scratch in either.
 #include "mot_internal.h"
 #include "mot_wave.h"
+#include "mot_track_model.h"
 
 #ifndef MOT_HIPEMU
 #define MOT_TM_BOUNDS(n) __launch_bounds__(n)
@@ -38,34 +39,10 @@
 
 constexpr int kTmPlanBlock = 256, kTmPlanWaves = kTmPlanBlock / 64;
 constexpr int kTmBlock = 64, kTmItems = kTrackModelTile / kTmBlock;   // M2: one wave
-constexpr int kTmObsTile = 64;   // observations in LDS at a time (a power of two: the lower bound halves it)
-static_assert(kTmBlock == 64 && kTrackModelTile % kTmBlock == 0 && (kTmObsTile & (kTmObsTile - 1)) == 0 && kTmObsTile <= kTmBlock, "tile geometry");
+static_assert(kTmBlock == 64 && kTrackModelTile % kTmBlock == 0 && kTmObsTile <= kTmBlock, "tile geometry");
 static_assert(sizeof(mot_track_model) == 48 && sizeof(mot_accum_point) == 16, "include/mot.h documents the sizes");
 
-// what a row says of its two rings, every number inside the tables whatever the row holds
-struct TmRing { int kept, ring0, n_obs, obs0; };
-__device__ __forceinline__ TmRing tm_ring(const mot_accum_row& row, int K, int O) {
-  TmRing g;
-  g.kept = row.total < (unsigned long long)K ? (int)row.total : K;
-  g.ring0 = row.total > (unsigned long long)K ? (int)(row.total & (unsigned long long)(K - 1)) : 0;
-  g.n_obs = row.obs_total < 0 ? 0 : (row.obs_total < O ? row.obs_total : O);
-  g.obs0 = row.obs_total > O ? (row.obs_total & (O - 1)) : 0;
-  return g;
-}
-// first unrolled position in [lo, hi) whose step is not below / is above `step` (hi when none)
-template <bool kAbove>
-__device__ __forceinline__ int tm_search(const mot_accum_point* __restrict__ ring, int ring0, int K, int lo, int hi, int step) {
-  while (lo < hi) {
-    const int mid = (int)(((unsigned)lo + (unsigned)hi) >> 1);
-    const int s = ring[(ring0 + mid) & (K - 1)].step;
-    if (kAbove ? s <= step : s < step) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-// order-preserving integer image of a float (a < b as floats <=> image(a) < image(b) as ints; -0.0 sits right below +0.0)
-__device__ __forceinline__ int tm_image(float v) { const int i = __float_as_int(v); return i ^ ((i >> 31) & 0x7fffffff); }
-__device__ __forceinline__ float tm_float(int i) { return __int_as_float(i ^ ((i >> 31) & 0x7fffffff)); }
-__device__ __forceinline__ bool tm_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+// (tm_ring, tm_search, tm_image / tm_float / tm_finite, the log tile and tm_record, the per-record transform: mot_track_model.h, shared with track_voxels.hip)
 
 // ------------------------------------------------------------------------------------------ M1
 __global__ void MOT_TM_BOUNDS(kTmPlanBlock)
@@ -111,8 +88,7 @@ track_models_plan_kernel(TrackModelBuffers a, int b0, int flags, mot_track_model
 // ------------------------------------------------------------------------------------------ M2
 __global__ void MOT_TM_BOUNDS(kTmBlock)
 track_models_transform_kernel(TrackModelBuffers a, int b0, int flags, mot_accum_point* __restrict__ points, long point_stride, mot_track_model* __restrict__ models) {
-  __shared__ int s_step[kTmObsTile];
-  __shared__ float s_px[kTmObsTile], s_py[kTmObsTile], s_c[kTmObsTile], s_s[kTmObsTile];
+  __shared__ TmObsTile s_obs;
   const int r = blockIdx.x, kb = blockIdx.y, b = b0 + kb, tid = threadIdx.x;
   mot_track_model* __restrict__ mp = models + (long)kb * a.T + r;
   // M1's header of this row (the whole workgroup reads the same words: every exit below is taken by all of it)
@@ -134,15 +110,11 @@ track_models_transform_kernel(TrackModelBuffers a, int b0, int flags, mot_accum_
   for (int t0 = 0; t0 < g.n_obs; t0 += kTmObsTile) {
     const int nt = g.n_obs - t0 < kTmObsTile ? g.n_obs - t0 : kTmObsTile;
     __syncthreads();   // (the previous tile is read)
-    if (tid < nt) {
-      const mot_accum_obs o = log[(g.obs0 + t0 + tid) & (a.O - 1)];
-      s_step[tid] = o.step; s_px[tid] = o.px; s_py[tid] = o.py;
-      if (axes) { double sn, cs; sincos(o.yaw, &sn, &cs); s_c[tid] = (float)cs; s_s[tid] = (float)sn; }   // (one argument reduction for both: 8 VGPRs less than cos + sin)
-    }
+    if (tid < nt) tm_load_obs(s_obs, tid, log[(g.obs0 + t0 + tid) & (a.O - 1)], axes);
     __syncthreads();
     // the tile's records: up to the last one of the tile's last step (the last tile takes what is left)
     int end = count;
-    if (t0 + nt < g.n_obs) end = tm_search<true>(ring, g.ring0, a.K, u0 + pos, u0 + count, s_step[nt - 1]) - u0;
+    if (t0 + nt < g.n_obs) end = tm_search<true>(ring, g.ring0, a.K, u0 + pos, u0 + count, s_obs.step[nt - 1]) - u0;
     for (int i0 = pos; i0 < end; i0 += kTrackModelTile) {
       float4 p[kTmItems];
 #pragma unroll
@@ -154,20 +126,7 @@ track_models_transform_kernel(TrackModelBuffers a, int b0, int flags, mot_accum_
       for (int k = 0; k < kTmItems; k++) {
         const int i = i0 + k * kTmBlock + tid;
         if (i >= end) continue;
-        const int step = __float_as_int(p[k].w);
-        int j = 0;   // the last observation of the tile whose step is not above the point's: the point's own
-#pragma unroll
-        for (int h = kTmObsTile / 2; h >= 1; h >>= 1)
-          if (j + h < nt && s_step[j + h] <= step) j += h;
-        const float dx = p[k].x - s_px[j], dy = p[k].y - s_py[j];
-        float4 q = p[k];
-        if (axes) {
-          const float c = s_c[j], s = s_s[j];
-          q.x = c * dx + s * dy;
-          q.y = c * dy - s * dx;
-        } else {
-          q.x = dx; q.y = dy;
-        }
+        const float4 q = tm_record(s_obs, nt, p[k], axes);
         if (first + i < point_stride) *reinterpret_cast<float4*>(out + first + i) = q;
         if (tm_finite(q.x) && tm_finite(q.y) && tm_finite(q.z)) {
           const int ix = tm_image(q.x), iy = tm_image(q.y), iz = tm_image(q.z);

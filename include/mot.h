@@ -622,6 +622,62 @@ int mot_export_track_models_dev(mot_ctx* ctx, int batch, int flags,
 int mot_get_track_models(mot_ctx* ctx, int slot, int flags, mot_track_model* models, int max_models, int* n_models,
         mot_accum_point* points, int point_capacity, int* n_points);
 
+/* ---------------------------------------------------------------- voxel-thinned object models (additions within ABI v6)
+ * The same models, ONE RECORD PER OCCUPIED VOXEL: a LiDAR scans the same surface at every step, so a raw model is the same few hundred surface points many times
+ * over; here every model is reduced, where it lives, to the centroids and point counts of the cells of a lattice anchored at the track's position (a voxel is the
+ * same piece of the object from call to call). Nothing is launched, written or allocated unless these calls are made; every other entry point gives the bytes it
+ * gives without them.
+ *
+ * mot_export_track_model_voxels_dev(batch, flags, params, ...): rows r = 0 .. T-1 of slots 0 .. batch-1 into block b of the caller's DEVICE buffers:
+ * d_models[b * T + r], d_voxels[b * voxel_stride + ...], d_counts[2 * b] = the slot's models, d_counts[2 * b + 1] = its voxels. Asynchronous on the context stream,
+ * nothing is read back; two calls on the same accumulators give identical bytes (no floating-point atomics, nothing depends on scheduling).
+ *   ROWS, RECORDS: the rows that give a model, the records {x', y', z} that belong to it and their coordinates are those of mot_export_track_models_dev under the
+ *     same flags (MOT_MODEL_AXES, MOT_MODEL_CURRENT), bit for bit: one device function computes the record for both calls.
+ *   CELL of a record, per axis a = x, y, z: inv_a = 1.0f / leaf_a (fp32, once, on the host); t_a = coord_a * inv_a (one fp32 multiplication). The record TAKES PART
+ *     iff its three coordinates are finite and -1024 <= t_x, t_y < 1024 and -512 <= t_z < 512, compared as floats; then i_a = (int)floorf(t_a). Every other record
+ *     is counted in n_outside.
+ *   VOXELS of a model: the distinct cells in ascending (i_z, i_y, i_x); count = the cell's records; a voxel with count < min_points is dropped and counted in
+ *     n_sparse.
+ *   CENTROID: x, y, z = the mean of the cell's records, accumulated in fp64 and rounded once to fp32, (float)(sum / count); the order of the additions is fixed by
+ *     the model's records alone. It lies within [min, max] of the cell's records on every axis, so floorf(c * inv) is the voxel's own cell.
+ *   PACKING: the models of a slot lie back to back in ascending r: `first` of a model = first + count of the previous model, 0 for the first. A slot with more
+ *     voxels than voxel_stride gets the first voxel_stride of them and nothing beyond is written; the headers and d_counts carry the TRUE numbers. d_voxels null
+ *     with voxel_stride 0: headers only.
+ *   HEADER: n_obs, first_step, last_step and the extent are mot_track_model's (the extent is that of the RAW records); n_records = mot_track_model.count;
+ *     sum of the voxels' counts + the records of the dropped voxels = n_records - n_outside.
+ * MOT_E_ARG: a leaf that is not finite or outside [1e-3, 1e3], min_points outside [1, MOT_MODEL_VOXEL_MAX_K], null params, unknown flag bits, batch outside
+ * [1, max_batch], voxel_stride < 0, null d_models / d_counts, d_voxels null with voxel_stride > 0, d_voxels not 16-byte or the others not 4-byte aligned.
+ * MOT_E_STATE: accumulation off or obs_per_track == 0; points_per_track > MOT_MODEL_VOXEL_MAX_K (the message names the limit: a model is sorted in the LDS of one
+ * workgroup; longer rings would need a sort in global memory). Every refusal comes before anything is launched.
+ * mot_get_track_model_voxels(slot, flags, params, ...): the same for ONE slot, to the host (synchronises). *n_models = T and *n_voxels are always delivered; a null
+ * buffer is not filled and not tested; MOT_E_CAPACITY with nothing copied when a buffer that was given is too small; MOT_E_ARG for a slot or capacity out of
+ * range or a null count.
+ * Memory: no voxel is staged — the models are sorted twice, once to count and once to write — so the library's scratch is 96 bytes per row (96 * max_batch *
+ * max_tracks_total + 8 * max_batch bytes: the plan's headers and the per-model counts), beside the latest-step block of the raw export; the getter adds a staging
+ * block of 64 T bytes and one for the slot's voxels, grown on demand. Allocated at the first call, released when accumulation is turned off or its geometry
+ * changes, and by mot_destroy; MOT_E_HIP when that fails, with everything else as it was (the next call resumes).
+ * Kernels (csrc/track_voxels.hip): the raw export's plan kernel, a count kernel and a write kernel (one workgroup per model, a bitonic sort of the model's cells in
+ * LDS) and a pack kernel (one workgroup per stream). Cost: profiles/track_voxels.md (tools/time_track_voxels.py). */
+#define MOT_MODEL_VOXEL_MAX_K 4096          /* largest points_per_track the voxel calls serve */
+typedef struct mot_voxel_params { float leaf_x, leaf_y, leaf_z; int32_t min_points; } mot_voxel_params;   /* 16 bytes */
+typedef struct mot_model_voxel  { float x, y, z; int32_t count; } mot_model_voxel;                        /* 16 bytes */
+typedef struct mot_track_voxel_model {      /* 64 bytes; one per TRACK SLOT, indexed as mot_accum_row / mot_track_model are */
+  int32_t track_id;                          /* -1: no model, every other field 0 */
+  int32_t first, count;                      /* the model's VOXELS in the slot's block (TRUE numbers) */
+  int32_t n_obs, first_step, last_step;      /* as mot_track_model */
+  float   min_x, min_y, min_z, max_x, max_y, max_z;   /* as mot_track_model: extent of the RAW records */
+  int32_t n_records;                         /* raw records of the model = mot_track_model.count */
+  int32_t n_outside;                         /* records that took no part: a non-finite coordinate or a cell outside the lattice */
+  int32_t n_sparse;                          /* occupied voxels dropped for holding fewer than min_points records */
+  int32_t reserved;                          /* 0 */
+} mot_track_voxel_model;
+int mot_export_track_model_voxels_dev(mot_ctx* ctx, int batch, int flags, const mot_voxel_params* params,
+        mot_model_voxel* d_voxels, long voxel_stride,      /* voxels per slot */
+        mot_track_voxel_model* d_models,                    /* [batch][max_tracks_total] */
+        int32_t* d_counts /* [batch][2]: models, voxels — the TRUE numbers */);
+int mot_get_track_model_voxels(mot_ctx* ctx, int slot, int flags, const mot_voxel_params* params,
+        mot_track_voxel_model* models, int max_models, int* n_models, mot_model_voxel* voxels, int voxel_capacity, int* n_voxels);
+
 /* on != 0: the fused entry points send their launch sequence (13 kernels with the tracker) as ONE hipGraph launch, captured once per launch geometry
  * (batch, chunks of the largest frame, tracker on / off, outputs); what changes per call without changing the geometry travels in the
  * device-resident argument block. For contexts somebody waits on frame by frame (one or a few streams): the host's part of a frame
