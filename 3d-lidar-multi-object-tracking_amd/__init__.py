@@ -95,6 +95,15 @@ VOXEL_MODEL_DTYPE = np.dtype([("track_id", "i4"), ("first", "i4"), ("count", "i4
                               ("min", "f4", 3), ("max", "f4", 3), ("n_records", "i4"), ("n_outside", "i4"), ("n_sparse", "i4"), ("reserved", "i4")])
 MODEL_VOXEL_DTYPE = np.dtype([("xyz", "f4", 3), ("count", "i4")])
 assert VOXEL_MODEL_DTYPE.itemsize == 64 and MODEL_VOXEL_DTYPE.itemsize == 16
+# struct mot_scene_cell / mot_scene_header of mot_export_scene_grid_dev / mot_get_scene_grid (rolling static-scene grid, include/mot.h)
+SCENE_CELL_DTYPE = np.dtype([("static_hits", "u4"), ("dynamic_hits", "u4"), ("max_z", "f4"), ("last_seen", "i4")])
+SCENE_HEADER_DTYPE = np.dtype([("origin_i", "i4"), ("origin_j", "i4"), ("step", "i4"), ("size", "i4"), ("n_static", "u4"), ("n_dynamic", "u4"), ("n_outside", "u4"), ("cell", "f4")])
+assert SCENE_CELL_DTYPE.itemsize == 16 and SCENE_HEADER_DTYPE.itemsize == 32
+
+
+class MotSceneParams(C.Structure):
+    """struct mot_scene_params"""
+    _fields_ = [("cell", C.c_float), ("size", C.c_int32)]
 
 
 class MotVoxelParams(C.Structure):
@@ -134,6 +143,7 @@ EXPORTS = (
     "mot_export_track_points_dev", "mot_get_track_points",
     "mot_set_track_accumulation", "mot_accumulate_track_points", "mot_sequence_accumulate_dev", "mot_track_accumulators_dev", "mot_get_accum_rows", "mot_get_track_accumulated",
     "mot_export_track_models_dev", "mot_get_track_models", "mot_export_track_model_voxels_dev", "mot_get_track_model_voxels",
+    "mot_set_scene_grid", "mot_accumulate_scene", "mot_export_scene_grid_dev", "mot_get_scene_grid",
     "mot_gather_unique_id", "mot_gather_create", "mot_gather_contribute", "mot_gather_result", "mot_gather_synchronize", "mot_gather_destroy", "mot_gather_last_error",
 )
 ABI_VERSION = 6
@@ -415,6 +425,40 @@ class Context:
         self._ck(self.lib.mot_get_track_model_voxels(self._h, int(slot), flags, C.byref(p), _vp(models), len(models), C.byref(nm), _vp(vox), len(vox), C.byref(nv)))
         vox = vox[: nv.value]
         return dict(models=models[: nm.value].copy(), xyz=vox["xyz"].copy(), count=vox["count"].copy())
+
+    def set_scene_grid(self, cell, size: int | None = None):
+        """rolling static-scene grid per stream (mot_set_scene_grid): `cell` metres per cell in [0.05, 10], `size` cells per side, a power of two in [64, 2048];
+        set_scene_grid(None): off, memory freed. Needs set_track_links"""
+        if cell is None:
+            self._ck(self.lib.mot_set_scene_grid(self._h, None))
+            self._scene_size = 0
+            return
+        p = MotSceneParams(float(cell), int(size))
+        self._ck(self.lib.mot_set_scene_grid(self._h, C.byref(p)))
+        self._scene_size = int(size)
+
+    def accumulate_scene(self, batch: int):
+        """take the latest fused step of slots 0..batch-1 into their scene grids (asynchronous; once per step): points without owner and points of static-flagged
+        tracks as static hits, every other owned point as a dynamic hit"""
+        self._ck(self.lib.mot_accumulate_scene(self._h, int(batch)))
+
+    def export_scene_grid_dev(self, batch: int, d_cells_ptr: int, cell_stride: int, d_headers_ptr: int):
+        """the grids of slots 0..batch-1, unrolled -> caller's device blocks (mot_export_scene_grid_dev): 16-byte cells d_cells[b * cell_stride + v * size + u]
+        (SCENE_CELL_DTYPE; window offset (u, v) = global cell (origin_i + u, origin_j + v)) and 32-byte headers d_headers[b] (SCENE_HEADER_DTYPE). Asynchronous"""
+        self._ck(self.lib.mot_export_scene_grid_dev(self._h, int(batch), C.c_void_p(d_cells_ptr or None), C.c_long(cell_stride), C.c_void_p(d_headers_ptr or None)))
+
+    def get_scene_grid(self, slot: int = 0, cells: bool = True) -> dict:
+        """one slot's grid on the host (mot_get_scene_grid): header (a SCENE_HEADER_DTYPE record) and cells [size, size] indexed (v, u) (SCENE_CELL_DTYPE;
+        cells=False: the header alone, cells None)"""
+        hdr = np.zeros(1, SCENE_HEADER_DTYPE); n = C.c_int(0)
+        if not cells:
+            self._ck(self.lib.mot_get_scene_grid(self._h, int(slot), None, 0, C.byref(n), _vp(hdr)))
+            return dict(header=hdr[0].copy(), cells=None)
+        self._ck(self.lib.mot_get_scene_grid(self._h, int(slot), None, 0, C.byref(n), None))   # the count alone
+        W = int(round(n.value ** 0.5))
+        out = np.zeros(max(n.value, 1), SCENE_CELL_DTYPE)
+        self._ck(self.lib.mot_get_scene_grid(self._h, int(slot), _vp(out), n.value, C.byref(n), _vp(hdr)))
+        return dict(header=hdr[0].copy(), cells=out[: n.value].reshape(W, W))
 
     def _track_buffer(self, slot, max_tracks):
         """records a call can deliver: one per track EVER created on the stream, which outgrows the number of slots on a long run"""

@@ -440,6 +440,7 @@ extern "C" int mot_reset(mot_ctx* c) {
   MOT_HIP(c, hipMemsetAsync(c->d_nlive, 0, c->batch * sizeof(int), c->stream));
   MOT_HIP(c, hipMemsetAsync(c->d_tflags, 0, c->batch * sizeof(int), c->stream));
   MOT_TRY(accum_restart_slots(c, 0, c->batch));
+  MOT_TRY(scene_restart_slots(c, 0, c->batch));
   c->ego.assign(c->batch, mot_ctx::SlotEgo());
   return MOT_OK;
 }
@@ -946,6 +947,7 @@ extern "C" int mot_set_track_links(mot_ctx* c, int on) {
   on = on ? 1 : 0;
   if (on == c->track_links) return MOT_OK;
   if (!on && c->accum_K) return fail(c, MOT_E_STATE, "mot_set_track_links: the per-track accumulators are on (mot_set_track_accumulation(ctx, 0, 0) first)");
+  if (!on && c->scene_W) return fail(c, MOT_E_STATE, "mot_set_track_links: the scene grid is on (mot_set_scene_grid(ctx, NULL) first)");
   if (on) MOT_TRY(ensure_links(c));   // MOT_E_HIP: the mode stays as it was
   MOT_TRY(drop_graphs(c));   // the link kernel and the owner pointers are part of the launch sequence: graphs captured in the other mode go
   c->track_links = on;

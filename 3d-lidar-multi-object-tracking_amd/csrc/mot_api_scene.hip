@@ -1,0 +1,152 @@
+// mot_api_scene.hip — host side of the C-ABI (include/mot.h), the rolling static-scene grid: the setter and what it owns, the per-slot step counters, the state
+// checks of mot_accumulate_scene, and the two readers. Kernels: scene_grid.hip. Context and helpers: mot_host.h.
+#include "mot_host.h"
+
+// The setter owns the feature's memory: cells, headers, previous origins, the argument block and its ring of page-locked staging blocks are allocated together and
+// released together (off, or another geometry); the getter's staging block, taken at ITS first call, goes with them. (The ring's events stay in the registry until
+// mot_destroy, as those of every ring do.)
+struct SceneBlocks {
+  SceneCell* cells = nullptr; mot_scene_header* hdr = nullptr; SceneWindow* prev = nullptr; char* args = nullptr;
+};
+static int scene_release(mot_ctx* c, SceneBlocks* s) {
+  MOT_TRY(release(c, &s->cells)); MOT_TRY(release(c, &s->hdr)); MOT_TRY(release(c, &s->prev));
+  return release(c, &s->args);
+}
+static size_t scene_arg_bytes(const mot_ctx* c) { return (size_t)c->batch * (sizeof(EgoTf) + sizeof(int)); }   // [batch] matrices, then [batch] step stamps
+static SceneGridBuffers scene_buffers(const mot_ctx* c) {
+  SceneGridBuffers g;
+  g.cells = c->d_sg_cells; g.hdr = c->d_sg_hdr; g.prev = c->d_sg_prev; g.W = c->scene_W; g.log2_W = __builtin_ctz((unsigned)c->scene_W); g.cell = c->scene_cell; g.inv = c->scene_inv;
+  return g;
+}
+static int check_scene_on(mot_ctx* c, const char* who) { return c->scene_W ? MOT_OK : fail(c, MOT_E_STATE, who, ": the scene grid is off (mot_set_scene_grid)"); }
+
+int scene_restart_slots(mot_ctx* c, int first, int n) {
+  if (!c->scene_W) return MOT_OK;
+  const size_t slot_cells = (size_t)c->scene_W * c->scene_W;
+  MOT_HIP(c, hipMemsetAsync(c->d_sg_cells + (size_t)first * slot_cells, 0, (size_t)n * slot_cells * sizeof(SceneCell), c->stream));
+  mot_launch_scene_reset(scene_buffers(c), first, n, c->stream);
+  MOT_HIP(c, hipGetLastError());
+  for (int b = first; b < first + n; b++) { c->scene_step[b] = 0; c->res.scene_taken(b); }
+  return MOT_OK;
+}
+
+// off: nothing may still read the blocks
+static int scene_off(mot_ctx* c) {
+  MOT_HIP(c, hipStreamSynchronize(c->stream));
+  c->scene_W = 0; c->scene_cell = 0.f; c->scene_inv = 0.f;
+  SceneBlocks s = {c->d_sg_cells, c->d_sg_hdr, c->d_sg_prev, c->d_sg_args};
+  c->d_sg_cells = nullptr; c->d_sg_hdr = nullptr; c->d_sg_prev = nullptr; c->d_sg_args = nullptr;
+  MOT_TRY(scene_release(c, &s));
+  MOT_TRY(release(c, &c->sg_ring.base));
+  for (bool& u : c->sg_ring.used) u = false;
+  return release(c, &c->d_sg_stage);
+}
+
+extern "C" int mot_set_scene_grid(mot_ctx* c, const mot_scene_params* p) {
+  if (!c) return MOT_E_ARG;
+  MOT_GUARD(c);
+  const char* who = "mot_set_scene_grid";
+  if (!p) return c->scene_W ? scene_off(c) : MOT_OK;
+  if (!(p->cell >= 0.05f && p->cell <= 10.f)) return fail(c, MOT_E_ARG, who, ": cell must be finite and in [0.05, 10] metres");   // (NaN fails both compares)
+  const int W = p->size;
+  if (W < 64 || W > 2048 || (W & (W - 1))) return fail(c, MOT_E_ARG, who, ": size must be a power of two in [64, 2048]");
+  if (!c->track_links) return fail(c, MOT_E_STATE, who, ": track links are off (mot_set_track_links)");
+  if (W == c->scene_W && p->cell == c->scene_cell) return MOT_OK;
+  // the new blocks first: a failure leaves the mode, an earlier geometry included, as it was
+  const bool had_ring = c->sg_ring.base != nullptr;
+  SceneBlocks s;
+  int rc = dev_alloc(c, &s.cells, (size_t)c->batch * W * W * sizeof(SceneCell));
+  if (!rc) rc = dev_alloc(c, &s.hdr, (size_t)c->batch * sizeof(mot_scene_header));
+  if (!rc) rc = dev_alloc(c, &s.prev, (size_t)c->batch * sizeof(SceneWindow));
+  if (!rc) rc = dev_alloc(c, &s.args, scene_arg_bytes(c));
+  if (!rc) rc = c->sg_ring.create(c, scene_arg_bytes(c));   // (skips what exists: the blocks do not depend on the geometry)
+  if (rc) {
+    const std::string why = c->err;
+    (void)scene_release(c, &s);
+    if (!had_ring) (void)release(c, &c->sg_ring.base);
+    c->err = why;
+    return rc;
+  }
+  if (c->scene_W) {   // another geometry: nothing may still read the old blocks
+    MOT_HIP(c, hipStreamSynchronize(c->stream));
+    SceneBlocks old = {c->d_sg_cells, c->d_sg_hdr, c->d_sg_prev, c->d_sg_args};
+    MOT_TRY(scene_release(c, &old));
+    MOT_TRY(release(c, &c->d_sg_stage));
+  }
+  c->d_sg_cells = s.cells; c->d_sg_hdr = s.hdr; c->d_sg_prev = s.prev; c->d_sg_args = s.args;
+  c->scene_W = W; c->scene_cell = p->cell; c->scene_inv = 1.0f / p->cell;
+  c->scene_step.assign(c->batch, 0);
+  return scene_restart_slots(c, 0, c->batch);   // every grid empty; the steps the slots hold were taken without the feature: the next fused call is the first to be taken
+}
+
+extern "C" int mot_accumulate_scene(mot_ctx* c, int batch) {
+  if (!c) return MOT_E_ARG;
+  MOT_GUARD(c);
+  const char* who = "mot_accumulate_scene";
+  MOT_TRY(check_scene_on(c, who));
+  if (batch < 1 || batch > c->batch) return fail(c, MOT_E_ARG, who, ": batch out of range");
+  for (int b = 0; b < batch; b++) {   // every slot before anything is launched or counted
+    if (!c->track_links || !c->res.point_tracks_valid(b))
+      return fail(c, MOT_E_STATE, who, ": the slot's cloud, boxes and tracker step do not come from one fused call (a stage-wise call took the slot, the tracker was fed from outside, "
+                                       "or no fused call ran the tracker since the links were turned on)");
+    if (c->res.sequence_frame(b)) return fail(c, MOT_E_STATE, who, ": the slots hold the frames of ONE stream (mot_sequence_dev); the scene grid does not support sequence mode");
+    if (c->res.scene_done(b)) return fail(c, MOT_E_STATE, who, ": a slot of the batch was already taken into its grid for its current step, or was reset / loaded since that step");
+  }
+  // the matrices the slots' boxes took and the slots' step stamps, in one stream-ordered copy ahead of the kernels
+  char* raw;
+  MOT_TRY(c->sg_ring.acquire(c, &raw));
+  memcpy(raw, c->link_tf.data(), (size_t)batch * sizeof(EgoTf));
+  memcpy(raw + (size_t)batch * sizeof(EgoTf), c->scene_step.data(), (size_t)batch * sizeof(int));
+  MOT_TRY(c->sg_ring.commit(c, c->d_sg_args, 0, (size_t)batch * (sizeof(EgoTf) + sizeof(int)), c->stream));
+  const EgoTf* d_tf = reinterpret_cast<const EgoTf*>(c->d_sg_args);
+  const int* d_steps = reinterpret_cast<const int*>(d_tf + batch);
+  SceneSplatInput in;
+  in.ids = c->d_point_track; in.elevated = c->d_elev; in.cap = c->cap; in.counts = c->d_counts; in.slot_of = c->d_slot_of; in.out = c->d_tout;
+  in.T = c->max_tracks_total; in.E = c->max_tracks_ever;
+  const SceneGridBuffers g = scene_buffers(c);
+  for (int k0 = 0; k0 < batch;) {   // one launch per run of slots of one cloud layout (launch_track_points, mot_api_tracks.hip)
+    int k1 = k0 + 1;
+    while (k1 < batch && c->res.elev_packed_at(k1) == c->res.elev_packed_at(k0)) k1++;
+    in.elevated_packed = c->res.elev_packed_at(k0) ? 1 : 0;
+    mot_launch_scene_accumulate(g, in, k0, k1 - k0, c->max_points, d_tf + k0, d_steps + k0, c->stream);
+    k0 = k1;
+  }
+  MOT_HIP(c, hipGetLastError());
+  for (int b = 0; b < batch; b++) { c->scene_step[b]++; c->res.scene_taken(b); }
+  return MOT_OK;
+}
+
+extern "C" int mot_export_scene_grid_dev(mot_ctx* c, int batch, mot_scene_cell* d_cells, long cell_stride, mot_scene_header* d_headers) {
+  if (!c) return MOT_E_ARG;
+  MOT_GUARD(c);
+  const char* who = "mot_export_scene_grid_dev";
+  MOT_TRY(check_scene_on(c, who));
+  if (!d_cells || !d_headers || batch < 1 || batch > c->batch || cell_stride < (long)c->scene_W * c->scene_W || ((size_t)d_cells & 15) || ((size_t)d_headers & 3))
+    return fail(c, MOT_E_ARG, who, ": bad argument (null or misaligned block, cell_stride below size^2, batch out of range)");
+  mot_launch_scene_export(scene_buffers(c), 0, batch, d_cells, cell_stride, d_headers, c->stream);
+  MOT_HIP(c, hipGetLastError());
+  return MOT_OK;
+}
+
+extern "C" int mot_get_scene_grid(mot_ctx* c, int slot, mot_scene_cell* cells, int capacity, int* n_cells, mot_scene_header* header) {
+  if (!c) return MOT_E_ARG;
+  MOT_GUARD(c);
+  const char* who = "mot_get_scene_grid";
+  if (slot < 0 || slot >= c->batch || capacity < 0 || !n_cells) return fail(c, MOT_E_ARG, who, ": slot or capacity out of range, or null n_cells");
+  MOT_TRY(check_scene_on(c, who));
+  const size_t n = (size_t)c->scene_W * c->scene_W;
+  *n_cells = (int)n;
+  if (cells && (size_t)capacity < n) return fail(c, MOT_E_CAPACITY, "more cells (size^2) than the caller's buffer holds");
+  char* pin;
+  MOT_TRY(pinned_scratch(c, sizeof(mot_scene_header), &pin));
+  if (cells) {   // the slot alone, unrolled into the staging block; the header comes from the device block either way
+    MOT_TRY(dev_alloc(c, &c->d_sg_stage, n * sizeof(mot_scene_cell)));
+    mot_launch_scene_export(scene_buffers(c), slot, 1, c->d_sg_stage, (long)n, nullptr, c->stream);
+    MOT_HIP(c, hipGetLastError());
+    MOT_HIP(c, hipMemcpyAsync(cells, c->d_sg_stage, n * sizeof(mot_scene_cell), hipMemcpyDeviceToHost, c->stream));
+  }
+  if (header) MOT_HIP(c, hipMemcpyAsync(pin, c->d_sg_hdr + slot, sizeof(mot_scene_header), hipMemcpyDeviceToHost, c->stream));
+  MOT_HIP(c, hipStreamSynchronize(c->stream));
+  if (header) memcpy(header, pin, sizeof(mot_scene_header));
+  return MOT_OK;
+}

@@ -814,7 +814,8 @@ static int clear_tracks(mot_ctx* c, int slot) {
   MOT_HIP(c, hipMemsetAsync(c->d_nt + slot, 0, sizeof(int), c->stream));
   MOT_HIP(c, hipMemsetAsync(c->d_nlive + slot, 0, sizeof(int), c->stream));
   MOT_HIP(c, hipMemsetAsync(c->d_tflags + slot, 0, sizeof(int), c->stream));
-  return accum_restart_slots(c, slot, 1);
+  MOT_TRY(accum_restart_slots(c, slot, 1));
+  return scene_restart_slots(c, slot, 1);
 }
 // forget the TRACKS of one stream, keep its ego dead reckoning (the origin of its global frame)
 extern "C" int mot_reset_tracks_slot(mot_ctx* c, int slot) {
@@ -990,7 +991,8 @@ extern "C" int mot_stream_load(mot_ctx* c, int slot, const void* blob, size_t by
   e.step_ego_yaw = h.step_ego_yaw;
   e.nt = h.nt;
   c->ego[slot] = e;
-  return accum_restart_slots(c, slot, 1);   // (the accumulators are not stream state: the loaded stream's ids start with empty rows)
+  MOT_TRY(accum_restart_slots(c, slot, 1));   // (the accumulators are not stream state: the loaded stream's ids start with empty rows)
+  return scene_restart_slots(c, slot, 1);     // (nor is the scene grid)
 }
 
 // immUkfJpdaf(), OT/tracking/imm_ukf_jpda.cpp:704

@@ -1,5 +1,5 @@
 // mot_host.h — what the host-only translation units of the C-ABI share (mot_api.hip: life cycle, setters, launch sequence, ingest; mot_api_stages.hip: stage-wise calls and
-// getters; mot_api_tracks.hip: tracker, exports, snapshots; mot_gather.hip: the RCCL gather): the context, the record of slot residency, and the ONE owner of every device /
+// getters; mot_api_tracks.hip: tracker, exports, snapshots; mot_api_scene.hip: the scene grid; mot_gather.hip: the RCCL gather): the context, the record of slot residency, and the ONE owner of every device /
 // page-locked allocation, event and captured graph of a context ("ownership", below). No kernel includes this.
 #ifndef MOT_HOST_H_
 #define MOT_HOST_H_
@@ -52,6 +52,7 @@ struct SlotState {
   bool sequence = false;                  // the slot holds FRAME k of one stream (mot_sequence_dev, mot_sequence_accumulate_dev), not stream k's frame:
                                           // mot_accumulate_track_points refuses it
   bool accumulated = false;               // mot_accumulate_track_points has appended the step the slot holds (or a reset / load has put it out of reach): not again
+  bool scene = false;                     // the same for mot_accumulate_scene and the slot's scene grid (every transition that gives the slot a new step starts it over)
 };
 struct Residency {
   std::vector<SlotState> slots;
@@ -97,6 +98,8 @@ struct Residency {
   void step_accumulated(int slot) { slots[slot].accumulated = true; }   // (also: the slot's stream was reset or loaded — the step it holds belongs to ids that are gone)
   // mot_sequence_accumulate_dev has appended the frames the slots hold to stream 0's accumulators (they stay sequence slots: no call appends them again)
   void sequence_accumulated(int frames) { for (int b = 0; b < frames; b++) slots[b].accumulated = true; }
+  bool scene_done(int slot) const { return slots[slot].scene; }
+  void scene_taken(int slot) { slots[slot].scene = true; }   // (also: the slot's stream was reset or loaded)
   bool elev_packed_at(int slot) const { return slots[slot].packed; }
   bool labels_ready(int slot) const { return slots[slot].labels == kLabelsReady; }
   bool cells_usable(int slot) const { return slots[slot].labels == kLabelsFromCells; }
@@ -259,6 +262,16 @@ struct mot_ctx {
   char* d_tv_stage = nullptr;              // the getter: one slot's [T headers][2 counts] before they go to the host (allocated at ITS first call)
   mot_model_voxel* d_tv_voxels = nullptr;  // ... and its voxels: tv_voxels_cap of them, grown to what a call needs
   size_t tv_voxels_cap = 0;
+  // mot_set_scene_grid (scene_grid.hip, mot_api_scene.hip): allocated by the setter, released when it turns the feature off or changes its geometry
+  int scene_W = 0;                         // cells per side; 0: off
+  float scene_cell = 0.f, scene_inv = 0.f; // metres per cell, and 1.0f / cell
+  SceneCell* d_sg_cells = nullptr;         // [batch][W * W], toroidal
+  mot_scene_header* d_sg_hdr = nullptr;    // [batch] the latest step's header
+  SceneWindow* d_sg_prev = nullptr;        // [batch] the origin the cells are laid out for
+  char* d_sg_args = nullptr;               // [batch] sensor -> global matrices, then [batch] ints: the step stamps of an accumulate call
+  PinnedRing sg_ring;                      // blocks of `batch` matrices and `batch` ints
+  mot_scene_cell* d_sg_stage = nullptr;    // mot_get_scene_grid: one slot's unrolled cells before they go to the host (allocated at ITS first call)
+  std::vector<int> scene_step;             // [batch] accepted mot_accumulate_scene calls that covered the slot (the next step stamp)
   std::vector<EgoTf> link_tf;          // [batch] the matrix every slot's boxes took in its last fused call with the tracker, kept while links are on (host side)
   Vec2d* d_cp = nullptr;
   TrackItem* d_items = nullptr;
@@ -404,6 +417,8 @@ TrackBuffers track_buffers(mot_ctx* c, bool fused);
 void prepare_track_args(mot_ctx* c, TrackFrameArgs* targs, int slot, int m, double timestamp, bool run);
 int pinned_scratch(mot_ctx* c, size_t bytes, char** out);
 int accum_restart_slots(mot_ctx* c, int first, int n);   // the accumulators of those streams back to empty, stream-ordered (nothing while the feature is off)
+// mot_api_scene.hip
+int scene_restart_slots(mot_ctx* c, int first, int n);   // the scene grids of those streams back to empty, stream-ordered (nothing while the feature is off)
 // mot_sequence_accumulate_dev's share of the accumulators (the entry point itself is mot_sequence_dev's body, mot_api.hip): links and accumulation on and the scratch
 // there, before anything runs / the capture behind tracker step `frame` / the append of slots 0 .. frames - 1 behind the chain, with the host's bookkeeping
 int seq_accum_ready(mot_ctx* c, const char* who);

@@ -462,6 +462,35 @@ void mot_launch_track_voxels_count(const TrackModelBuffers& a, int first, int ba
 void mot_launch_track_voxels_write(const TrackModelBuffers& a, int first, int batch, int flags, const TrackVoxelArgs& v, const mot_track_model* plan, mot_model_voxel* voxels,
                                    long voxel_stride, const mot_track_voxel_model* models, hipStream_t stream);
 
+// Rolling static-scene grid (scene_grid.hip, mot_set_scene_grid): per stream a W x W torus of 16-byte cells in the tracker's global frame, W a power of two.
+constexpr int kSceneChunk = 2048;          // points per workgroup of the splat kernel
+constexpr int kSceneScrollBlocks = 32;     // workgroups per slot of the scroll kernel (a grid-stride loop over the cells that entered)
+struct SceneCell { unsigned static_hits, dynamic_hits, zkey; int last_seen; };   // as mot_scene_cell, max_z as (unsigned)mot_float_key(z) ^ 0x80000000 (0: none); empty = 16 zero bytes
+struct SceneWindow { int oi, oj, ok, pad; };   // per slot: the origin the cells are laid out for, and whether the latest step's window was valid
+struct SceneGridBuffers {
+  SceneCell* cells;            // [B][W * W], global cell (gi, gj) at (gj & (W - 1)) * W + (gi & (W - 1))
+  mot_scene_header* hdr;       // [B] the latest step's header
+  SceneWindow* prev;           // [B]
+  int W, log2_W;
+  float cell, inv;             // inv = 1.0f / cell, computed once on the host in fp32
+};
+struct SceneSplatInput {
+  const int* ids;              // [B][cap] track id of every elevated point (link.hip)
+  const float4* elevated;      // [B][cap] the elevated cloud in INPUT order
+  int elevated_packed;
+  long cap;
+  const int* counts;           // [B][kCountsStride]
+  const int* slot_of;          // [B][E] TrackBuffers::slot_of
+  const mot_track* out;        // [B][T] TrackBuffers::out
+  int T, E;
+};
+// the step of slots first .. first + batch - 1 (scroll, then splat); tf / steps: [batch] of the launch, every frame's sensor -> global matrix and step stamp
+void mot_launch_scene_accumulate(const SceneGridBuffers& g, const SceneSplatInput& in, int first, int batch, int max_n, const EgoTf* tf, const int* steps, hipStream_t stream);
+// slots first .. first + batch - 1 unrolled into block k = 0 .. batch - 1 of the caller's buffers (out may be null: headers only; headers may be null)
+void mot_launch_scene_export(const SceneGridBuffers& g, int first, int batch, mot_scene_cell* out, long cell_stride, mot_scene_header* headers, hipStream_t stream);
+// headers and origins of slots [first, first + n) back to "no step yet" (the cells are the caller's memset)
+void mot_launch_scene_reset(const SceneGridBuffers& g, int first, int n, hipStream_t stream);
+
 #ifdef MOT_HIPEMU
 #define MOT_WAVE_SYNC() ((void)__ballot(1))
 #else

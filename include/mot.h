@@ -678,6 +678,72 @@ int mot_export_track_model_voxels_dev(mot_ctx* ctx, int batch, int flags, const 
 int mot_get_track_model_voxels(mot_ctx* ctx, int slot, int flags, const mot_voxel_params* params,
         mot_track_voxel_model* models, int max_models, int* n_models, mot_model_voxel* voxels, int voxel_capacity, int* n_voxels);
 
+/* ---------------------------------------------------------------- rolling static-scene grid (additions within ABI v6)
+ * The third use of mot_set_track_links, on the device: a MAP WITHOUT THE MOVING OBJECTS. Per stream a rolling W x W occupancy grid in the tracker's global frame,
+ * centred on the vehicle, updated by one asynchronous call after a fused step; every elevated point of the step is counted in its cell as STATIC or DYNAMIC. The
+ * scene-side twin of the per-track accumulators; independent of them (either, both, in either order after one step). Integer atomics only: the grid is
+ * byte-identical from run to run. Off by default; nothing is launched, written or allocated unless the feature is turned on and called. The reference has no such
+ * output (its createCostMap is a 50 x 50 per-frame cost map without memory and without tracks). Every rule below is fp32 exactly as written.
+ *
+ * mot_set_scene_grid(p): cell finite and in [0.05, 10] metres, size = W a power of two in [64, 2048], else MOT_E_ARG; inv = 1.0f / cell. p = NULL turns the feature
+ * off and frees its memory (draining the context stream). Needs mot_set_track_links on (MOT_E_STATE otherwise), and while the grid is on mot_set_track_links(0)
+ * answers MOT_E_STATE. Allocates max_batch x W^2 x 16 bytes, 48 bytes of headers and 52 of arguments per slot and a ring of page-locked argument blocks; MOT_E_HIP
+ * when that fails, and the mode (an earlier geometry included) stays as it was. The same geometry again changes nothing; another geometry frees the memory and
+ * starts from empty grids. The grid is NOT stream state: mot_stream_save / mot_stream_load do not carry it. mot_reset, mot_reset_slot, mot_reset_tracks_slot and
+ * mot_stream_load empty the grids of the slots they touch and restart those slots' step counters, stream-ordered and without a host synchronisation; the step those
+ * slots hold can then no longer be taken. mot_get_scene_grid's staging block (W^2 x 16 bytes, at its first call) goes with the rest.
+ *
+ * mot_accumulate_scene(batch): takes every elevated point of the latest fused step of slots 0..batch-1. Asynchronous on the context stream, nothing is read back.
+ * Validity is that of mot_accumulate_track_points, tested for every slot before anything is launched; a refused call changes nothing and counts no step:
+ * MOT_E_STATE unless the slot's cloud, boxes and tracker step come from ONE fused call with links on (a stage-wise call since, a tracker step fed from outside),
+ * on the slots of mot_sequence_dev / mot_sequence_accumulate_dev, for a second call on the same step, and after a reset or a load since that step.
+ * STEP STAMP of a slot = the number of accepted mot_accumulate_scene calls that covered the slot before this one (0, 1, ...; a counter of its own, apart from the
+ * accumulators'; counted on the host, it travels with the slots' matrices in one stream-ordered copy).
+ * POINTS: the slot's elevated cloud in input order (MOT_ORDER_ANY included), each under the matrix mot_export_track_points_dev(MOT_FRAME_GLOBAL) applies —
+ * global_from_sensor of mot_sensor_pose read right after the fused call; fp32, left to right, no contraction: g = ((m0 x + m1 y) + m2 z) + m3 per row.
+ * WINDOW: (tx, ty) = entries 3 and 7 of that matrix; ci = floorf(tx * inv), cj = floorf(ty * inv); origin = (ci - W/2, cj - W/2); the window is [origin, origin + W)
+ * on both axes. When tx * inv or ty * inv is not finite or is >= 2^30 in magnitude the step keeps the slot's old origin and clears nothing, every point of the
+ * step counts in n_outside, and the step is still stamped. After the setter, a reset or a load the origin is (0, 0) until the first step with a valid window.
+ * SCROLL: before the adds of a step every cell whose global index lay outside the previous window is empty (16 zero bytes); cells in the intersection of the old
+ * and the new window keep their contents. The first step after the setter, a reset or a load starts from an empty grid. Storage is toroidal — global cell
+ * (gi, gj) lives at (gi & (W - 1), gj & (W - 1)) — so a scroll clears only the columns and rows that entered, or everything when the shift is >= W on an axis.
+ * CELL OF A POINT: t = g * inv per axis, one fp32 product. The point takes part when its global x, y and z are finite, both |t| < 2^30 and (floorf(tx), floorf(ty))
+ * lies in the window; every other point counts in n_outside.
+ * KIND: a point is DYNAMIC when its owner id (mot_get_point_tracks) is >= 0 and that track's mot_track.is_static, as this step left it, is 0; every other point
+ * is STATIC: points without owner and points of static-flagged tracks. A track is flagged static only once it is confirmed and older than 8 steps, so TENTATIVE
+ * AND YOUNG TRACKS COUNT AS DYNAMIC — a parked car shows up as dynamic hits for its first steps and as static hits from then on.
+ * PER CELL: static_hits / dynamic_hits count the points (uint32, wrapping); max_z = the largest global z over the cell's static hits since the cell was last
+ * emptied, 0.0f while static_hits == 0; last_seen = 1 + the stamp of the latest step that hit the cell (0: never).
+ * HEADER: the window's origin; step = the latest stamp, -1 when there was none; n_static, n_dynamic, n_outside of the latest step; size and cell.
+ *
+ * READERS (MOT_E_STATE while the feature is off; valid whenever it is on, whatever the slots hold: before the first step every grid is empty with step = -1).
+ * mot_export_scene_grid_dev writes slot b's grid UNROLLED: the cell at window offset (u, v) — global cell (origin_i + u, origin_j + v) — goes to
+ * d_cells[b * cell_stride + v * W + u], the header to d_headers[b]; asynchronous on the context stream, nothing is read back. MOT_E_ARG for cell_stride < W^2, null
+ * pointers, a d_cells that is not 16-byte aligned (d_headers: 4-byte), or a batch outside [1, max_batch]. mot_get_scene_grid does the same for ONE slot, to
+ * the host (synchronises): *n_cells = W^2 is always delivered; MOT_E_CAPACITY with nothing copied when cells is given and capacity is smaller; a null cells gives
+ * the header alone. A refused call writes nothing into the caller's blocks.
+ *
+ * Kernels (csrc/scene_grid.hip): a scroll kernel (clears what entered, writes the header), the splat kernel (16 bytes read per point and two small gathers per
+ * owned point; one lane per run of neighbouring points of one cell and kind issues the atomics) and the export kernel (32 bytes per cell). Cost:
+ * profiles/scene_grid.md (tools/time_scene_grid.py measures both calls against device-to-device copies of the bytes they read). */
+typedef struct mot_scene_params { float cell; int32_t size; } mot_scene_params;   /* metres per cell; W cells per side */
+typedef struct mot_scene_cell {     /* 16 bytes */
+  uint32_t static_hits, dynamic_hits;
+  float    max_z;                   /* global frame; 0.0f while static_hits == 0 */
+  int32_t  last_seen;               /* 1 + step stamp of the latest hit; 0: never */
+} mot_scene_cell;
+typedef struct mot_scene_header {   /* 32 bytes */
+  int32_t  origin_i, origin_j;      /* global cell index of window offset (0, 0) */
+  int32_t  step;                    /* latest step stamp; -1: none yet */
+  int32_t  size;                    /* W */
+  uint32_t n_static, n_dynamic, n_outside;   /* of the latest step */
+  float    cell;
+} mot_scene_header;
+int mot_set_scene_grid(mot_ctx* ctx, const mot_scene_params* p /* NULL: off, memory freed */);
+int mot_accumulate_scene(mot_ctx* ctx, int batch);
+int mot_export_scene_grid_dev(mot_ctx* ctx, int batch, mot_scene_cell* d_cells, long cell_stride /* cells per slot */, mot_scene_header* d_headers);
+int mot_get_scene_grid(mot_ctx* ctx, int slot, mot_scene_cell* cells, int capacity, int* n_cells, mot_scene_header* header);
+
 /* on != 0: the fused entry points send their launch sequence (13 kernels with the tracker) as ONE hipGraph launch, captured once per launch geometry
  * (batch, chunks of the largest frame, tracker on / off, outputs); what changes per call without changing the geometry travels in the
  * device-resident argument block. For contexts somebody waits on frame by frame (one or a few streams): the host's part of a frame
