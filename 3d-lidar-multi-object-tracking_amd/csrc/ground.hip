@@ -8,10 +8,12 @@
 //   K3 classify_compact_kernel  N pts  -> elevated / ground clouds     (second loop of groundRemove, order preserving)
 //                                         (+ in the fused path the occupancy bit-planes of the cluster stage)
 //
-// HBM traffic per point: K1 reads 16 B, K3 reads 16 B and writes 16 B (+1 B mask) = 48(+1) B — the
-// algorithmic minimum of SURVEY.md §8d: the classification needs the complete grid, so the cloud has to
-// be read twice — plus 2 + 2 B for the polar cell K1 hands to K3 (the cell computation was half of K3's instructions and
-// K3 was bound by them, not by HBM: profiles/r02_ablate_k3.txt). The polar grid (38 KB per frame) lives in L2.
+// HBM traffic per point: K1 reads 16 B, K3 reads 16 B and writes 16 B (+1 B mask) = 48(+1) B with every output — the classification
+// needs the complete grid, so the cloud has to be looked at twice — plus 2 + 2 B for the polar cell K1 hands to K3 (the
+// cell computation was half of K3's instructions and K3 was bound by them, not by HBM: profiles/r02_ablate_k3.txt). The fused path's
+// default K3 (elevated cloud only) does NOT read the whole cloud again: K1 also hands it 0.5 B per point, a conservative max z per
+// aligned group of 8 points (one 128-byte line), and a line none of whose points can be elevated is not loaded — a ground or dropped
+// point leaves K3 as a count and a mask byte only (profiles/ground_skip.md). The polar grid (38 KB per frame) lives in L2.
 //
 // Design notes (MI355X-first, not a translation of the CPU loops):
 //  * K1 has no grid at all and issues NO atomics: beam-major clouds put a cell's points next to each other, so every
@@ -41,11 +43,19 @@
 #ifndef MOT_HIPEMU
 typedef float v4f_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 load_stream(const float4* p) {
-  v4f_t q = __builtin_nontemporal_load((const v4f_t*)p);
+  v4f_t q = __builtin_nontemporal_load((const __attribute__((address_space(1))) v4f_t*)p);   // device memory: a global load, not a flat one (the pointer may come from a FrameLaunch record)
   return make_float4(q.x, q.y, q.z, q.w);
 }
 #else
 __device__ __forceinline__ float4 load_stream(const float4* p) { return *p; }
+#endif
+
+// the compiler forgets what it knows about a register value: an expression of it that has been evaluated before is evaluated again instead of being
+// kept (as twice the registers) across the code in between
+#ifndef MOT_HIPEMU
+#define MOT_FORGET(v) asm volatile("" : "+v"(v))
+#else
+#define MOT_FORGET(v) (void)(v)
 #endif
 
 // Polar cells of a thread's ITEMS points (filterCloud + getCellIndexFromPoints, ground_removal.cpp:46-76). Pass 1 is the
@@ -136,21 +146,6 @@ polar_minz_kernel(MotDevParams p, GroundBuffers g) {
      // loading side it was 8 two-byte stores per thread, 128 bytes per wave instruction).
     static_assert(kGroundItems == 8, "one 16-byte store of 8 cells per thread");
     const long i0 = base + (long)threadIdx.x * kGroundItems;
-#if MOT_CELL_CHANNEL_BYTE
-    // ... and since round 5 one BYTE: the channel (the atan), the compaction kernel recomputes the bin (mot_internal.h): an 8-byte store per thread
-    unsigned char* __restrict__ chan8 = reinterpret_cast<unsigned char*>(g.cell) + (long)b * g.cap;
-    unsigned ch[kGroundItems];
-#pragma unroll
-    for (int j = 0; j < kGroundItems; j++) ch[j] = (int)e[j].x >= 0 ? e[j].x / (unsigned)MOT_NUM_BIN : 0xffu;
-    if (i0 + kGroundItems <= n) {
-      uint2 v;
-      v.x = ch[0] | (ch[1] << 8) | (ch[2] << 16) | (ch[3] << 24); v.y = ch[4] | (ch[5] << 8) | (ch[6] << 16) | (ch[7] << 24);
-      *reinterpret_cast<uint2*>(chan8 + i0) = v;
-    } else {
-#pragma unroll
-      for (int j = 0; j < kGroundItems; j++) if (i0 + j < n) chan8[i0 + j] = (unsigned char)ch[j];
-    }
-#else
     unsigned short* __restrict__ cell16 = g.cell + (long)b * g.cap;
     if (i0 + kGroundItems <= n) {
       uint4 v;
@@ -161,7 +156,14 @@ polar_minz_kernel(MotDevParams p, GroundBuffers g) {
 #pragma unroll
       for (int j = 0; j < kGroundItems; j++) if (i0 + j < n) cell16[i0 + j] = (unsigned short)e[j].x;
     }
-#endif
+    // ... and ONE conservative max z for the 8 points (a 128-byte line of the cloud), 0.5 byte per point: where it classifies as ground under
+    // every cell of the group, the compaction kernel does not load the line at all. Maximum of the ordered keys over the points that have a
+    // cell: a NaN z travels with the largest key and comes out as NaN (no skip: the reference's `z < h + margin` is false for it, the point is
+    // elevated), -0 has become +0 above, a group without a point in a cell gets -inf. Points beyond n are (0,0): no cell.
+    int zmax = mot_float_key(-INFINITY);
+#pragma unroll
+    for (int j = 0; j < kGroundItems; j++) zmax = ((int)e[j].x >= 0 && (int)e[j].y > zmax) ? (int)e[j].y : zmax;
+    if (i0 < n) g.gzmax[(long)b * (g.cap / kGroundItems) + (i0 >> 3)] = mot_key_float(zmax);
   }
   int cnt = 0;   // runs of a real cell among my 8 points
 #pragma unroll
@@ -374,46 +376,7 @@ __device__ __forceinline__ void classify_compact_body(const MotDevParams& p, con
   int cls[kCompactItems];    // MOT_MASK_*
   int rank[kCompactItems];   // rank inside the 64-point tile, among points of the same class
   const bool full = base + kCompactChunk <= n;   // all but the frame's last chunk: no per-point bounds test
-  if (full) {
-#pragma unroll
-    for (int k = 0; k < kCompactItems; k++) pt[k] = load_stream(&in[base + k * kCompactBlock + threadIdx.x]);  // last use of the input cloud
-  } else {
-#pragma unroll
-    for (int k = 0; k < kCompactItems; k++) {
-      long i = base + k * kCompactBlock + threadIdx.x;
-      pt[k] = i < n ? load_stream(&in[i]) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  }
-  {  // polar cell of every point, as the min-z kernel found it (filterCloud + getCellIndexFromPoints + the node's crop)
-#if MOT_CELL_CHANNEL_BYTE
-    // its CHANNEL travels (one byte; 0xff: the point takes no part), the bin is recomputed from x, y with the same guarded expression
-    // (mot_polar_bin_try; the few undecided points go through ONE copy of the exact evaluation, as in the min-z kernel)
-    const unsigned char* __restrict__ chan8 = reinterpret_cast<const unsigned char*>(g.cell) + (long)b * g.cap;
-    unsigned undecided = 0;
-#pragma unroll
-    for (int k = 0; k < kCompactItems; k++) {
-      const long i = base + k * kCompactBlock + threadIdx.x;
-      const unsigned ch = (full || i < n) ? (unsigned)chan8[i] : 0xffu;
-      const int bin = mot_polar_bin_try(p, pt[k].x, pt[k].y);
-      cls[k] = (ch == 0xffu || bin == -1) ? -1 : (bin == -2 ? -2 : (int)ch * MOT_NUM_BIN + bin);
-      if (ch != 0xffu && bin == -2) undecided |= 1u << k;
-      if (ch == 0xffu) cls[k] = -1;
-    }
-    if (__ballot(undecided != 0)) {   // wave-uniform
-      while (undecided) {
-        const int k = __ffs(undecided) - 1;
-        undecided &= undecided - 1;
-        float qx = pt[0].x, qy = pt[0].y;
-#pragma unroll
-        for (int kk = 1; kk < kCompactItems; kk++) { qx = kk == k ? pt[kk].x : qx; qy = kk == k ? pt[kk].y : qy; }
-        const long i = base + k * kCompactBlock + threadIdx.x;
-        const int bin = mot_polar_bin_exact(p, qx, qy);
-        const int r = bin < 0 ? -1 : (int)chan8[i] * MOT_NUM_BIN + bin;
-#pragma unroll
-        for (int kk = 0; kk < kCompactItems; kk++) cls[kk] = kk == k ? r : cls[kk];
-      }
-    }
-#else
+  {  // polar cell of every point, as the min-z kernel found it (filterCloud + getCellIndexFromPoints + the node's crop): 2 bytes, BEFORE the point
     const unsigned short* __restrict__ cell16 = g.cell + (long)b * g.cap;
     if (full) {   // (one 16-byte load per lane + a wave-private LDS transposition instead of these 8 two-byte loads, and the same for
                   // the mask bytes on the way out, measured no faster: 366-369 against 371 us — this kernel waits for HBM, not for its TA)
@@ -427,11 +390,58 @@ __device__ __forceinline__ void classify_compact_body(const MotDevParams& p, con
         cls[k] = c == 0xffffu ? -1 : (int)c;
       }
     }
-#endif
+  }
+  // ... and the conservative max z of the point's aligned group of 8 (the min-z kernel's gzmax: one word per 128-byte line of the cloud, the
+  // same address in 8 neighbouring lanes). Only the elevated-only instantiation looks at it: the ground cloud needs every point.
+  float gz[kCompactItems];
+  if (!kGround) {
+    const float* __restrict__ gzmax = g.gzmax + (long)b * (g.cap / 8);
+    if (full) {
+#pragma unroll
+      for (int k = 0; k < kCompactItems; k++) gz[k] = gzmax[(base + k * kCompactBlock + threadIdx.x) >> 3];
+    } else {
+#pragma unroll
+      for (int k = 0; k < kCompactItems; k++) {
+        const long i = base + k * kCompactBlock + threadIdx.x;
+        gz[k] = i < n ? gzmax[i >> 3] : -INFINITY;
+      }
+    }
   }
   float hgv[kCompactItems];
 #pragma unroll
   for (int k = 0; k < kCompactItems; k++) hgv[k] = hg[cls[k] > 0 ? cls[k] : 0];   // unpredicated independent gathers (L2), all in flight: -inf when the cell is not ground
+  // A ground or dropped point leaves this kernel as a count and a mask byte: its x, y, z, w are not needed. A lane "cannot be elevated" when
+  // its point has no cell, or when the group's max z classifies as ground under the lane's own cell — the SAME expression as the point's
+  // test below, so z <= zmax (float -> double is monotone) makes the implication exact; a NaN zmax never passes. A group whose 8 lanes all
+  // cannot be elevated is not loaded (67 % of the lines of a street frame); an item whose 64 lanes all skip is a scalar branch.
+  unsigned need = 0, wave_needs = 0;   // items whose point I load / of which some lane of the wave loads its point (uniform)
+#pragma unroll
+  for (int k = 0; k < kCompactItems; k++) {
+    const long i = base + k * kCompactBlock + threadIdx.x;
+    if (kGround) { if (full || i < n) need |= 1u << k; }
+    else {
+      const bool cannot = cls[k] < 0 || ((double)gz[k] < (double)hgv[k] + p.ground_margin);   // (lanes beyond n have no cell)
+      const unsigned long long bc = __ballot(cannot);
+      const bool group_skips = ((bc >> (lane & 56)) & 0xffull) == 0xffull;
+      if (!group_skips && (full || i < n)) need |= 1u << k;
+      if (bc != ~0ull) wave_needs |= 1u << k;
+      // (the eight fp64 thresholds, kept from here to the points' own test below, cost 8 registers more than the eight floats and a wave per SIMD)
+      MOT_FORGET(hgv[k]);
+      if (group_skips) hgv[k] = INFINITY;   // not loaded: ground or dropped by the cell alone — the zero that stands for the point is below this threshold
+    }
+  }
+  // the loads, back to back, behind ALL the decisions
+#pragma unroll
+  for (int k = 0; k < kCompactItems; k++) {
+    const long i = base + k * kCompactBlock + threadIdx.x;
+    pt[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (kGround) {
+      if (full) pt[k] = load_stream(&in[i]);
+      else if ((need >> k) & 1u) pt[k] = load_stream(&in[i]);
+    } else if ((wave_needs >> k) & 1u) {   // scalar branch
+      if ((need >> k) & 1u) pt[k] = load_stream(&in[i]);  // last use of the input cloud
+    }
+  }
   const unsigned long long below = (1ull << lane) - 1ull;
   unsigned wave_has_elevated = 0;   // items whose 64 points include an elevated one (wave-uniform)
 #pragma unroll

@@ -314,6 +314,7 @@ static int create_impl(mot_ctx* c) {
   MOT_TRY(dev_zeroed(c, &c->d_pair_count, B * c->max_chunks * sizeof(int)));
   MOT_TRY(dev_alloc(c, &c->d_hg, B * MOT_POLAR_CELLS * sizeof(float)));
   MOT_TRY(dev_alloc(c, &c->d_cell, B * N * sizeof(unsigned short)));
+  MOT_TRY(dev_alloc(c, &c->d_gzmax, B * (N / 8) * sizeof(float)));   // (cap is a multiple of 64)
   MOT_TRY(dev_zeroed(c, &c->d_desc, B * c->max_chunks * sizeof(unsigned long long)));
   MOT_TRY(dev_zeroed(c, &c->d_ticket, B * sizeof(int)));
   MOT_TRY(dev_alloc(c, &c->d_elev, B * N * sizeof(float4)));
@@ -460,7 +461,7 @@ GroundBuffers ground_buffers(mot_ctx* c, const float4* in, long stride, bool wan
   GroundBuffers g;
   g.launch = nullptr;
   g.epoch = c->epoch;
-  g.in = in; g.in_stride = stride; g.n = c->d_n; g.pairs = c->d_pairs; g.pair_count = c->d_pair_count; g.hg = c->d_hg; g.cell = c->d_cell; g.desc = c->d_desc;
+  g.in = in; g.in_stride = stride; g.n = c->d_n; g.pairs = c->d_pairs; g.pair_count = c->d_pair_count; g.hg = c->d_hg; g.cell = c->d_cell; g.gzmax = c->d_gzmax; g.desc = c->d_desc;
   g.ticket = c->d_ticket; g.elevated = c->d_elev; g.elevated_packed = 0; g.ground = c->d_ground; g.mask = want_mask ? c->d_mask : nullptr;
   g.counts = c->d_counts; g.cap = c->cap; g.max_chunks = c->max_chunks;
   g.occ_list = planes ? c->d_occ_list : nullptr; g.occ_count = planes ? c->d_occ_count : nullptr; g.occ_chunks = c->occ_chunks;

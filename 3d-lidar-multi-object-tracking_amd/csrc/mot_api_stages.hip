@@ -564,6 +564,10 @@ extern "C" int mot_debug_copy(mot_ctx* c, int which, int slot, void* dst, size_t
   else if (which == 11) src = c->d_tboxes + (size_t)slot * kMaxBoxesPerFrame * 24;
   else if (which == 12) src = reinterpret_cast<const long long*>(c->d_items) + (size_t)slot * 32;   // -DMOT_DBG_STREAM_TIMING builds: phase clocks of track_step_stream_kernel
   else if (which == 13) src = c->d_cluster_gstart + (size_t)slot * (kMaxClusters + 1);
+  else if (which == 14) src = c->d_elev + (size_t)slot * c->cap;    // as the last compaction left it: 12-byte points behind the fused path's default, float4 records otherwise
+  else if (which == 15) src = c->d_mask + (size_t)slot * c->cap;
+  else if (which == 16) src = c->d_gzmax + (size_t)slot * (c->cap / 8);
+  else if (which == 17) src = c->d_cell + (size_t)slot * c->cap;
   else return MOT_E_ARG;
   MOT_HIP(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
   MOT_HIP(c, hipStreamSynchronize(c->stream));

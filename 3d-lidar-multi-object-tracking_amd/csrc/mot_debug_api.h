@@ -11,7 +11,9 @@ extern "C" {
 /* raw copy of a per-slot device array to the host (which: 0 box candidates, 1 cluster statistics,
  * 3 polygon pool, 5 cluster-sorted index, 7 cluster starts, 8 pixels, 9 (tile, cluster) groups, 10 polar thresholds hGround,
  * 11 the fused path's boxes in the global frame (the tracker's input), 13 first (tile, cluster) group of every cluster: entry [num_cluster] is the
- * frame's group count as the label kernel counted it) */
+ * frame's group count as the label kernel counted it, 14 the elevated cloud and 15 the mask bytes exactly as the last compaction kernel left them (no re-run, unlike
+ * mot_get_ground: what the elevated-only instantiation itself wrote; the cloud is 12-byte points behind the fused path's default outputs), 16 the min-z kernel's max z per
+ * aligned group of 8 input points, 17 its polar cell per input point (0xffff: none)) */
 int mot_debug_copy(mot_ctx* ctx, int which, int slot, void* dst, size_t bytes);
 /* the context's device-side parameter block (MotDevParams, mot_internal.h; bytes >= 512 is enough): what the on-device sweeps of the guarded
  * fast paths (tests/devcheck/sweep.hip -> libmot_sweep.so: test infrastructure, not in this library) are run with */

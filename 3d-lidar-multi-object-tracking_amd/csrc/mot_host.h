@@ -149,6 +149,7 @@ struct mot_ctx {
   int* d_pair_count = nullptr;
   float* d_hg = nullptr;
   unsigned short* d_cell = nullptr;
+  float* d_gzmax = nullptr;
   unsigned long long* d_desc = nullptr;
   int* d_ticket = nullptr;
   float4* d_elev = nullptr;

@@ -100,8 +100,9 @@ struct GroundBuffers {
   const int* n;            // [B] points per frame (device)
   uint2* pairs;            // [B][max_chunks][kGroundChunk] {polar cell, ordered-int key of a partial min z}
   int* pair_count;         // [B][max_chunks] entries each workgroup of the min-z kernel produced
-  unsigned short* cell;    // [B][cap] polar cell of every point (0xffff: takes no part), written by the min-z kernel, read by the compaction kernel —
-                           // or, MOT_CELL_CHANNEL_BYTE (default): one BYTE per point in the same allocation, the point's polar channel (0xff: takes no part)
+  unsigned short* cell;    // [B][cap] polar cell of every point (0xffff: takes no part), written by the min-z kernel, read by the compaction kernel
+  float* gzmax;            // [B][cap / 8] per aligned group of 8 points (a 128-byte line of the cloud): the largest z among its points that have a cell (+-0 as +0; NaN
+                           // if one of them has a NaN z; -inf if none has a cell), written by the min-z kernel; the elevated-only compaction skips lines by it
   float* hg;               // [B][9600] hGround of ground cells, -inf for non-ground cells
   unsigned long long* desc;  // [B][max_chunks]
   int* ticket;             // [B], zero between launches (the workgroup drawing the last ticket re-arms it)
@@ -660,15 +661,9 @@ MOT_HD int mot_polar_cell_fast(const MotDevParams& p, float x, float y, float di
   return cell;
 }
 
-// ---- the BIN alone (round 5). The min-z kernel hands the compaction kernel one byte per point — the point's polar CHANNEL, whose atan is the
-// expensive half of the cell — and the compaction kernel recomputes the bin from x, y (a square root) instead of reading a two-byte cell:
-// one byte less written and one less read per input point (0.12 of the 3.6 GB a 512-frame launch sequence moves). Both kernels evaluate the bin
-// with the SAME guarded expression, so they agree by construction: where the guard holds the estimate's floor is the exact floor (the
-// claim of mot_polar_cell_fast, swept on the device with the channel guard switched off: tests/devcheck/sweep.hip what = 2), elsewhere
-// both take the exact evaluation below.
-#ifndef MOT_CELL_CHANNEL_BYTE
-#define MOT_CELL_CHANNEL_BYTE 1
-#endif
+// ---- the BIN alone. Round 5's compaction kernel read one byte per point (the polar channel) and recomputed the bin from x, y with these; since
+// it decides from the cell and the group's max z whether to load a point AT ALL (ground.hip), the whole 2-byte cell travels again and no kernel
+// calls them. Kept for the device sweeps of the guard with the channel switched off (tests/devcheck/sweep.hip what = 2, primitives.hip).
 MOT_HD int mot_polar_bin_exact(const MotDevParams& p, float x, float y) {   // the bin of mot_polar_cell_exact (same expressions), -1: outside rMin..rMax
   float distance = sqrtf(x * x + y * y);
   if (distance <= p.r_min || distance >= p.r_max) return -1;

@@ -25,7 +25,7 @@ EXPERIMENTS = {
     "k3_no_mask": [("ground.hip", "    if (mask) {\n      if (full) {", "    if (false) {\n      if (full) {")],
     "k3_no_ground_store": [("ground.hip", "    if (cls[k] != MOT_MASK_DROPPED) dst[at] = pt[k];", "    if (is_e) dst[at] = pt[k];")],
     "k3_no_stores": [("ground.hip", "    if (cls[k] != MOT_MASK_DROPPED) dst[at] = pt[k];", "    if (at == -12345) dst[at] = pt[k];")],
-    "k3_plain_loads": [("ground.hip", "pt[k] = load_stream(&in[base + k * kCompactBlock + threadIdx.x]);  // last use of the input cloud", "pt[k] = in[base + k * kCompactBlock + threadIdx.x];")],
+    "k3_plain_loads": [("ground.hip", "pt[k] = load_stream(&in[i]);  // last use of the input cloud", "pt[k] = in[i];")],
     "k3_cheap_cell": [("ground.hip", "    int c = mot_polar_cell_try(p, pt[k].x, pt[k].y);", "    int c = ((int)(pt[k].x * 0.5f) & 63) * MOT_NUM_BIN + ((int)(pt[k].y * 0.5f) & 63);")],
     # ---- LDS footprints of the low-occupancy kernels (do they keep other contexts' kernels off their CUs?)
     "rect_small_lds": [("box.hip", "  __shared__ int s_in[kMaxHullIn + 2];                        // candidate points (x | y << 16), sorted by (x,y)", "  __shared__ int s_in[512];"),
