@@ -143,11 +143,12 @@ EXPORTS = (
     "mot_export_track_points_dev", "mot_get_track_points",
     "mot_set_track_accumulation", "mot_accumulate_track_points", "mot_sequence_accumulate_dev", "mot_track_accumulators_dev", "mot_get_accum_rows", "mot_get_track_accumulated",
     "mot_export_track_models_dev", "mot_get_track_models", "mot_export_track_model_voxels_dev", "mot_get_track_model_voxels",
-    "mot_set_scene_grid", "mot_accumulate_scene", "mot_export_scene_grid_dev", "mot_get_scene_grid",
+    "mot_set_scene_grid", "mot_accumulate_scene", "mot_export_scene_grid_dev", "mot_get_scene_grid", "mot_sequence_products_dev",
     "mot_gather_unique_id", "mot_gather_create", "mot_gather_contribute", "mot_gather_result", "mot_gather_synchronize", "mot_gather_destroy", "mot_gather_last_error",
 )
 ABI_VERSION = 6
 OUT_GROUND, OUT_MASK, OUT_LABELS = 1, 2, 4
+SEQ_ACCUMULATE, SEQ_SCENE = 1, 2   # mot_sequence_products_dev's product bits
 
 _libs: dict[str, C.CDLL] = {}
 
@@ -585,6 +586,18 @@ class Context:
         assert len(ts) == len(ev) == len(ey) == K
         self._ck(self.lib.mot_sequence_accumulate_dev(self._h, C.c_void_p(d_ptr), C.c_long(frame_stride_floats), _vp(n), K, _vp(ts), _vp(ev), _vp(ey),
                                                       C.c_void_p(d_tracks_ptr or None), int(max_per_frame), C.c_void_p(d_counts_ptr or None)))
+
+    def sequence_products_dev(self, d_ptr: int, frame_stride_floats: int, n_points, timestamps, ego_v, ego_yaw, d_tracks_ptr: int = 0,
+                              max_per_frame: int = 0, d_counts_ptr: int = 0, accumulate: bool = False, scene: bool = False, products: int | None = None):
+        """sequence_dev with products taken from every frame in the same asynchronous call (mot_sequence_products_dev): accumulate = stream 0's per-track
+        accumulators (as sequence_accumulate_dev), scene = stream 0's scene grid — what len(n_points) rounds of frames_dev(batch 1) + accumulate_scene(1) leave
+        in slot 0, byte for byte. products: the raw bit set instead of the two flags."""
+        n = np.ascontiguousarray(n_points, np.int32); K = len(n)
+        ts = np.ascontiguousarray(timestamps, np.float64); ev = np.ascontiguousarray(ego_v, np.float64); ey = np.ascontiguousarray(ego_yaw, np.float64)
+        assert len(ts) == len(ev) == len(ey) == K
+        bits = int(products) if products is not None else (SEQ_ACCUMULATE if accumulate else 0) | (SEQ_SCENE if scene else 0)
+        self._ck(self.lib.mot_sequence_products_dev(self._h, C.c_void_p(d_ptr), C.c_long(frame_stride_floats), _vp(n), K, _vp(ts), _vp(ev), _vp(ey),
+                                                    C.c_void_p(d_tracks_ptr or None), int(max_per_frame), C.c_void_p(d_counts_ptr or None), bits))
 
     def get_ground(self, slot: int = 0, n_hint: int | None = None, want_clouds: bool = True):
         """n_hint: number of input points of the frame (length of the returned mask); the buffers are sized by max_points"""

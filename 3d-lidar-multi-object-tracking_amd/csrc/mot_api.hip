@@ -692,14 +692,16 @@ extern "C" int mot_frames_dev(mot_ctx* c, const float* d_xyzw, long frame_stride
 // ground -> cluster -> box as ONE batch (slot k = frame k: the launches a batch of K streams would get), and only the tracker — sequential
 // by nature, imm_ukf_jpda.cpp:704-1112 carries targets_ from frame to frame — runs K steps, chained on the device, each reading frame
 // k's boxes where the box stage left them (slot k) and stream 0's track state. No host synchronisation anywhere.
-static int sequence_frames(mot_ctx* c, const char* who, bool accumulate, const float* d_xyzw, long frame_stride, const int* n_points, int frames,
+static int sequence_frames(mot_ctx* c, const char* who, int products, const float* d_xyzw, long frame_stride, const int* n_points, int frames,
                            const double* timestamps, const double* ego_v, const double* ego_yaw, void* d_tracks, int max_per_frame, int32_t* d_counts) {
   MOT_TRY(check_frames_args(c, d_xyzw, frame_stride, n_points, frames, 1, timestamps, ego_v, ego_yaw));
   if ((d_tracks != nullptr) != (d_counts != nullptr) || (d_tracks && max_per_frame < 1)) return fail(c, MOT_E_ARG, who, ": d_tracks and d_counts go together, max_per_frame >= 1");
-  if (accumulate) {   // every refusal before the first state change: the tracker has not stepped, nothing has run
+  const bool accumulate = (products & MOT_SEQ_ACCUMULATE) != 0, scene = (products & MOT_SEQ_SCENE) != 0;
+  if (products) {   // every refusal before the first state change: the tracker has not stepped, nothing has run
     int max_n;
     MOT_TRY(check_batch(c, n_points, frames, frame_stride / 4, false, nullptr, &max_n));
-    MOT_TRY(seq_accum_ready(c, who));
+    if (accumulate) MOT_TRY(seq_accum_ready(c, who));
+    if (scene) MOT_TRY(seq_scene_ready(c, who, frames));
   }
   MOT_TRY(set_batch(c, n_points, frames, (const float4*)d_xyzw, frame_stride / 4, false));
   MOT_TRY(next_epoch(c));
@@ -716,6 +718,7 @@ static int sequence_frames(mot_ctx* c, const char* who, bool accumulate, const f
     if (tb.owner) { tb.owner += (long)k * kMaxBoxesPerFrame; tb.owner_n += k; }
     mot_launch_track(tb, 1, c->stream, false);
     if (accumulate) seq_accum_capture(c, k);   // the id -> slot map and the records of step k, before step k + 1 moves them
+    if (scene) seq_scene_capture(c, k);        // ... and which ids of the frame step k left flagged static
     if (d_tracks) mot_launch_export_tracks(tb, 1, reinterpret_cast<mot_track*>(d_tracks) + (long)k * max_per_frame, max_per_frame, reinterpret_cast<int*>(d_counts) + k, c->stream);
   }
   if (c->track_links) {   // every frame's points against its own owner row, in one launch behind the last step
@@ -724,14 +727,15 @@ static int sequence_frames(mot_ctx* c, const char* who, bool accumulate, const f
     mot_launch_point_tracks(c->dp, cb, c->d_owner, K, max_n, c->d_point_track, c->cap, nullptr, c->stream);
   }
   MOT_HIP(c, hipGetLastError());
-  return accumulate ? seq_accum_append(c, K, max_n) : MOT_OK;
+  if (accumulate) MOT_TRY(seq_accum_append(c, K, max_n));
+  return scene ? seq_scene_append(c, K, max_n) : MOT_OK;
 }
 extern "C" int mot_sequence_dev(mot_ctx* c, const float* d_xyzw, long frame_stride, const int* n_points, int frames,
                                 const double* timestamps, const double* ego_v, const double* ego_yaw,
                                 void* d_tracks, int max_per_frame, int32_t* d_counts) {
   if (!c) return MOT_E_ARG;
   MOT_GUARD(c);
-  return sequence_frames(c, "mot_sequence_dev", false, d_xyzw, frame_stride, n_points, frames, timestamps, ego_v, ego_yaw, d_tracks, max_per_frame, d_counts);
+  return sequence_frames(c, "mot_sequence_dev", 0, d_xyzw, frame_stride, n_points, frames, timestamps, ego_v, ego_yaw, d_tracks, max_per_frame, d_counts);
 }
 // the same call, and every frame appended to stream 0's per-track accumulators behind the chain (mot_api_tracks.hip: seq_accum_*; kernels: track_accum_seq.hip)
 extern "C" int mot_sequence_accumulate_dev(mot_ctx* c, const float* d_xyzw, long frame_stride, const int* n_points, int frames,
@@ -739,7 +743,17 @@ extern "C" int mot_sequence_accumulate_dev(mot_ctx* c, const float* d_xyzw, long
                                            void* d_tracks, int max_per_frame, int32_t* d_counts) {
   if (!c) return MOT_E_ARG;
   MOT_GUARD(c);
-  return sequence_frames(c, "mot_sequence_accumulate_dev", true, d_xyzw, frame_stride, n_points, frames, timestamps, ego_v, ego_yaw, d_tracks, max_per_frame, d_counts);
+  return sequence_frames(c, "mot_sequence_accumulate_dev", MOT_SEQ_ACCUMULATE, d_xyzw, frame_stride, n_points, frames, timestamps, ego_v, ego_yaw, d_tracks, max_per_frame, d_counts);
+}
+// the same call with a set of products: MOT_SEQ_ACCUMULATE as above, MOT_SEQ_SCENE every frame into stream 0's scene grid (mot_api_scene.hip: seq_scene_*; kernels:
+// scene_grid_seq.hip), both, or none
+extern "C" int mot_sequence_products_dev(mot_ctx* c, const float* d_xyzw, long frame_stride, const int* n_points, int frames,
+                                         const double* timestamps, const double* ego_v, const double* ego_yaw,
+                                         void* d_tracks, int max_per_frame, int32_t* d_counts, int products) {
+  if (!c) return MOT_E_ARG;
+  MOT_GUARD(c);
+  if (products & ~(MOT_SEQ_ACCUMULATE | MOT_SEQ_SCENE)) return fail(c, MOT_E_ARG, "mot_sequence_products_dev: unknown product bit");
+  return sequence_frames(c, "mot_sequence_products_dev", products, d_xyzw, frame_stride, n_points, frames, timestamps, ego_v, ego_yaw, d_tracks, max_per_frame, d_counts);
 }
 
 static int ensure_copy_path(mot_ctx* c) {

@@ -12,6 +12,11 @@ static int scene_release(mot_ctx* c, SceneBlocks* s) {
   MOT_TRY(release(c, &s->cells)); MOT_TRY(release(c, &s->hdr)); MOT_TRY(release(c, &s->prev));
   return release(c, &s->args);
 }
+// what mot_sequence_products_dev(MOT_SEQ_SCENE) took at its first call: both blocks or neither (the caller has drained the stream)
+static int seq_scene_release(mot_ctx* c) {
+  MOT_TRY(release(c, &c->d_sgs_win));
+  return release(c, &c->d_sgs_static);
+}
 static size_t scene_arg_bytes(const mot_ctx* c) { return (size_t)c->batch * (sizeof(EgoTf) + sizeof(int)); }   // [batch] matrices, then [batch] step stamps
 static SceneGridBuffers scene_buffers(const mot_ctx* c) {
   SceneGridBuffers g;
@@ -39,6 +44,7 @@ static int scene_off(mot_ctx* c) {
   MOT_TRY(scene_release(c, &s));
   MOT_TRY(release(c, &c->sg_ring.base));
   for (bool& u : c->sg_ring.used) u = false;
+  MOT_TRY(seq_scene_release(c));
   return release(c, &c->d_sg_stage);
 }
 
@@ -71,6 +77,7 @@ extern "C" int mot_set_scene_grid(mot_ctx* c, const mot_scene_params* p) {
     MOT_HIP(c, hipStreamSynchronize(c->stream));
     SceneBlocks old = {c->d_sg_cells, c->d_sg_hdr, c->d_sg_prev, c->d_sg_args};
     MOT_TRY(scene_release(c, &old));
+    MOT_TRY(seq_scene_release(c));
     MOT_TRY(release(c, &c->d_sg_stage));
   }
   c->d_sg_cells = s.cells; c->d_sg_hdr = s.hdr; c->d_sg_prev = s.prev; c->d_sg_args = s.args;
@@ -89,7 +96,8 @@ extern "C" int mot_accumulate_scene(mot_ctx* c, int batch) {
     if (!c->track_links || !c->res.point_tracks_valid(b))
       return fail(c, MOT_E_STATE, who, ": the slot's cloud, boxes and tracker step do not come from one fused call (a stage-wise call took the slot, the tracker was fed from outside, "
                                        "or no fused call ran the tracker since the links were turned on)");
-    if (c->res.sequence_frame(b)) return fail(c, MOT_E_STATE, who, ": the slots hold the frames of ONE stream (mot_sequence_dev); the scene grid does not support sequence mode");
+    if (c->res.sequence_frame(b)) return fail(c, MOT_E_STATE, who, ": the slots hold the frames of ONE stream (mot_sequence_dev); mot_sequence_products_dev(MOT_SEQ_SCENE) takes a drive's frames into "
+                                                                              "the grid inside the sequence call");
     if (c->res.scene_done(b)) return fail(c, MOT_E_STATE, who, ": a slot of the batch was already taken into its grid for its current step, or was reset / loaded since that step");
   }
   // the matrices the slots' boxes took and the slots' step stamps, in one stream-ordered copy ahead of the kernels
@@ -113,6 +121,49 @@ extern "C" int mot_accumulate_scene(mot_ctx* c, int batch) {
   }
   MOT_HIP(c, hipGetLastError());
   for (int b = 0; b < batch; b++) { c->scene_step[b]++; c->res.scene_taken(b); }
+  return MOT_OK;
+}
+
+// ---------------------------------------------------------------------------------------- the grid fed by sequence mode (scene_grid_seq.hip)
+// mot_sequence_products_dev with MOT_SEQ_SCENE is mot_sequence_dev's body (mot_api.hip) with these three hooks. The scratch of the feature's own — 32 bytes per
+// frame for the windows and one bit per track id and frame for the kinds — is taken at the first call, both blocks or neither (a failure leaves the live allocations
+// as they were), and goes with the grid.
+static SceneSeqBuffers seq_scene_buffers(const mot_ctx* c) {
+  SceneSeqBuffers s;
+  s.win = c->d_sgs_win; s.is_static = c->d_sgs_static; s.words = (c->max_tracks_ever + 31) / 32; s.step0 = c->scene_step[0];
+  return s;
+}
+int seq_scene_ready(mot_ctx* c, const char* who, int frames) {
+  MOT_TRY(check_scene_on(c, who));
+  if (!c->track_links) return fail(c, MOT_E_STATE, who, ": track links are off (mot_set_track_links)");
+  const size_t row_bytes = (size_t)((c->max_tracks_ever + 31) / 32) * sizeof(unsigned);
+  if (!c->d_sgs_win || !c->d_sgs_static) {
+    int rc = dev_alloc(c, &c->d_sgs_win, ((size_t)c->batch + 1) * sizeof(SceneSeqFrame));
+    if (!rc) rc = dev_alloc(c, &c->d_sgs_static, (size_t)c->batch * row_bytes);
+    if (rc) {
+      const std::string why = c->err;
+      (void)seq_scene_release(c);
+      c->err = why;
+      return rc;
+    }
+  }
+  // the captures set bits with an OR: every frame's row starts from zero (scratch of the call's own: nothing anybody reads if the call is refused after this)
+  MOT_HIP(c, hipMemsetAsync(c->d_sgs_static, 0, (size_t)frames * row_bytes, c->stream));
+  return MOT_OK;
+}
+void seq_scene_capture(mot_ctx* c, int frame) {
+  mot_launch_scene_seq_capture(c->d_counts, c->d_owner, c->d_slot_of, c->d_tout, c->max_tracks_total, c->max_tracks_ever, seq_scene_buffers(c), frame, c->stream);
+}
+int seq_scene_append(mot_ctx* c, int frames, int max_n) {
+  SceneSplatInput in;
+  in.ids = c->d_point_track; in.elevated = c->d_elev; in.cap = c->cap; in.counts = c->d_counts; in.slot_of = nullptr; in.out = nullptr;
+  in.T = c->max_tracks_total; in.E = c->max_tracks_ever;
+  in.elevated_packed = c->res.elev_packed_at(0) ? 1 : 0;   // (one fused call filled the slots: one layout)
+  // frame k's matrix is entry k of the call's own argument block (what link_tf[k] keeps on the host): later calls rewrite it behind these kernels, stream-ordered
+  mot_launch_scene_sequence(scene_buffers(c), in, seq_scene_buffers(c), frames, max_n, c->d_ego, c->stream);
+  MOT_HIP(c, hipGetLastError());
+  c->scene_step[0] += frames;   // (a frame refused for capacity has no points to add and counts)
+  c->res.sequence_scene_taken(frames);
   return MOT_OK;
 }
 

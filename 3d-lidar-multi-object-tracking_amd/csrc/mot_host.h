@@ -49,8 +49,8 @@ struct SlotState {
   bool regrouped = false;                 // the box stage ran in MOT_ORDER_ANY: its products (groups, cluster order, first / extreme point indices) index the slot's
                                           // cluster-ordered COPY of the cloud, not the cloud itself. Meaningful while `boxes`; every reader that walks clusters asks.
   LinkState links = kLinksNone;
-  bool sequence = false;                  // the slot holds FRAME k of one stream (mot_sequence_dev, mot_sequence_accumulate_dev), not stream k's frame:
-                                          // mot_accumulate_track_points refuses it
+  bool sequence = false;                  // the slot holds FRAME k of one stream (mot_sequence_dev, mot_sequence_accumulate_dev, mot_sequence_products_dev), not
+                                          // stream k's frame: mot_accumulate_track_points and mot_accumulate_scene refuse it
   bool accumulated = false;               // mot_accumulate_track_points has appended the step the slot holds (or a reset / load has put it out of reach): not again
   bool scene = false;                     // the same for mot_accumulate_scene and the slot's scene grid (every transition that gives the slot a new step starts it over)
 };
@@ -100,6 +100,8 @@ struct Residency {
   void sequence_accumulated(int frames) { for (int b = 0; b < frames; b++) slots[b].accumulated = true; }
   bool scene_done(int slot) const { return slots[slot].scene; }
   void scene_taken(int slot) { slots[slot].scene = true; }   // (also: the slot's stream was reset or loaded)
+  // mot_sequence_products_dev(MOT_SEQ_SCENE) has taken the frames the slots hold into stream 0's grid (they stay sequence slots: no call takes them again)
+  void sequence_scene_taken(int frames) { for (int b = 0; b < frames; b++) slots[b].scene = true; }
   bool elev_packed_at(int slot) const { return slots[slot].packed; }
   bool labels_ready(int slot) const { return slots[slot].labels == kLabelsReady; }
   bool cells_usable(int slot) const { return slots[slot].labels == kLabelsFromCells; }
@@ -273,6 +275,9 @@ struct mot_ctx {
   PinnedRing sg_ring;                      // blocks of `batch` matrices and `batch` ints
   mot_scene_cell* d_sg_stage = nullptr;    // mot_get_scene_grid: one slot's unrolled cells before they go to the host (allocated at ITS first call)
   std::vector<int> scene_step;             // [batch] accepted mot_accumulate_scene calls that covered the slot (the next step stamp)
+  // mot_sequence_products_dev(MOT_SEQ_SCENE) (scene_grid_seq.hip): allocated at its first call, both or neither; released with the blocks above
+  SceneSeqFrame* d_sgs_win = nullptr;      // [batch + 1] every frame's window and what is left of it at the end of the call; entry 0: the window before the call
+  unsigned* d_sgs_static = nullptr;        // [batch][(E + 31) / 32] per frame one bit per track id: flagged static as that frame's step left it
   std::vector<EgoTf> link_tf;          // [batch] the matrix every slot's boxes took in its last fused call with the tracker, kept while links are on (host side)
   Vec2d* d_cp = nullptr;
   TrackItem* d_items = nullptr;
@@ -425,6 +430,11 @@ int scene_restart_slots(mot_ctx* c, int first, int n);   // the scene grids of t
 int seq_accum_ready(mot_ctx* c, const char* who);
 void seq_accum_capture(mot_ctx* c, int frame);
 int seq_accum_append(mot_ctx* c, int frames, int max_n);
+// ... and into stream 0's scene grid (mot_api_scene.hip, scene_grid_seq.hip): ready refuses (grid or links off, no scratch) before anything has run and zeroes the
+// capture table of `frames` frames; capture right behind tracker step `frame`; append behind the last step and the point links
+int seq_scene_ready(mot_ctx* c, const char* who, int frames);
+void seq_scene_capture(mot_ctx* c, int frame);
+int seq_scene_append(mot_ctx* c, int frames, int max_n);
 // head of a packed live-track block: one count per slot, padded to 16 bytes; the records follow (mot_export_tracks_packed_dev, mot_gather)
 inline long mot_packed_head_bytes(int batch) { return ((long)batch * 4 + 15) & ~15l; }
 #endif  // MOT_HOST_H_

@@ -492,6 +492,23 @@ void mot_launch_scene_export(const SceneGridBuffers& g, int first, int batch, mo
 // headers and origins of slots [first, first + n) back to "no step yet" (the cells are the caller's memset)
 void mot_launch_scene_reset(const SceneGridBuffers& g, int first, int n, hipStream_t stream);
 
+// The scene grid fed by sequence mode (scene_grid_seq.hip, mot_sequence_products_dev with MOT_SEQ_SCENE): slot k = FRAME k of stream 0, all frames into slot 0's grid.
+constexpr int kSceneSeqClearBlocks = 256;  // workgroups of the clear kernel (a grid-stride loop over the cells the drive scrolled out)
+struct SceneSeqFrame {         // 32 bytes; entry k + 1 is frame k, entry 0 the window the grid was laid out for before the call (ok unused)
+  int oi, oj, ok, pad;         // the frame's window (the window before it when its own is invalid) and whether its own is valid
+  int lo_i, hi_i, lo_j, hi_j;  // the intersection of this window and every later one of the call: global cells [lo, hi) per axis, may be empty
+};
+struct SceneSeqBuffers {
+  SceneSeqFrame* win;          // [frames + 1]
+  unsigned* is_static;         // [frames][words]: bit id of frame k = track id was flagged static as step k left it (ids of the frame's owner row only)
+  int words;                   // (E + 31) / 32
+  int step0;                   // step stamp of frame 0; frame k gets step0 + k
+};
+// right behind tracker step `frame` of a sequence (the frame's words are zero: one memset per call); slot_of / out are stream 0's
+void mot_launch_scene_seq_capture(const int* counts, const int* owner, const int* slot_of, const mot_track* out, int T, int E, const SceneSeqBuffers& s, int frame, hipStream_t stream);
+// behind the last step and the point-link launch: windows, clear, splat — slots 0 .. frames - 1 into slot 0's grid; in.slot_of / in.out are not read
+void mot_launch_scene_sequence(const SceneGridBuffers& g, const SceneSplatInput& in, const SceneSeqBuffers& s, int frames, int max_n, const EgoTf* tf, hipStream_t stream);
+
 #ifdef MOT_HIPEMU
 #define MOT_WAVE_SYNC() ((void)__ballot(1))
 #else

@@ -11,7 +11,8 @@
 //   G1  scene_splat_kernel    grid (ceil(N_e / 2048), B), 256 threads, 8 points a thread: per point one 12-byte load (16 in the float4 layout), one 4-byte id load, the
 //                             transform, the cell test, and for an owned point the two dependent gathers id -> track slot -> is_static (track_accum_plan's reads).
 //                             Then, wave by wave, ONE lane per run of neighbouring lanes with the same (cell, kind) adds the run's length and its largest z
-//                             (MOT_SCENE_MERGE, below); the three counters of the step are summed per wave first. Workgroup (0, b) moves the previous origin on
+//                             (MOT_SCENE_MERGE, below); the three counters of the step are summed per wave first. Workgroup (0, b) moves the previous origin on.
+//                             The per-point step and the merged adds are scene_point_cell / scene_add_wave of mot_scene_splat.h, shared with scene_grid_seq.hip
 //   G2  scene_export_kernel   the torus unrolled into the caller's block, one 16-byte load and one 16-byte store a cell; the z image converted; the header copied
 //   --  scene_reset_kernel    headers and previous origins of a run of slots back to "no step yet" (the setter, the resets, mot_stream_load; the cells by a memset)
 //
@@ -27,36 +28,9 @@
 // storage index is (gi & (W - 1)) + (gj & (W - 1)) * W < W^2 by construction, the slot offset b * W^2 with b below the launch's batch <= max_batch. Point and id loads stay
 // below min(count, cap) of the slot; an id outside [0, E) or a track slot outside [0, T) is not followed (the point then counts as dynamic: an owner that is not static).
 // Resources (tools/kernel_resources.py): no LDS, no scratch.
-#include "mot_internal.h"
-#include "mot_wave.h"
+#include "mot_scene_splat.h"   // the window rule, the per-point step and the merged adds, shared with scene_grid_seq.hip
 
-#ifndef MOT_HIPEMU
-#define MOT_SG_BOUNDS(n) __launch_bounds__(n)
-#else
-#define MOT_SG_BOUNDS(n)
-#endif
-#ifndef MOT_SCENE_MERGE
-#define MOT_SCENE_MERGE 1
-#endif
-#ifndef MOT_SCENE_RUN
-#define MOT_SCENE_RUN 64   // lanes a run may span: 16 (a DPP row) or 64 (profiles/scene_grid.md has both)
-#endif
-static_assert(MOT_SCENE_RUN == 16 || MOT_SCENE_RUN == 64, "runs end at multiples of 16 or of 64 lanes");
-
-constexpr int kSceneBlock = 256, kSceneItems = kSceneChunk / kSceneBlock;
-static_assert(kSceneChunk % kSceneBlock == 0, "every thread takes the same number of points");
 static_assert(sizeof(mot_scene_cell) == 16 && sizeof(SceneCell) == 16 && sizeof(mot_scene_header) == 32 && sizeof(SceneWindow) == 16, "include/mot.h documents the sizes");
-
-constexpr float kSceneLimit = 1073741824.f;   // 2^30
-
-// the window a matrix asks for: false when either product is not finite or is >= 2^30 in magnitude (NaN fails both compares)
-__device__ __forceinline__ bool scene_window(const EgoTf& m, float inv, int W, int* oi, int* oj) {
-  const float a = m.m[3] * inv, c = m.m[7] * inv;
-  if (!(fabsf(a) < kSceneLimit) || !(fabsf(c) < kSceneLimit)) return false;
-  *oi = (int)floorf(a) - W / 2;
-  *oj = (int)floorf(c) - W / 2;
-  return true;
-}
 
 // ------------------------------------------------------------------------------------------ G0
 __global__ void MOT_SG_BOUNDS(kSceneBlock)
@@ -119,21 +93,14 @@ scene_splat_kernel(SceneGridBuffers g, SceneSplatInput in, int b0, const EgoTf* 
     if (i < n) { id[k] = ids[i]; q[k] = mot_load_xyz(cloud, i, in.elevated_packed); }
   }
   int n_static = 0, n_dynamic = 0, n_outside = 0;
+  const SceneRect window = {oi, oi + W, oj, oj + W};
 #pragma unroll
   for (int k = 0; k < kSceneItems; k++) {
     const long i = base + k * kSceneBlock + tid;
     const bool valid = i < n;
-    // fp32, left to right; the build has -ffp-contract=off (mot_track_place.h's sensor -> global step: the very bits the MOT_FRAME_GLOBAL export writes)
-    const float gx = m.m[0] * q[k].x + m.m[1] * q[k].y + m.m[2] * q[k].z + m.m[3];
-    const float gy = m.m[4] * q[k].x + m.m[5] * q[k].y + m.m[6] * q[k].z + m.m[7];
-    const float gz = m.m[8] * q[k].x + m.m[9] * q[k].y + m.m[10] * q[k].z + m.m[11];
-    const float tx = gx * inv, ty = gy * inv;
-    bool inside = valid && window_ok && (gx - gx == 0.f) && (gy - gy == 0.f) && (gz - gz == 0.f) && fabsf(tx) < kSceneLimit && fabsf(ty) < kSceneLimit;
-    int u = 0, v = 0;
-    if (inside) {
-      u = (int)floorf(tx) - oi; v = (int)floorf(ty) - oj;
-      inside = u >= 0 && u < W && v >= 0 && v < W;
-    }
+    float gz;
+    const int at = scene_point_cell(m, q[k], inv, valid && window_ok, window, W, &gz);   // (mot_scene_splat.h)
+    const bool inside = at >= 0;
     int dynamic = 0;
     if (inside && id[k] >= 0) {
       dynamic = 1;
@@ -143,44 +110,10 @@ scene_splat_kernel(SceneGridBuffers g, SceneSplatInput in, int b0, const EgoTf* 
       }
     }
     n_static += inside && !dynamic; n_dynamic += inside && dynamic; n_outside += valid && !inside;
-    // what the point adds to: (storage index, kind), -1: nothing
-    const int key = inside ? (((((oj + v) & (W - 1)) * W + ((oi + u) & (W - 1))) << 1) | dynamic) : -1;
-    const unsigned zkey = (unsigned)mot_float_key(gz) ^ 0x80000000u;
-#if MOT_SCENE_MERGE
-    // every lane of the wave is here (no divergent exit above): the lane before me, then the heads of the runs
-    const int before = __shfl_up(key, 1, 64);
-    const bool head = (lane & (MOT_SCENE_RUN - 1)) == 0 || before != key;
-    const unsigned long long heads = __ballot(head);
-    const unsigned long long above = lane == 63 ? 0ull : heads & ~((2ull << lane) - 1ull);
-    int end = above ? __ffsll(above) - 1 : 64;   // first lane of the next run
-    const int row_end = (lane | (MOT_SCENE_RUN - 1)) + 1;
-    if (end > row_end) end = row_end;
-    unsigned zmax = zkey;
-#pragma unroll
-    for (int d = 1; d < MOT_SCENE_RUN; d <<= 1) {   // lane l holds the maximum over [l, min(end, l + 2 d))
-      const unsigned o = __shfl_down(zmax, d, 64);
-      if (lane + d < end && o > zmax) zmax = o;
-    }
-    const unsigned count = (unsigned)(end - lane);
-    const bool writer = head && key >= 0;
-#else
-    const unsigned zmax = zkey, count = 1u;
-    const bool writer = key >= 0;
-#endif
-    if (writer) {
-      SceneCell* __restrict__ c = cells + (key >> 1);
-      if (key & 1) atomicAdd(&c->dynamic_hits, count);
-      else { atomicAdd(&c->static_hits, count); atomicMax(&c->zkey, zmax); }
-      c->last_seen = stamp;
-    }
+    // what the point adds to: (storage index, kind), -1: nothing. Every lane of the wave is here (no divergent exit above)
+    scene_add_wave<false>(cells, inside ? ((at << 1) | dynamic) : -1, gz, stamp, lane);
   }
-  // the step's counters: one add per wave and counter
-  n_static = wave_sum_i32(n_static); n_dynamic = wave_sum_i32(n_dynamic); n_outside = wave_sum_i32(n_outside);
-  if (lane == 0) {
-    if (n_static) atomicAdd(&hdr->n_static, (unsigned)n_static);
-    if (n_dynamic) atomicAdd(&hdr->n_dynamic, (unsigned)n_dynamic);
-    if (n_outside) atomicAdd(&hdr->n_outside, (unsigned)n_outside);
-  }
+  scene_count_wave(hdr, n_static, n_dynamic, n_outside, lane);
 }
 
 // ------------------------------------------------------------------------------------------ G2

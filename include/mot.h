@@ -696,7 +696,7 @@ int mot_get_track_model_voxels(mot_ctx* ctx, int slot, int flags, const mot_voxe
  * mot_accumulate_scene(batch): takes every elevated point of the latest fused step of slots 0..batch-1. Asynchronous on the context stream, nothing is read back.
  * Validity is that of mot_accumulate_track_points, tested for every slot before anything is launched; a refused call changes nothing and counts no step:
  * MOT_E_STATE unless the slot's cloud, boxes and tracker step come from ONE fused call with links on (a stage-wise call since, a tracker step fed from outside),
- * on the slots of mot_sequence_dev / mot_sequence_accumulate_dev, for a second call on the same step, and after a reset or a load since that step.
+ * on the slots of mot_sequence_dev / mot_sequence_accumulate_dev / mot_sequence_products_dev (the last takes a sequence's frames inside the call, below), for a second call on the same step, and after a reset or a load since that step.
  * STEP STAMP of a slot = the number of accepted mot_accumulate_scene calls that covered the slot before this one (0, 1, ...; a counter of its own, apart from the
  * accumulators'; counted on the host, it travels with the slots' matrices in one stream-ordered copy).
  * POINTS: the slot's elevated cloud in input order (MOT_ORDER_ANY included), each under the matrix mot_export_track_points_dev(MOT_FRAME_GLOBAL) applies —
@@ -743,6 +743,38 @@ int mot_set_scene_grid(mot_ctx* ctx, const mot_scene_params* p /* NULL: off, mem
 int mot_accumulate_scene(mot_ctx* ctx, int batch);
 int mot_export_scene_grid_dev(mot_ctx* ctx, int batch, mot_scene_cell* d_cells, long cell_stride /* cells per slot */, mot_scene_header* d_headers);
 int mot_get_scene_grid(mot_ctx* ctx, int slot, mot_scene_cell* cells, int capacity, int* n_cells, mot_scene_header* header);
+
+/* ---------------------------------------------------------------- a recorded drive into a map: sequence mode with products (addition within ABI v6)
+ * mot_sequence_products_dev IS mot_sequence_dev — the same arguments, the same launch sequence — plus a bit set of products taken from every frame of the call in
+ * the same asynchronous call (nothing is read back, no host synchronisation). products == 0 is mot_sequence_dev; products == MOT_SEQ_ACCUMULATE is
+ * mot_sequence_accumulate_dev (above); MOT_SEQ_SCENE takes every frame into STREAM 0's scene grid; both bits: a drive into the accumulators and the grid at once.
+ * The two older entry points stay as they are.
+ *
+ * RESULT of MOT_SEQ_SCENE. Slot 0's grid and header (mot_export_scene_grid_dev / mot_get_scene_grid) are, byte for byte, what `frames` rounds of
+ * { mot_frames_dev(batch 1) on frame k; mot_accumulate_scene(ctx, 1) } leave there from the same tracker and grid state: the toroidal cells, last_seen, the header of
+ * the LAST frame (origin, stamp, that frame's three counters), the stored previous origin and window validity — frame-by-frame steps and further sequence calls
+ * continue the same grid. The grids of slots >= 1 are not touched. Every other result of the call is byte-identical to mot_sequence_dev's (with
+ * MOT_SEQ_ACCUMULATE: to mot_sequence_accumulate_dev's).
+ * STEP STAMPS: frame k gets (slot 0's scene step counter) + k and the counter advances by `frames`; a frame the box stage refused for capacity is taken as the
+ * frame-by-frame route takes it (its elevated points, none of them owned), and it counts.
+ * AFTER THE CALL the slots are sequence slots: mot_accumulate_scene keeps answering MOT_E_STATE on them. mot_reset* and mot_stream_load empty slot 0's grid and
+ * restart its counter as they always do.
+ * REFUSALS, each before anything has run (the tracker has not stepped): MOT_E_ARG for unknown bits and for mot_sequence_dev's argument errors; MOT_E_STATE when
+ * MOT_SEQ_SCENE is set and the grid is off, when MOT_SEQ_ACCUMULATE is set and accumulation is off, when either is set with links off; MOT_E_HIP when a product's
+ * own scratch cannot be had at its first use — all of its blocks or none, the next call tries again. The scene's scratch is 32 bytes per slot of max_batch (+ 32)
+ * for the windows and max_batch x ceil(max_tracks_ever / 32) x 4 bytes (one bit per track id and frame: the tracks a frame's step left flagged static; 16 KB a
+ * frame at the default max_tracks_ever of 64 x 2048); it is released with the grid (mot_set_scene_grid(NULL) or another geometry) and by mot_destroy.
+ * HOW (csrc/scene_grid_seq.hip). The kind of a point ("is_static as this step left it") is gone one tracker step later: a small kernel behind every step keeps it,
+ * one bit per id. The rolling window needs no serial pass: all windows are squares of one size, so "this cell was never scrolled out between frame k and the last
+ * frame" is membership in ONE rectangle per frame, R[k] = [max_{j >= k} o[j], min_{j >= k} o[j] + W) per axis over the origins o[j] of the windows k .. frames - 1
+ * (an invalid window keeps the origin before it; R[-1] starts at the origin the grid was laid out for before the call). Cells of the final window outside R[-1]
+ * are emptied, a point of frame k takes part iff its frame's window is valid and its cell lies in R[k] — with the arithmetic of mot_accumulate_scene bit for bit;
+ * last_seen is an integer maximum, only the last frame feeds the header's counters. One windows workgroup (two scans), a clear and ONE splat launch over all
+ * frames, whatever `frames` is. Cost: profiles/scene_grid_sequence.md (tools/time_scene_grid_sequence.py). */
+enum { MOT_SEQ_ACCUMULATE = 1, MOT_SEQ_SCENE = 2 };
+int mot_sequence_products_dev(mot_ctx* ctx, const float* d_xyzw, long frame_stride, const int* n_points, int frames,
+                              const double* timestamps, const double* ego_v, const double* ego_yaw,
+                              void* d_tracks, int max_per_frame, int32_t* d_counts, int products);
 
 /* on != 0: the fused entry points send their launch sequence (13 kernels with the tracker) as ONE hipGraph launch, captured once per launch geometry
  * (batch, chunks of the largest frame, tracker on / off, outputs); what changes per call without changing the geometry travels in the
