@@ -99,6 +99,25 @@ assert VOXEL_MODEL_DTYPE.itemsize == 64 and MODEL_VOXEL_DTYPE.itemsize == 16
 SCENE_CELL_DTYPE = np.dtype([("static_hits", "u4"), ("dynamic_hits", "u4"), ("max_z", "f4"), ("last_seen", "i4")])
 SCENE_HEADER_DTYPE = np.dtype([("origin_i", "i4"), ("origin_j", "i4"), ("step", "i4"), ("size", "i4"), ("n_static", "u4"), ("n_dynamic", "u4"), ("n_outside", "u4"), ("cell", "f4")])
 assert SCENE_CELL_DTYPE.itemsize == 16 and SCENE_HEADER_DTYPE.itemsize == 32
+# the classes of mot_export_scene_points_dev / mot_get_scene_points, struct mot_scene_segment and struct mot_scene_judge_params (a frame's points judged against the grid)
+SCENE_UNKNOWN, SCENE_MOVING, SCENE_TRAIL, SCENE_NEW, SCENE_KNOWN, SCENE_CLASSES = 0, 1, 2, 3, 4, 5
+SCENE_CLASS_NAMES = ("unknown", "moving", "trail", "new", "known")
+SCENE_SEGMENT_DTYPE = np.dtype([("first", "i4"), ("count", "i4")])
+assert SCENE_SEGMENT_DTYPE.itemsize == 8
+
+
+class MotSceneJudgeParams(C.Structure):
+    """struct mot_scene_judge_params"""
+    _fields_ = [("min_static_hits", C.c_uint32), ("trail_num", C.c_uint32), ("trail_den", C.c_uint32)]
+
+
+def _scene_mask(classes) -> int:
+    """None: all five; an int: the bit mask itself; else an iterable of class numbers or names"""
+    if classes is None:
+        return (1 << SCENE_CLASSES) - 1
+    if isinstance(classes, (int, np.integer)):
+        return int(classes)
+    return sum({1 << (SCENE_CLASS_NAMES.index(k) if isinstance(k, str) else int(k)) for k in classes})
 
 
 class MotSceneParams(C.Structure):
@@ -144,6 +163,7 @@ EXPORTS = (
     "mot_set_track_accumulation", "mot_accumulate_track_points", "mot_sequence_accumulate_dev", "mot_track_accumulators_dev", "mot_get_accum_rows", "mot_get_track_accumulated",
     "mot_export_track_models_dev", "mot_get_track_models", "mot_export_track_model_voxels_dev", "mot_get_track_model_voxels",
     "mot_set_scene_grid", "mot_accumulate_scene", "mot_export_scene_grid_dev", "mot_get_scene_grid", "mot_sequence_products_dev",
+    "mot_export_scene_points_dev", "mot_get_scene_points",
     "mot_gather_unique_id", "mot_gather_create", "mot_gather_contribute", "mot_gather_result", "mot_gather_synchronize", "mot_gather_destroy", "mot_gather_last_error",
 )
 ABI_VERSION = 6
@@ -447,6 +467,26 @@ class Context:
         """the grids of slots 0..batch-1, unrolled -> caller's device blocks (mot_export_scene_grid_dev): 16-byte cells d_cells[b * cell_stride + v * size + u]
         (SCENE_CELL_DTYPE; window offset (u, v) = global cell (origin_i + u, origin_j + v)) and 32-byte headers d_headers[b] (SCENE_HEADER_DTYPE). Asynchronous"""
         self._ck(self.lib.mot_export_scene_grid_dev(self._h, int(batch), C.c_void_p(d_cells_ptr or None), C.c_long(cell_stride), C.c_void_p(d_headers_ptr or None)))
+
+    def export_scene_points_dev(self, batch: int, d_points_ptr: int, point_stride: int, d_segments_ptr: int, d_classes_ptr: int = 0, class_stride: int = 0,
+                                min_static_hits: int = 1, trail=(1, 2), classes=None, frame=MOT_FRAME_GLOBAL):
+        """the elevated points of slots 0..batch-1 judged against their scene grids and partitioned by class (mot_export_scene_points_dev) -> caller's device blocks:
+        16-byte records d_points[b * point_stride + i] (the classes of `classes`, ascending, each in input order), 8-byte segments d_segments[b * 5 + k] = {first,
+        count} (SCENE_SEGMENT_DTYPE; the true count of every class, first = -1 outside the mask) and, if given, one class byte per elevated point
+        d_classes[b * class_stride + i]. trail = (num, den). Reads the grid; asynchronous"""
+        p = MotSceneJudgeParams(int(min_static_hits), int(trail[0]), int(trail[1]))
+        self._ck(self.lib.mot_export_scene_points_dev(self._h, int(batch), C.byref(p), _scene_mask(classes), _frame(frame), C.c_void_p(d_points_ptr or None), C.c_long(point_stride),
+                                                      C.c_void_p(d_segments_ptr or None), C.c_void_p(d_classes_ptr or None), C.c_long(class_stride)))
+
+    def get_scene_points(self, slot: int = 0, min_static_hits: int = 1, trail=(1, 2), classes=None, frame=MOT_FRAME_GLOBAL) -> dict:
+        """one slot's elevated points judged against its scene grid (mot_get_scene_points): segments [5] (SCENE_SEGMENT_DTYPE: first, count per class SCENE_UNKNOWN ..
+        SCENE_KNOWN; first = -1 for a class outside `classes`), xyz [n, 3] and index [n] of the selected classes back to back, classes [n_elevated] (uint8, input order)"""
+        p = MotSceneJudgeParams(int(min_static_hits), int(trail[0]), int(trail[1]))
+        cap = self.max_points
+        pts = np.zeros(max(cap, 1), TRACK_POINT_DTYPE); seg = np.zeros(SCENE_CLASSES, SCENE_SEGMENT_DTYPE); cls = np.zeros(max(cap, 1), np.uint8); npts, ne = C.c_int(0), C.c_int(0)
+        self._ck(self.lib.mot_get_scene_points(self._h, int(slot), C.byref(p), _scene_mask(classes), _frame(frame), _vp(pts), cap, C.byref(npts), _vp(seg), _vp(cls), cap, C.byref(ne)))
+        pts = pts[: npts.value]
+        return dict(segments=seg, xyz=pts["xyz"].copy(), index=pts["index"].copy(), classes=cls[: ne.value].copy())
 
     def get_scene_grid(self, slot: int = 0, cells: bool = True) -> dict:
         """one slot's grid on the host (mot_get_scene_grid): header (a SCENE_HEADER_DTYPE record) and cells [size, size] indexed (v, u) (SCENE_CELL_DTYPE;

@@ -1,5 +1,5 @@
 // mot_api_scene.hip — host side of the C-ABI (include/mot.h), the rolling static-scene grid: the setter and what it owns, the per-slot step counters, the state
-// checks of mot_accumulate_scene, and the two readers. Kernels: scene_grid.hip. Context and helpers: mot_host.h.
+// checks of mot_accumulate_scene, the two readers, and the frame's points judged against the grid. Kernels: scene_grid.hip, scene_judge.hip. Context and helpers: mot_host.h.
 #include "mot_host.h"
 
 // The setter owns the feature's memory: cells, headers, previous origins, the argument block and its ring of page-locked staging blocks are allocated together and
@@ -17,6 +17,11 @@ static int seq_scene_release(mot_ctx* c) {
   MOT_TRY(release(c, &c->d_sgs_win));
   return release(c, &c->d_sgs_static);
 }
+// what mot_export_scene_points_dev took at its first call (all three or none) and the getter's staging block (the caller has drained the stream)
+static int judge_release(mot_ctx* c) {
+  MOT_TRY(release(c, &c->d_sj_cls)); MOT_TRY(release(c, &c->d_sj_rows)); MOT_TRY(release(c, &c->d_sj_args));
+  return release(c, &c->d_sj_stage);
+}
 static size_t scene_arg_bytes(const mot_ctx* c) { return (size_t)c->batch * (sizeof(EgoTf) + sizeof(int)); }   // [batch] matrices, then [batch] step stamps
 static SceneGridBuffers scene_buffers(const mot_ctx* c) {
   SceneGridBuffers g;
@@ -31,7 +36,7 @@ int scene_restart_slots(mot_ctx* c, int first, int n) {
   MOT_HIP(c, hipMemsetAsync(c->d_sg_cells + (size_t)first * slot_cells, 0, (size_t)n * slot_cells * sizeof(SceneCell), c->stream));
   mot_launch_scene_reset(scene_buffers(c), first, n, c->stream);
   MOT_HIP(c, hipGetLastError());
-  for (int b = first; b < first + n; b++) { c->scene_step[b] = 0; c->res.scene_taken(b); }
+  for (int b = first; b < first + n; b++) { c->scene_step[b] = 0; c->res.scene_restarted(b); }
   return MOT_OK;
 }
 
@@ -45,6 +50,7 @@ static int scene_off(mot_ctx* c) {
   MOT_TRY(release(c, &c->sg_ring.base));
   for (bool& u : c->sg_ring.used) u = false;
   MOT_TRY(seq_scene_release(c));
+  MOT_TRY(judge_release(c));
   return release(c, &c->d_sg_stage);
 }
 
@@ -78,6 +84,7 @@ extern "C" int mot_set_scene_grid(mot_ctx* c, const mot_scene_params* p) {
     SceneBlocks old = {c->d_sg_cells, c->d_sg_hdr, c->d_sg_prev, c->d_sg_args};
     MOT_TRY(scene_release(c, &old));
     MOT_TRY(seq_scene_release(c));
+    MOT_TRY(judge_release(c));
     MOT_TRY(release(c, &c->d_sg_stage));
   }
   c->d_sg_cells = s.cells; c->d_sg_hdr = s.hdr; c->d_sg_prev = s.prev; c->d_sg_args = s.args;
@@ -199,5 +206,123 @@ extern "C" int mot_get_scene_grid(mot_ctx* c, int slot, mot_scene_cell* cells, i
   if (header) MOT_HIP(c, hipMemcpyAsync(pin, c->d_sg_hdr + slot, sizeof(mot_scene_header), hipMemcpyDeviceToHost, c->stream));
   MOT_HIP(c, hipStreamSynchronize(c->stream));
   if (header) memcpy(header, pin, sizeof(mot_scene_header));
+  return MOT_OK;
+}
+
+// ---------------------------------------------------------------------------------------- a frame's points judged against the grid (scene_judge.hip)
+// The validity of mot_accumulate_scene without its once-per-step clause: the step may have been taken or not, but a grid emptied since (the setter, a reset, a load)
+// no longer belongs to the step the slot holds.
+static int check_judge_slot(mot_ctx* c, int b, const char* who) {
+  if (!c->track_links || !c->res.point_tracks_valid(b))
+    return fail(c, MOT_E_STATE, who, ": the slot's cloud, boxes and tracker step do not come from one fused call (a stage-wise call took the slot, the tracker was fed from outside, "
+                                     "or no fused call ran the tracker since the links were turned on)");
+  if (c->res.sequence_frame(b)) return fail(c, MOT_E_STATE, who, ": the slots hold the frames of ONE stream (mot_sequence_dev)");
+  if (!c->res.scene_judgeable(b)) return fail(c, MOT_E_STATE, who, ": the slot's grid was emptied (mot_set_scene_grid, a reset or a load) since the step the slot holds");
+  return MOT_OK;
+}
+static int check_judge_args(mot_ctx* c, const char* who, const mot_scene_judge_params* p, int class_mask, int frame) {
+  if (!p) return fail(c, MOT_E_ARG, who, ": null params");
+  if (p->min_static_hits < 1u || p->min_static_hits > 0x80000000u) return fail(c, MOT_E_ARG, who, ": min_static_hits must lie in [1, 2^31]");
+  if (p->trail_den < 1u || p->trail_den > 65535u || p->trail_num > p->trail_den) return fail(c, MOT_E_ARG, who, ": trail_den must lie in [1, 65535] and trail_num in [0, trail_den]");
+  if (class_mask & ~((1 << MOT_SCENE_CLASSES) - 1)) return fail(c, MOT_E_ARG, who, ": unknown class bits");
+  if (frame != MOT_FRAME_GLOBAL && frame != MOT_FRAME_SENSOR) return fail(c, MOT_E_ARG, who, ": frame must be MOT_FRAME_GLOBAL or MOT_FRAME_SENSOR");
+  return MOT_OK;
+}
+// the scratch, at the first call: all of its blocks or none (a failure leaves the live allocations as they were; the next call tries again)
+static int ensure_judge(mot_ctx* c, bool host_stage) {
+  c->sj_chunks = (c->cap + kSceneChunk - 1) / kSceneChunk;
+  if (!c->d_sj_cls || !c->d_sj_rows || !c->d_sj_args) {
+    int rc = dev_alloc(c, &c->d_sj_cls, (size_t)c->batch * c->cap);
+    if (!rc) rc = dev_alloc(c, &c->d_sj_rows, (size_t)c->batch * c->sj_chunks * kSceneJudgeRow * sizeof(int));
+    if (!rc) rc = dev_alloc(c, &c->d_sj_args, scene_arg_bytes(c));
+    if (rc) {
+      const std::string why = c->err;
+      (void)release(c, &c->d_sj_cls); (void)release(c, &c->d_sj_rows); (void)release(c, &c->d_sj_args);
+      c->err = why;
+      return rc;
+    }
+  }
+  // [cap records][5 segments, padded to 48 bytes][cap class bytes]
+  if (host_stage) MOT_TRY(dev_alloc(c, &c->d_sj_stage, (size_t)c->cap * sizeof(mot_track_point) + 48 + (size_t)c->cap));
+  return MOT_OK;
+}
+// the kernels over slots first .. first + n - 1, block k of the caller's buffers for slot first + k; one launch per run of slots of one cloud layout (launch_track_points)
+static int launch_judge(mot_ctx* c, int first, int n, const mot_scene_judge_params* p, int class_mask, int frame, mot_track_point* d_points, long point_stride,
+                        mot_scene_segment* d_segments, uint8_t* d_classes, long class_stride) {
+  // the matrices the slots' boxes took, in one stream-ordered copy ahead of the kernels (the cell test needs them in either frame)
+  char* raw;
+  MOT_TRY(c->sg_ring.acquire(c, &raw));
+  memcpy(raw, c->link_tf.data() + first, (size_t)n * sizeof(EgoTf));
+  MOT_TRY(c->sg_ring.commit(c, c->d_sj_args, 0, (size_t)n * sizeof(EgoTf), c->stream));
+  const EgoTf* d_tf = reinterpret_cast<const EgoTf*>(c->d_sj_args);
+  SceneSplatInput in;
+  in.ids = c->d_point_track; in.elevated = c->d_elev; in.cap = c->cap; in.counts = c->d_counts; in.slot_of = c->d_slot_of; in.out = c->d_tout;
+  in.T = c->max_tracks_total; in.E = c->max_tracks_ever;
+  SceneJudgeBuffers j;
+  j.cls = c->d_sj_cls; j.rows = c->d_sj_rows; j.max_chunks = c->sj_chunks;
+  j.min_static_hits = p->min_static_hits; j.trail_num = p->trail_num; j.trail_den = p->trail_den; j.class_mask = class_mask;
+  const SceneGridBuffers g = scene_buffers(c);
+  for (int k0 = 0; k0 < n;) {
+    int k1 = k0 + 1;
+    while (k1 < n && c->res.elev_packed_at(first + k1) == c->res.elev_packed_at(first + k0)) k1++;
+    in.elevated_packed = c->res.elev_packed_at(first + k0) ? 1 : 0;
+    mot_launch_scene_judge(g, in, j, first + k0, k1 - k0, c->max_points, d_tf + k0, frame == MOT_FRAME_GLOBAL, d_points ? d_points + (long)k0 * point_stride : nullptr, point_stride,
+                           d_segments + (long)k0 * MOT_SCENE_CLASSES, d_classes ? d_classes + (long)k0 * class_stride : nullptr, class_stride, c->stream);
+    k0 = k1;
+  }
+  MOT_HIP(c, hipGetLastError());
+  return MOT_OK;
+}
+
+extern "C" int mot_export_scene_points_dev(mot_ctx* c, int batch, const mot_scene_judge_params* p, int class_mask, int frame, mot_track_point* d_points, long point_stride,
+                                           mot_scene_segment* d_segments, uint8_t* d_classes, long class_stride) {
+  if (!c) return MOT_E_ARG;
+  MOT_GUARD(c);
+  const char* who = "mot_export_scene_points_dev";
+  MOT_TRY(check_scene_on(c, who));
+  MOT_TRY(check_judge_args(c, who, p, class_mask, frame));
+  if (!d_segments || batch < 1 || batch > c->batch || point_stride < 0 || class_stride < 0 || (!d_points && (point_stride > 0 || class_mask)) ||
+      (((size_t)d_points | (size_t)d_segments) & 3))
+    return fail(c, MOT_E_ARG, who, ": bad argument (null segments, batch out of range, a negative stride, null points with a stride or a mask, a block off 4 bytes)");
+  for (int b = 0; b < batch; b++) MOT_TRY(check_judge_slot(c, b, who));   // every slot before anything is launched
+  MOT_TRY(ensure_judge(c, false));
+  return launch_judge(c, 0, batch, p, class_mask, frame, d_points, point_stride, d_segments, d_classes, class_stride);
+}
+
+extern "C" int mot_get_scene_points(mot_ctx* c, int slot, const mot_scene_judge_params* p, int class_mask, int frame, mot_track_point* points, int point_capacity, int* n_points,
+                                    mot_scene_segment segments[5], uint8_t* classes, int class_capacity, int* n_elevated) {
+  if (!c) return MOT_E_ARG;
+  MOT_GUARD(c);
+  const char* who = "mot_get_scene_points";
+  MOT_TRY(check_scene_on(c, who));
+  MOT_TRY(check_judge_args(c, who, p, class_mask, frame));
+  if (slot < 0 || slot >= c->batch || point_capacity < 0 || class_capacity < 0 || !n_points || !n_elevated || !segments)
+    return fail(c, MOT_E_ARG, who, ": slot or a capacity out of range, or a null count or segment table");
+  MOT_TRY(check_judge_slot(c, slot, who));
+  MOT_TRY(ensure_judge(c, true));
+  // the slot alone into the staging block, with the block's own capacities; what fits the caller's buffers is decided here
+  mot_track_point* d_pts = reinterpret_cast<mot_track_point*>(c->d_sj_stage);
+  mot_scene_segment* d_seg = reinterpret_cast<mot_scene_segment*>(c->d_sj_stage + (size_t)c->cap * sizeof(mot_track_point));
+  uint8_t* d_cls = reinterpret_cast<uint8_t*>(c->d_sj_stage + (size_t)c->cap * sizeof(mot_track_point) + 48);
+  MOT_TRY(launch_judge(c, slot, 1, p, class_mask, frame, d_pts, c->cap, d_seg, classes ? d_cls : nullptr, c->cap));
+  char* pin;
+  MOT_TRY(pinned_scratch(c, 48, &pin));
+  MOT_HIP(c, hipMemcpyAsync(pin, d_seg, MOT_SCENE_CLASSES * sizeof(mot_scene_segment), hipMemcpyDeviceToHost, c->stream));
+  MOT_HIP(c, hipStreamSynchronize(c->stream));
+  const mot_scene_segment* h = reinterpret_cast<const mot_scene_segment*>(pin);
+  long ne = 0, np = 0;
+  for (int k = 0; k < MOT_SCENE_CLASSES; k++) {
+    if (h[k].count < 0 || h[k].count > c->cap) return fail(c, MOT_E_STATE, who, ": inconsistent counts");
+    ne += h[k].count;
+    if ((class_mask >> k) & 1) np += h[k].count;
+  }
+  if (ne > c->cap) return fail(c, MOT_E_STATE, who, ": inconsistent counts");
+  memcpy(segments, h, MOT_SCENE_CLASSES * sizeof(mot_scene_segment));
+  *n_points = (int)np; *n_elevated = (int)ne;
+  if (points && np > point_capacity) return fail(c, MOT_E_CAPACITY, "more selected points than the caller's point buffer holds");
+  if (classes && ne > class_capacity) return fail(c, MOT_E_CAPACITY, "more elevated points than the caller's class buffer holds");
+  if (points && np > 0) MOT_HIP(c, hipMemcpyAsync(points, d_pts, (size_t)np * sizeof(mot_track_point), hipMemcpyDeviceToHost, c->stream));
+  if (classes && ne > 0) MOT_HIP(c, hipMemcpyAsync(classes, d_cls, (size_t)ne, hipMemcpyDeviceToHost, c->stream));
+  MOT_HIP(c, hipStreamSynchronize(c->stream));
   return MOT_OK;
 }

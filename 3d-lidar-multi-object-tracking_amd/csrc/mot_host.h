@@ -53,6 +53,7 @@ struct SlotState {
                                           // stream k's frame: mot_accumulate_track_points and mot_accumulate_scene refuse it
   bool accumulated = false;               // mot_accumulate_track_points has appended the step the slot holds (or a reset / load has put it out of reach): not again
   bool scene = false;                     // the same for mot_accumulate_scene and the slot's scene grid (every transition that gives the slot a new step starts it over)
+  bool scene_restarted = false;           // the slot's grid was emptied (the setter, a reset, a load) since the step the slot holds: mot_export_scene_points_dev refuses it too
 };
 struct Residency {
   std::vector<SlotState> slots;
@@ -99,7 +100,9 @@ struct Residency {
   // mot_sequence_accumulate_dev has appended the frames the slots hold to stream 0's accumulators (they stay sequence slots: no call appends them again)
   void sequence_accumulated(int frames) { for (int b = 0; b < frames; b++) slots[b].accumulated = true; }
   bool scene_done(int slot) const { return slots[slot].scene; }
-  void scene_taken(int slot) { slots[slot].scene = true; }   // (also: the slot's stream was reset or loaded)
+  void scene_taken(int slot) { slots[slot].scene = true; }
+  void scene_restarted(int slot) { slots[slot].scene = true; slots[slot].scene_restarted = true; }   // the slot's stream was reset or loaded, or the setter emptied the grids
+  bool scene_judgeable(int slot) const { return !slots[slot].scene_restarted; }   // (taken or not: judging a step is legal before and after mot_accumulate_scene)
   // mot_sequence_products_dev(MOT_SEQ_SCENE) has taken the frames the slots hold into stream 0's grid (they stay sequence slots: no call takes them again)
   void sequence_scene_taken(int frames) { for (int b = 0; b < frames; b++) slots[b].scene = true; }
   bool elev_packed_at(int slot) const { return slots[slot].packed; }
@@ -275,6 +278,12 @@ struct mot_ctx {
   PinnedRing sg_ring;                      // blocks of `batch` matrices and `batch` ints
   mot_scene_cell* d_sg_stage = nullptr;    // mot_get_scene_grid: one slot's unrolled cells before they go to the host (allocated at ITS first call)
   std::vector<int> scene_step;             // [batch] accepted mot_accumulate_scene calls that covered the slot (the next step stamp)
+  // mot_export_scene_points_dev / mot_get_scene_points (scene_judge.hip): allocated at the first call, all three or none; released with the blocks above
+  uint8_t* d_sj_cls = nullptr;             // [batch][cap] class of every elevated point
+  int* d_sj_rows = nullptr;                // [batch][sj_chunks][10] per chunk the points per class and where its records go
+  int sj_chunks = 0;                       // max_points / kSceneChunk rounded up
+  char* d_sj_args = nullptr;               // [batch] sensor -> global matrices (a block as d_sg_args, sent through sg_ring)
+  char* d_sj_stage = nullptr;              // mot_get_scene_points: one slot's records, segments and classes before they go to the host (allocated at ITS first call)
   // mot_sequence_products_dev(MOT_SEQ_SCENE) (scene_grid_seq.hip): allocated at its first call, both or neither; released with the blocks above
   SceneSeqFrame* d_sgs_win = nullptr;      // [batch + 1] every frame's window and what is left of it at the end of the call; entry 0: the window before the call
   unsigned* d_sgs_static = nullptr;        // [batch][(E + 31) / 32] per frame one bit per track id: flagged static as that frame's step left it

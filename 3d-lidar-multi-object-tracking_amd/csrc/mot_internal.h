@@ -509,6 +509,20 @@ void mot_launch_scene_seq_capture(const int* counts, const int* owner, const int
 // behind the last step and the point-link launch: windows, clear, splat — slots 0 .. frames - 1 into slot 0's grid; in.slot_of / in.out are not read
 void mot_launch_scene_sequence(const SceneGridBuffers& g, const SceneSplatInput& in, const SceneSeqBuffers& s, int frames, int max_n, const EgoTf* tf, hipStream_t stream);
 
+// A frame's points judged against the scene grid (scene_judge.hip, mot_export_scene_points_dev): READS the grid. Chunks of kSceneChunk points, as the splat kernel's.
+constexpr int kSceneJudgeRow = 2 * MOT_SCENE_CLASSES;   // ints per (slot, chunk): the chunk's points per class, then where its first record of every class goes
+struct SceneJudgeBuffers {
+  uint8_t* cls;                // [B][cap] class of every elevated point (classify -> scatter: the cell of a point is gathered once per call)
+  int* rows;                   // [B][max_chunks][kSceneJudgeRow]
+  int max_chunks;              // max_points / kSceneChunk rounded up
+  unsigned min_static_hits, trail_num, trail_den;
+  int class_mask;
+};
+// slots first .. first + batch - 1 into block k = 0 .. batch - 1 of the caller's buffers: classify, scan and — with a mask and room for records — scatter. tf: [batch]
+// sensor -> global matrices of the launch; global != 0: the records carry global coordinates. points / classes may be null
+void mot_launch_scene_judge(const SceneGridBuffers& g, const SceneSplatInput& in, const SceneJudgeBuffers& j, int first, int batch, int max_n, const EgoTf* tf, int global,
+                            mot_track_point* points, long point_stride, mot_scene_segment* segments, uint8_t* classes, long class_stride, hipStream_t stream);
+
 #ifdef MOT_HIPEMU
 #define MOT_WAVE_SYNC() ((void)__ballot(1))
 #else

@@ -744,6 +744,61 @@ int mot_accumulate_scene(mot_ctx* ctx, int batch);
 int mot_export_scene_grid_dev(mot_ctx* ctx, int batch, mot_scene_cell* d_cells, long cell_stride /* cells per slot */, mot_scene_header* d_headers);
 int mot_get_scene_grid(mot_ctx* ctx, int slot, mot_scene_cell* cells, int capacity, int* n_cells, mot_scene_header* header);
 
+/* ---------------------------------------------------------------- a frame's points judged against the scene grid (additions within ABI v6)
+ * The grid asked a question, on the device: which of the points of the latest fused step belong to the standing scene, which to something that has just appeared,
+ * which lie where a mover passed. One verdict per elevated point, the points partitioned by verdict into the caller's block. The call READS the grid: it changes
+ * not a byte of it and consumes no step. Nothing is launched, written or allocated unless these calls are used. All integer work is exact.
+ *
+ * CLASS of an elevated point of the slot's latest fused step, the rules in this order:
+ *   1 MOVING   the grid's KIND rule says DYNAMIC: owner id >= 0 and that track's is_static, as this step left it, is 0 (an id or a track slot out of range counts as
+ *              dynamic, as in the splat kernel). No cell is needed: inside and outside the window alike.
+ *   2 UNKNOWN  the point does not take part by the grid's rule CELL OF A POINT, tested against the window in the slot's grid header AS IT STANDS: a global x, y or z
+ *              that is not finite, |t| >= 2^30, a cell outside [origin, origin + W)^2, a grid whose latest accepted step had a window that could not be placed, a
+ *              grid with no step yet. The matrix is the one mot_accumulate_scene would use for this step and the arithmetic is the grid's own: the cell is bit for
+ *              bit the one the point would be counted in.
+ *   3 otherwise, with s = static_hits and d = dynamic_hits of that cell as stored:
+ *     TRAIL    d > 0 and (uint64)d * trail_den > ((uint64)s + d) * trail_num: dynamic_hits / (static_hits + dynamic_hits) > num / den. Equality is not a trail;
+ *              num == den turns the class off; num == 0 makes every cell with a dynamic hit a trail.
+ *     NEW      not TRAIL and s < min_static_hits. An empty cell is NEW.
+ *     KNOWN    every other point.
+ * BEFORE OR AFTER mot_accumulate_scene of the same step, both are legal. Before: the point is judged against history alone — the intended use; cells the vehicle's
+ * motion is about to bring into the window are UNKNOWN. After: the cell already holds the frame's own hits.
+ * VALIDITY is that of mot_accumulate_scene without its once-per-step clause, tested for every slot before anything is launched: MOT_E_STATE while the grid is off,
+ * unless the slot's cloud, boxes and tracker step come from ONE fused call with links on, on sequence slots, and after the setter, a reset or a load since that step.
+ *
+ * mot_export_scene_points_dev, slots 0..batch-1, asynchronous on the context stream, nothing is read back:
+ *   d_segments[b * 5 + k] = {first, count}: count is the TRUE number of class-k points of slot b, for every class whether or not it is in class_mask (bits 0..4);
+ *   the classes in the mask are packed back to back into d_points[b * point_stride ..] in ascending class order, first = the segment's start; a class that is not in
+ *   the mask gets first = -1. Inside a segment the 16-byte records {x, y, z, index} keep the elevated cloud's INPUT order, index strictly ascending (MOT_ORDER_ANY
+ *   included). frame: MOT_FRAME_SENSOR (the point's bits) or MOT_FRAME_GLOBAL (the bits mot_export_track_points_dev writes). A slot with more selected records than
+ *   point_stride gets the first point_stride of them and nothing beyond. d_points == NULL with point_stride == 0 and mask 0 gives the counts alone.
+ *   d_classes (may be NULL): d_classes[b * class_stride + i] = the class of elevated point i in input order, truncated at class_stride.
+ * REFUSALS, each before anything runs, the caller's blocks untouched: MOT_E_STATE as above; MOT_E_ARG for null params or segments, min_static_hits of 0 or > 2^31,
+ * trail_den of 0 or > 65535, trail_num > trail_den, mask bits >= 5, an unknown frame, a batch outside [1, max_batch], a negative stride, null d_points with
+ * point_stride > 0 or a non-zero mask, d_points or d_segments not 4-byte aligned; MOT_E_HIP when the scratch cannot be had at the first call — all of its blocks or
+ * none, the next call tries again.
+ * mot_get_scene_points does the same for ONE slot, to the host (synchronises): *n_points (the selected records), *n_elevated and the five segments are always
+ * delivered; MOT_E_CAPACITY with nothing copied when a buffer that was given (points, classes) is too small; either may be NULL.
+ *
+ * Scratch, at the first call: 1 byte per point of max_points and 40 bytes per 2048 points per slot, and an argument block as the grid's (52 bytes per slot, sent
+ * through the grid's page-locked ring in one stream-ordered copy); the getter's staging block at ITS first call. Released with the grid (mot_set_scene_grid(NULL) or
+ * another geometry) and by mot_destroy.
+ * Kernels (csrc/scene_judge.hip): classify (per point 16 bytes read, two small gathers for an owned point, ONE 8-byte gather of the cell's two counters; the class
+ * byte and the chunk's five counts out), a scan (one workgroup per slot) and the scatter (class byte and point in, one 16-byte store per selected record). No global
+ * atomics, no workgroup waits on another, the output does not depend on scheduling. Cost: profiles/scene_judge.md (tools/time_scene_judge.py). */
+enum { MOT_SCENE_UNKNOWN = 0, MOT_SCENE_MOVING = 1, MOT_SCENE_TRAIL = 2, MOT_SCENE_NEW = 3, MOT_SCENE_KNOWN = 4, MOT_SCENE_CLASSES = 5 };
+typedef struct mot_scene_judge_params {
+  uint32_t min_static_hits;      /* [1, 2^31]: a cell with fewer static hits has not been seen standing */
+  uint32_t trail_num, trail_den; /* 0 <= num <= den, den in [1, 65535]: a cell is a mover's trail when dynamic_hits / (static + dynamic) > num / den */
+} mot_scene_judge_params;
+typedef struct mot_scene_segment { int32_t first, count; } mot_scene_segment;   /* 8 bytes */
+int mot_export_scene_points_dev(mot_ctx* ctx, int batch, const mot_scene_judge_params* params, int class_mask, int frame,
+        mot_track_point* d_points, long point_stride, mot_scene_segment* d_segments /* [batch][5] */,
+        uint8_t* d_classes /* may be NULL */, long class_stride);
+int mot_get_scene_points(mot_ctx* ctx, int slot, const mot_scene_judge_params* params, int class_mask, int frame,
+        mot_track_point* points, int point_capacity, int* n_points, mot_scene_segment segments[5],
+        uint8_t* classes /* may be NULL */, int class_capacity, int* n_elevated);
+
 /* ---------------------------------------------------------------- a recorded drive into a map: sequence mode with products (addition within ABI v6)
  * mot_sequence_products_dev IS mot_sequence_dev — the same arguments, the same launch sequence — plus a bit set of products taken from every frame of the call in
  * the same asynchronous call (nothing is read back, no host synchronisation). products == 0 is mot_sequence_dev; products == MOT_SEQ_ACCUMULATE is
