@@ -163,7 +163,7 @@ EXPORTS = (
     "mot_set_track_accumulation", "mot_accumulate_track_points", "mot_sequence_accumulate_dev", "mot_track_accumulators_dev", "mot_get_accum_rows", "mot_get_track_accumulated",
     "mot_export_track_models_dev", "mot_get_track_models", "mot_export_track_model_voxels_dev", "mot_get_track_model_voxels",
     "mot_set_scene_grid", "mot_accumulate_scene", "mot_export_scene_grid_dev", "mot_get_scene_grid", "mot_sequence_products_dev",
-    "mot_export_scene_points_dev", "mot_get_scene_points",
+    "mot_export_scene_points_dev", "mot_get_scene_points", "mot_export_sequence_scene_points_dev", "mot_get_sequence_scene_points",
     "mot_gather_unique_id", "mot_gather_create", "mot_gather_contribute", "mot_gather_result", "mot_gather_synchronize", "mot_gather_destroy", "mot_gather_last_error",
 )
 ABI_VERSION = 6
@@ -487,6 +487,33 @@ class Context:
         self._ck(self.lib.mot_get_scene_points(self._h, int(slot), C.byref(p), _scene_mask(classes), _frame(frame), _vp(pts), cap, C.byref(npts), _vp(seg), _vp(cls), cap, C.byref(ne)))
         pts = pts[: npts.value]
         return dict(segments=seg, xyz=pts["xyz"].copy(), index=pts["index"].copy(), classes=cls[: ne.value].copy())
+
+    def export_sequence_scene_points_dev(self, frames: int, d_points_ptr: int, point_capacity: int, d_segments_ptr: int, d_totals_ptr: int, d_classes_ptr: int = 0,
+                                         class_stride: int = 0, min_static_hits: int = 1, trail=(1, 2), classes=None, frame=MOT_FRAME_GLOBAL):
+        """frames 0..frames-1 of the latest sequence_products_dev(scene=True) call judged against slot 0's grid as the whole drive left it
+        (mot_export_sequence_scene_points_dev) -> caller's device blocks: ONE block of 16-byte records for the drive, class-major (the classes of `classes` ascending,
+        inside a class the frames ascending, inside a frame input order), 8-byte d_totals[c] = {first, count} (the drive's run of class c) and d_segments[k * 5 + c]
+        (frame k's part of it, first absolute; SCENE_SEGMENT_DTYPE, first = -1 outside the mask, true counts) and, if given, class bytes d_classes[k * class_stride + i].
+        With classes=("known",) and frame="global" the records are the drive's static map. Reads the grid; asynchronous"""
+        p = MotSceneJudgeParams(int(min_static_hits), int(trail[0]), int(trail[1]))
+        self._ck(self.lib.mot_export_sequence_scene_points_dev(self._h, int(frames), C.byref(p), _scene_mask(classes), _frame(frame), C.c_void_p(d_points_ptr or None),
+                                                               C.c_long(point_capacity), C.c_void_p(d_segments_ptr or None), C.c_void_p(d_totals_ptr or None),
+                                                               C.c_void_p(d_classes_ptr or None), C.c_long(class_stride)))
+
+    def get_sequence_scene_points(self, frames: int, min_static_hits: int = 1, trail=(1, 2), classes=None, frame=MOT_FRAME_GLOBAL, with_classes: bool = True) -> dict:
+        """the same on the host (mot_get_sequence_scene_points; two calls: the counts, then the records): totals [5] and segments [frames, 5] (SCENE_SEGMENT_DTYPE),
+        xyz [n, 3] and index [n] of the selected classes, class-major over the drive, classes: a list of `frames` uint8 arrays (input order; None without with_classes)"""
+        p = MotSceneJudgeParams(int(min_static_hits), int(trail[0]), int(trail[1]))
+        mask, fr, F = _scene_mask(classes), _frame(frame), int(frames)
+        seg = np.zeros((max(F, 1), SCENE_CLASSES), SCENE_SEGMENT_DTYPE); tot = np.zeros(SCENE_CLASSES, SCENE_SEGMENT_DTYPE); n = C.c_long(0)
+        self._ck(self.lib.mot_get_sequence_scene_points(self._h, F, C.byref(p), mask, fr, None, C.c_long(0), C.byref(n), _vp(seg), _vp(tot), None, C.c_long(0)))
+        elevated = seg["count"].sum(axis=1)
+        stride = max(int(elevated.max()), 1)
+        pts = np.zeros(max(n.value, 1), TRACK_POINT_DTYPE); cls = np.zeros((F, stride), np.uint8) if with_classes else None
+        self._ck(self.lib.mot_get_sequence_scene_points(self._h, F, C.byref(p), mask, fr, _vp(pts), C.c_long(n.value), C.byref(n), _vp(seg), _vp(tot), _vp(cls), C.c_long(stride)))
+        pts = pts[: n.value]
+        return dict(totals=tot, segments=seg[:F], xyz=pts["xyz"].copy(), index=pts["index"].copy(),
+                    classes=[cls[k, : int(elevated[k])].copy() for k in range(F)] if with_classes else None)
 
     def get_scene_grid(self, slot: int = 0, cells: bool = True) -> dict:
         """one slot's grid on the host (mot_get_scene_grid): header (a SCENE_HEADER_DTYPE record) and cells [size, size] indexed (v, u) (SCENE_CELL_DTYPE;

@@ -1,5 +1,5 @@
 // mot_api_scene.hip — host side of the C-ABI (include/mot.h), the rolling static-scene grid: the setter and what it owns, the per-slot step counters, the state
-// checks of mot_accumulate_scene, the two readers, and the frame's points judged against the grid. Kernels: scene_grid.hip, scene_judge.hip. Context and helpers: mot_host.h.
+// checks of mot_accumulate_scene, the two readers, the frame's points and a recorded drive's points judged against the grid. Kernels: scene_grid.hip, scene_grid_seq.hip, scene_judge.hip, scene_judge_seq.hip. Context and helpers: mot_host.h.
 #include "mot_host.h"
 
 // The setter owns the feature's memory: cells, headers, previous origins, the argument block and its ring of page-locked staging blocks are allocated together and
@@ -20,6 +20,7 @@ static int seq_scene_release(mot_ctx* c) {
 // what mot_export_scene_points_dev took at its first call (all three or none) and the getter's staging block (the caller has drained the stream)
 static int judge_release(mot_ctx* c) {
   MOT_TRY(release(c, &c->d_sj_cls)); MOT_TRY(release(c, &c->d_sj_rows)); MOT_TRY(release(c, &c->d_sj_args));
+  MOT_TRY(release(c, &c->d_sjs_base)); MOT_TRY(release(c, &c->d_sjs_stage));   // (the drive's judge: its bases and its getter's staging block)
   return release(c, &c->d_sj_stage);
 }
 static size_t scene_arg_bytes(const mot_ctx* c) { return (size_t)c->batch * (sizeof(EgoTf) + sizeof(int)); }   // [batch] matrices, then [batch] step stamps
@@ -323,6 +324,135 @@ extern "C" int mot_get_scene_points(mot_ctx* c, int slot, const mot_scene_judge_
   if (classes && ne > class_capacity) return fail(c, MOT_E_CAPACITY, "more elevated points than the caller's class buffer holds");
   if (points && np > 0) MOT_HIP(c, hipMemcpyAsync(points, d_pts, (size_t)np * sizeof(mot_track_point), hipMemcpyDeviceToHost, c->stream));
   if (classes && ne > 0) MOT_HIP(c, hipMemcpyAsync(classes, d_cls, (size_t)ne, hipMemcpyDeviceToHost, c->stream));
+  MOT_HIP(c, hipStreamSynchronize(c->stream));
+  return MOT_OK;
+}
+
+// ---------------------------------------------------------------------------------------- a recorded drive's points judged against the grid it left (scene_judge_seq.hip)
+// Served while Residency::sequence_scene_frames() vouches for the slots and for slot 0's grid: the frames of the latest MOT_SEQ_SCENE call, nothing taken, emptied or
+// changed since. The judge's scratch (ensure_judge: sized for max_batch slots) and [max_batch][5] bases of the call's own; all of it or none.
+static int check_seq_judge(mot_ctx* c, const char* who, int frames) {
+  if (!c->track_links) return fail(c, MOT_E_STATE, who, ": track links are off (mot_set_track_links)");
+  const int held = c->res.sequence_scene_frames();
+  if (!held || !c->d_sgs_static)
+    return fail(c, MOT_E_STATE, who, ": slots 0 .. frames - 1 are not the frames of the latest mot_sequence_products_dev(MOT_SEQ_SCENE) call with stream 0's grid as that call left it "
+                                     "(no such call, or a fused or stage-wise call, a tracker step from outside, a reset, a load or the setter since)");
+  if (frames < 1 || frames > held) return fail(c, MOT_E_ARG, who, ": frames must lie in [1, frames of the sequence call]");
+  for (int b = 0; b < frames; b++)
+    if (!c->res.point_tracks_valid(b) || !c->res.sequence_frame(b) || c->res.elev_packed_at(b) != c->res.elev_packed_at(0))
+      return fail(c, MOT_E_STATE, who, ": a slot of the drive no longer holds its frame as the sequence call left it");
+  if ((long)frames * c->max_points > 2147483647L) return fail(c, MOT_E_ARG, who, ": frames * max_points exceeds 2^31 - 1 (places are int32)");
+  return MOT_OK;
+}
+static int ensure_seq_judge(mot_ctx* c, bool host_stage) {
+  const bool had = c->d_sj_cls && c->d_sj_rows && c->d_sj_args;
+  MOT_TRY(ensure_judge(c, false));
+  int rc = dev_alloc(c, &c->d_sjs_base, (size_t)c->batch * MOT_SCENE_CLASSES * sizeof(int));
+  if (!rc && host_stage) rc = dev_alloc(c, &c->d_sjs_stage, ((size_t)c->batch + 1) * MOT_SCENE_CLASSES * sizeof(mot_scene_segment));
+  if (rc) {   // all blocks or none: what this call took goes back (the per-frame judge's blocks stay if they were there before)
+    const std::string why = c->err;
+    (void)release(c, &c->d_sjs_base); (void)release(c, &c->d_sjs_stage);
+    if (!had) { (void)release(c, &c->d_sj_cls); (void)release(c, &c->d_sj_rows); (void)release(c, &c->d_sj_args); }
+    c->err = why;
+    return rc;
+  }
+  return MOT_OK;
+}
+struct SeqJudgeLaunch { SceneSplatInput in; SceneJudgeBuffers j; const EgoTf* d_tf; };
+// classify, the two scans and both tables; the matrices the frames' boxes took, in one stream-ordered copy ahead of the kernels (the cell test needs them in either frame)
+static int launch_seq_judge_count(mot_ctx* c, int frames, const mot_scene_judge_params* p, int class_mask, mot_scene_segment* d_segments, mot_scene_segment* d_totals,
+                                  uint8_t* d_classes, long class_stride, SeqJudgeLaunch* L) {
+  char* raw;
+  MOT_TRY(c->sg_ring.acquire(c, &raw));
+  memcpy(raw, c->link_tf.data(), (size_t)frames * sizeof(EgoTf));
+  MOT_TRY(c->sg_ring.commit(c, c->d_sj_args, 0, (size_t)frames * sizeof(EgoTf), c->stream));
+  L->d_tf = reinterpret_cast<const EgoTf*>(c->d_sj_args);
+  SceneSplatInput& in = L->in;
+  in.ids = c->d_point_track; in.elevated = c->d_elev; in.cap = c->cap; in.counts = c->d_counts; in.slot_of = nullptr; in.out = nullptr;   // (the kind comes from the captured bits)
+  in.T = c->max_tracks_total; in.E = c->max_tracks_ever;
+  in.elevated_packed = c->res.elev_packed_at(0) ? 1 : 0;   // (one layout: check_seq_judge)
+  SceneJudgeBuffers& j = L->j;
+  j.cls = c->d_sj_cls; j.rows = c->d_sj_rows; j.max_chunks = c->sj_chunks;
+  j.min_static_hits = p->min_static_hits; j.trail_num = p->trail_num; j.trail_den = p->trail_den; j.class_mask = class_mask;
+  mot_launch_scene_judge_seq_count(scene_buffers(c), in, j, seq_scene_buffers(c), c->d_sjs_base, frames, c->max_points, L->d_tf, d_segments, d_totals, d_classes, class_stride, c->stream);
+  MOT_HIP(c, hipGetLastError());
+  return MOT_OK;
+}
+
+extern "C" int mot_export_sequence_scene_points_dev(mot_ctx* c, int frames, const mot_scene_judge_params* p, int class_mask, int frame, mot_track_point* d_points, long point_capacity,
+                                                    mot_scene_segment* d_segments, mot_scene_segment* d_totals, uint8_t* d_classes, long class_stride) {
+  if (!c) return MOT_E_ARG;
+  MOT_GUARD(c);
+  const char* who = "mot_export_sequence_scene_points_dev";
+  MOT_TRY(check_scene_on(c, who));
+  MOT_TRY(check_judge_args(c, who, p, class_mask, frame));
+  if (!d_segments || !d_totals || point_capacity < 0 || class_stride < 0 || (!d_points && (point_capacity > 0 || class_mask)) ||
+      (((size_t)d_points | (size_t)d_segments | (size_t)d_totals) & 3))
+    return fail(c, MOT_E_ARG, who, ": bad argument (null segments or totals, a negative capacity or stride, null points with a capacity or a mask, a block off 4 bytes)");
+  MOT_TRY(check_seq_judge(c, who, frames));
+  MOT_TRY(ensure_seq_judge(c, false));
+  SeqJudgeLaunch L;
+  MOT_TRY(launch_seq_judge_count(c, frames, p, class_mask, d_segments, d_totals, d_classes, class_stride, &L));
+  mot_launch_scene_judge_seq_scatter(L.in, L.j, c->d_sjs_base, frames, c->max_points, L.d_tf, frame == MOT_FRAME_GLOBAL, d_points, point_capacity, c->stream);
+  MOT_HIP(c, hipGetLastError());
+  return MOT_OK;
+}
+
+extern "C" int mot_get_sequence_scene_points(mot_ctx* c, int frames, const mot_scene_judge_params* p, int class_mask, int frame, mot_track_point* points, long point_capacity,
+                                             long* n_points, mot_scene_segment* segments, mot_scene_segment totals[5], uint8_t* classes, long class_stride) {
+  if (!c) return MOT_E_ARG;
+  MOT_GUARD(c);
+  const char* who = "mot_get_sequence_scene_points";
+  MOT_TRY(check_scene_on(c, who));
+  MOT_TRY(check_judge_args(c, who, p, class_mask, frame));
+  if (!n_points || !segments || !totals || point_capacity < 0 || class_stride < 0)
+    return fail(c, MOT_E_ARG, who, ": a negative capacity or stride, or a null count, segment table or totals");
+  MOT_TRY(check_seq_judge(c, who, frames));
+  MOT_TRY(ensure_seq_judge(c, true));
+  // the counts first (they are always delivered); what fits the caller's buffers is decided here, and the records are scattered into a block of their own size
+  const size_t table = ((size_t)frames + 1) * MOT_SCENE_CLASSES * sizeof(mot_scene_segment);
+  mot_scene_segment* d_seg = reinterpret_cast<mot_scene_segment*>(c->d_sjs_stage);
+  mot_scene_segment* d_tot = d_seg + (size_t)frames * MOT_SCENE_CLASSES;
+  SeqJudgeLaunch L;
+  MOT_TRY(launch_seq_judge_count(c, frames, p, class_mask, d_seg, d_tot, nullptr, 0, &L));
+  char* pin;
+  MOT_TRY(pinned_scratch(c, table, &pin));
+  MOT_HIP(c, hipMemcpyAsync(pin, d_seg, table, hipMemcpyDeviceToHost, c->stream));
+  MOT_HIP(c, hipStreamSynchronize(c->stream));
+  const mot_scene_segment* h = reinterpret_cast<const mot_scene_segment*>(pin);
+  const mot_scene_segment* ht = h + (size_t)frames * MOT_SCENE_CLASSES;
+  std::vector<long> elevated(frames, 0);
+  long np = 0, widest = 0;
+  for (int k = 0; k < frames; k++) {
+    for (int cc = 0; cc < MOT_SCENE_CLASSES; cc++) {
+      const int n = h[k * MOT_SCENE_CLASSES + cc].count;
+      if (n < 0 || n > c->cap) return fail(c, MOT_E_STATE, who, ": inconsistent counts");
+      elevated[k] += n;
+    }
+    if (elevated[k] > c->cap) return fail(c, MOT_E_STATE, who, ": inconsistent counts");
+    widest = elevated[k] > widest ? elevated[k] : widest;
+  }
+  for (int cc = 0; cc < MOT_SCENE_CLASSES; cc++)
+    if ((class_mask >> cc) & 1) np += ht[cc].count;
+  if (np < 0 || np > (long)frames * c->cap) return fail(c, MOT_E_STATE, who, ": inconsistent counts");
+  memcpy(segments, h, (size_t)frames * MOT_SCENE_CLASSES * sizeof(mot_scene_segment));
+  memcpy(totals, ht, MOT_SCENE_CLASSES * sizeof(mot_scene_segment));
+  *n_points = np;
+  if (points && np > point_capacity) return fail(c, MOT_E_CAPACITY, "more selected points than the caller's point buffer holds");
+  if (classes && widest > class_stride) return fail(c, MOT_E_CAPACITY, "a frame has more elevated points than the caller's class_stride");
+  if (points && np > 0) {   // a block of this call's own, as large as the records (a getter's convenience: the export is the hot path)
+    mot_track_point* d_pts = nullptr;
+    MOT_TRY(dev_alloc(c, &d_pts, (size_t)np * sizeof(mot_track_point)));
+    mot_launch_scene_judge_seq_scatter(L.in, L.j, c->d_sjs_base, frames, c->max_points, L.d_tf, frame == MOT_FRAME_GLOBAL, d_pts, np, c->stream);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(points, d_pts, (size_t)np * sizeof(mot_track_point), hipMemcpyDeviceToHost, c->stream);
+    const hipError_t e2 = hipStreamSynchronize(c->stream);
+    MOT_TRY(release(c, &d_pts));
+    MOT_HIP_AS(c, "mot_get_sequence_scene_points: the records", e != hipSuccess ? e : e2);
+  }
+  if (classes)   // frame k's class bytes from where the classify kernel left them, as many as the frame has points
+    for (int k = 0; k < frames; k++)
+      if (elevated[k] > 0) MOT_HIP(c, hipMemcpyAsync(classes + (size_t)k * class_stride, c->d_sj_cls + (size_t)k * c->cap, (size_t)elevated[k], hipMemcpyDeviceToHost, c->stream));
   MOT_HIP(c, hipStreamSynchronize(c->stream));
   return MOT_OK;
 }

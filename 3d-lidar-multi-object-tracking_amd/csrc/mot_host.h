@@ -30,6 +30,8 @@
 //   links_switched (mot_set_track_links)                                           all         links -> None (no step since)
 //   (fused_batch and box_stage also record `regrouped`: whether the box stage ran on the cluster-ordered copy, MOT_ORDER_ANY; every transition that clears `boxes` clears it)
 //   sequence_accumulated (mot_sequence_accumulate_dev, behind its fused_batch)      0..frames-1 `accumulated`: the frames are in stream 0's accumulators; they stay `sequence` slots
+//   sequence_scene_taken (mot_sequence_products_dev(MOT_SEQ_SCENE), behind its fused_batch)  0..frames-1 `scene`, and scene_drive = frames: the drive can be judged until ANY
+//                                                                                 transition above but labels_written / compaction_rerun, a scene restart or mot_accumulate_scene
 //   compaction_rerun (mot_get_ground on demand, mot_time_stage)                    0..batch-1  as run       -                             -      as run, unless Foreign        -
 //   describe_batch (set_batch): the last_* input description. Nothing is vouched for in a slot at or beyond last_batch that needs the batch's input.
 // per-point labels: not computed, the cloud was uploaded by a stage-wise call (no cell codes: mot_get_clusters computes them from the points) / not computed, cloud and cell
@@ -60,7 +62,10 @@ struct Residency {
   bool last_fused = false;                // the last ground launch was a fused one (input, cells and thresholds of the batch still resident)
   int last_batch = 0, last_max_n = 0;     // the last ground launch's geometry and input: what a re-run of its compaction needs
   const float4* last_in = nullptr; long last_in_stride = 0;
-  void reset(int batch) { slots.assign(batch, SlotState()); }
+  // frames of the latest mot_sequence_products_dev(MOT_SEQ_SCENE) call while slots 0 .. scene_drive - 1 still hold them and slot 0's grid is as that call left it
+  // (mot_export_sequence_scene_points_dev judges exactly that); 0: no such call, or a slot was taken / stream 0's grid was emptied or changed since
+  int scene_drive = 0;
+  void reset(int batch) { slots.assign(batch, SlotState()); scene_drive = 0; }
   void describe_batch(int batch, int max_n, const float4* in, long stride) { last_batch = batch; last_max_n = max_n; last_in = in; last_in_stride = stride; }
   static bool fused_packs(int outputs) { return MOT_PACKED_ELEVATED && !(outputs & MOT_OUT_GROUND); }   // the elevated-only compaction leaves 12-byte points
   static bool fused_keeps_ground(int outputs) { return (outputs & (MOT_OUT_GROUND | MOT_OUT_MASK)) == (MOT_OUT_GROUND | MOT_OUT_MASK); }
@@ -69,29 +74,29 @@ struct Residency {
   // linked: the call runs the tracker with mot_set_track_links on
   // one_stream: mot_sequence_dev. Every fused call gives the slot a new step: `accumulated` starts over
   void fused_batch(int batch, int outputs, bool regrouped, bool linked, bool one_stream = false) {
-    last_fused = true;
+    last_fused = true; scene_drive = 0;
     for (int b = 0; b < batch; b++)
       slots[b] = {fused_packs(outputs), (outputs & MOT_OUT_LABELS) ? kLabelsReady : kLabelsFromCells, true, fused_keeps_ground(outputs) ? kGroundResident : kGroundNone, regrouped,
                   linked ? kLinksPoints : unlinked(slots[b].links), one_stream, false};
   }
   static LinkState unlinked(LinkState l) { return l == kLinksPoints ? kLinksBoxes : l; }   // the slot's cloud or boxes are being replaced: its owner row stays the last tracker step's
   // a stage-wise ground stage ran on slot 0 (float4 records); without a mask a later mot_get_ground that asks for one answers MOT_E_STATE
-  void ground_stage(bool with_mask) { last_fused = false; slots[0] = {false, kLabelsFromPoints, false, with_mask ? kGroundResident : kGroundNone, false, unlinked(slots[0].links)}; }
+  void ground_stage(bool with_mask) { last_fused = false; scene_drive = 0; slots[0] = {false, kLabelsFromPoints, false, with_mask ? kGroundResident : kGroundNone, false, unlinked(slots[0].links)}; }
   // slot 0 now holds a stage-wise cluster / box call's cloud, as float4 records: mot_get_ground must not re-run a fused batch's compaction over it, slot 0's ground cloud / mask (if any) are another
   // cloud's (mot_get_ground(0) answers MOT_E_STATE, as include/mot.h promises), what an earlier label kernel or box stage left is stale (mot_box_markers: MOT_E_STATE). The caller then states what it produced.
-  void slot0_taken() { last_fused = false; slots[0] = {false, kLabelsFromPoints, false, kGroundForeign, false, unlinked(slots[0].links)}; }
+  void slot0_taken() { last_fused = false; scene_drive = 0; slots[0] = {false, kLabelsFromPoints, false, kGroundForeign, false, unlinked(slots[0].links)}; }
   // the label kernel ran on the slot's cloud; written = false: in the fused geometry without per-point labels (mot_time_stage)
   void labels_written(int slot, bool written = true) { slots[slot].labels = written ? kLabelsReady : kLabelsFromCells; }
   // the box stage (label kernel included) ran on the slot's cloud: mot_box_markers / mot_get_boxes / mot_get_clusters may read its products
-  void box_stage(int slot, bool regrouped) { slots[slot].labels = kLabelsReady; slots[slot].boxes = true; slots[slot].regrouped = regrouped; }
+  void box_stage(int slot, bool regrouped) { scene_drive = 0; slots[slot].labels = kLabelsReady; slots[slot].boxes = true; slots[slot].regrouped = regrouped; }
   // the compaction of the last batch was run again: same points in the same order (what the later stages hold stays valid), in the layout and with the outputs
   // of this run. (A slot a stage-wise call has taken since stays refused: only mot_time_stage gets here in that state.)
   void compaction_rerun(int batch, bool packed, bool ground_and_mask) {
     for (int b = 0; b < batch; b++) { slots[b].packed = packed; if (slots[b].ground != kGroundForeign) slots[b].ground = ground_and_mask ? kGroundResident : kGroundNone; }
   }
   // a tracker step fed from outside the fused path ran on the slot (links on): its owner row is that step's, over the caller's box list
-  void tracker_fed(int slot) { slots[slot].links = kLinksBoxes; }
-  void links_switched() { for (auto& s : slots) s.links = kLinksNone; }
+  void tracker_fed(int slot) { slots[slot].links = kLinksBoxes; scene_drive = 0; }
+  void links_switched() { for (auto& s : slots) s.links = kLinksNone; scene_drive = 0; }
   bool box_tracks_valid(int slot) const { return slots[slot].links != kLinksNone; }
   bool point_tracks_valid(int slot) const { return slots[slot].links == kLinksPoints; }
   bool sequence_frame(int slot) const { return slots[slot].sequence; }
@@ -100,11 +105,14 @@ struct Residency {
   // mot_sequence_accumulate_dev has appended the frames the slots hold to stream 0's accumulators (they stay sequence slots: no call appends them again)
   void sequence_accumulated(int frames) { for (int b = 0; b < frames; b++) slots[b].accumulated = true; }
   bool scene_done(int slot) const { return slots[slot].scene; }
-  void scene_taken(int slot) { slots[slot].scene = true; }
-  void scene_restarted(int slot) { slots[slot].scene = true; slots[slot].scene_restarted = true; }   // the slot's stream was reset or loaded, or the setter emptied the grids
+  void scene_taken(int slot) { slots[slot].scene = true; scene_drive = 0; }
+  void scene_restarted(int slot) { slots[slot].scene = true; slots[slot].scene_restarted = true; scene_drive = 0; }   // the slot's stream was reset or loaded, or the setter emptied the grids
   bool scene_judgeable(int slot) const { return !slots[slot].scene_restarted; }   // (taken or not: judging a step is legal before and after mot_accumulate_scene)
   // mot_sequence_products_dev(MOT_SEQ_SCENE) has taken the frames the slots hold into stream 0's grid (they stay sequence slots: no call takes them again)
-  void sequence_scene_taken(int frames) { for (int b = 0; b < frames; b++) slots[b].scene = true; }
+  void sequence_scene_taken(int frames) { for (int b = 0; b < frames; b++) slots[b].scene = true; scene_drive = frames; }
+  // the frames a drive's judge may cover: every transition that takes a slot (a fused or stage-wise call, a tracker step from outside, the links switched) or that empties
+  // or changes a grid (the setter, a reset, a load, mot_accumulate_scene) ends it — any slot's, which is more than needed and costs nothing
+  int sequence_scene_frames() const { return scene_drive; }
   bool elev_packed_at(int slot) const { return slots[slot].packed; }
   bool labels_ready(int slot) const { return slots[slot].labels == kLabelsReady; }
   bool cells_usable(int slot) const { return slots[slot].labels == kLabelsFromCells; }
@@ -287,6 +295,9 @@ struct mot_ctx {
   // mot_sequence_products_dev(MOT_SEQ_SCENE) (scene_grid_seq.hip): allocated at its first call, both or neither; released with the blocks above
   SceneSeqFrame* d_sgs_win = nullptr;      // [batch + 1] every frame's window and what is left of it at the end of the call; entry 0: the window before the call
   unsigned* d_sgs_static = nullptr;        // [batch][(E + 31) / 32] per frame one bit per track id: flagged static as that frame's step left it
+  // mot_export_sequence_scene_points_dev / mot_get_sequence_scene_points (scene_judge_seq.hip): the judge's scratch above, and at the first call of these
+  int* d_sjs_base = nullptr;               // [batch][5] a frame's points per class, then where its first record of the class goes in the drive's block
+  char* d_sjs_stage = nullptr;             // the getter: [batch][5] + [5] segments before they go to the host (allocated at ITS first call)
   std::vector<EgoTf> link_tf;          // [batch] the matrix every slot's boxes took in its last fused call with the tracker, kept while links are on (host side)
   Vec2d* d_cp = nullptr;
   TrackItem* d_items = nullptr;

@@ -522,6 +522,14 @@ struct SceneJudgeBuffers {
 // sensor -> global matrices of the launch; global != 0: the records carry global coordinates. points / classes may be null
 void mot_launch_scene_judge(const SceneGridBuffers& g, const SceneSplatInput& in, const SceneJudgeBuffers& j, int first, int batch, int max_n, const EgoTf* tf, int global,
                             mot_track_point* points, long point_stride, mot_scene_segment* segments, uint8_t* classes, long class_stride, hipStream_t stream);
+// A recorded drive's points judged against the grid it left (scene_judge_seq.hip, mot_export_sequence_scene_points_dev): slots 0 .. frames - 1 = the frames of the
+// latest MOT_SEQ_SCENE call against SLOT 0's grid, the records class-major over the drive. bases: [frames][5] ints of scratch (a frame's totals, then its drive-wide
+// places); s.is_static: that call's bit rows (s.win / s.step0 are not read); tf: [frames] matrices. count: classify, the scan per frame and the scan over frames — the
+// class bytes, j.rows, bases and both tables; scatter (behind count, same j and bases): the records — nothing is launched without a mask or room for records
+void mot_launch_scene_judge_seq_count(const SceneGridBuffers& g, const SceneSplatInput& in, const SceneJudgeBuffers& j, const SceneSeqBuffers& s, int* bases, int frames, int max_n,
+                                      const EgoTf* tf, mot_scene_segment* segments, mot_scene_segment* totals, uint8_t* classes, long class_stride, hipStream_t stream);
+void mot_launch_scene_judge_seq_scatter(const SceneSplatInput& in, const SceneJudgeBuffers& j, const int* bases, int frames, int max_n, const EgoTf* tf, int global,
+                                        mot_track_point* points, long capacity, hipStream_t stream);
 
 #ifdef MOT_HIPEMU
 #define MOT_WAVE_SYNC() ((void)__ballot(1))

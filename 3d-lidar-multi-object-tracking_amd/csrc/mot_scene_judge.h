@@ -1,0 +1,101 @@
+// mot_scene_judge.h — device helpers the judge kernels of scene_judge.hip (every slot against its own grid) and scene_judge_seq.hip (a recorded drive against slot 0's
+// grid) share: THE class rule of a cell, the ballots that count and rank a wave's points by class, the scan over a frame's chunks, the chain over a chunk's tiles and the
+// record store. One definition, so that the last frame of a drive gets the very bytes the frame-by-frame route gives it (include/mot.h). Product code.
+#ifndef MOT_SCENE_JUDGE_H_
+#define MOT_SCENE_JUDGE_H_
+#include "mot_scene_splat.h"   // the per-point step shared with the splat kernels
+
+static_assert(sizeof(mot_scene_segment) == 8 && sizeof(mot_track_point) == 16, "include/mot.h documents the sizes");
+static_assert(MOT_SCENE_CLASSES == 5 && MOT_SCENE_KNOWN < 8, "a class is three bits");
+
+constexpr int kSjWaves = kSceneBlock / 64;
+constexpr int kSjTiles = kSceneChunk / 64;   // tile k * kSjWaves + wave of a chunk: item k of that wave
+constexpr int kSjNone = 7;                   // the class bits of a lane without a point
+
+__device__ __forceinline__ int sj_count(const SceneSplatInput& in, int b) {
+  const int n = in.counts[b * kCountsStride + kCntElev];
+  return n < 0 ? 0 : (n < (int)in.cap ? n : (int)in.cap);
+}
+// the lanes of the wave that hold class c, from the ballots of the three class bits (a lane without a point holds kSjNone)
+__device__ __forceinline__ unsigned long long sj_lanes_of(int c, unsigned long long b0, unsigned long long b1, unsigned long long b2) {
+  return ((c & 1) ? b0 : ~b0) & ((c & 2) ? b1 : ~b1) & ((c & 4) ? b2 : ~b2);
+}
+
+// THE class rule: dynamic by the grid's kind rule -> MOVING; no cell (at < 0) -> UNKNOWN; else ONE 8-byte load of the cell's two counters and the 64-bit trail test
+__device__ __forceinline__ int sj_class(int dynamic, int at, const SceneCell* __restrict__ cells, const SceneJudgeBuffers& j) {
+  int c = MOT_SCENE_UNKNOWN;
+  if (dynamic) c = MOT_SCENE_MOVING;
+  else if (at >= 0) {
+    const uint2 h = *reinterpret_cast<const uint2*>(cells + at);   // {static_hits, dynamic_hits}
+    const unsigned long long s = h.x, d = h.y;
+    const bool trail = d > 0 && d * j.trail_den > (s + d) * j.trail_num;   // < 2^33 * 2^16: exact
+    c = trail ? MOT_SCENE_TRAIL : (h.x < j.min_static_hits ? MOT_SCENE_NEW : MOT_SCENE_KNOWN);
+  }
+  return c;
+}
+// the wave's points per class, added to count[] (uniform over the wave). EVERY lane of the wave calls this
+__device__ __forceinline__ void sj_tally(int bits, int (&count)[MOT_SCENE_CLASSES]) {
+  const unsigned long long a0 = __ballot(bits & 1), a1 = __ballot(bits & 2), a2 = __ballot(bits & 4);
+#pragma unroll
+  for (int cc = 0; cc < MOT_SCENE_CLASSES; cc++) count[cc] += __popcll(sj_lanes_of(cc, a0, a1, a2));
+}
+// the waves' counts merged through LDS into the chunk's row (plain stores). EVERY thread of the workgroup calls this
+__device__ __forceinline__ void sj_store_counts(int (*s_cnt)[MOT_SCENE_CLASSES], const int (&count)[MOT_SCENE_CLASSES], int* __restrict__ row, int tid, int lane, int wave) {
+  if (lane == 0) {
+#pragma unroll
+    for (int cc = 0; cc < MOT_SCENE_CLASSES; cc++) s_cnt[wave][cc] = count[cc];
+  }
+  __syncthreads();
+  if (tid < MOT_SCENE_CLASSES) {
+    int sum = 0;
+#pragma unroll
+    for (int w = 0; w < kSjWaves; w++) sum += s_cnt[w][tid];
+    row[tid] = sum;
+  }
+}
+
+// rows[chunk][c] (counts) -> rows[chunk][5 + c]: per class the exclusive scan over the frame's chunks (the DPP wave scans of mot_wave.h), s_total[c] = the class's points
+// (readable behind the caller's barrier). Chunks tid, tid + 256, ... per thread; every lane takes part in every scan.
+__device__ __forceinline__ void sj_scan_chunks(int* __restrict__ rows, int chunks, int* s_part, int* s_total, int tid, int lane, int wave) {
+  for (int c = 0; c < MOT_SCENE_CLASSES; c++) {
+    int carry = 0;   // the class's points in the chunks of earlier rounds
+    for (int r0 = 0; r0 < chunks; r0 += kSceneBlock) {   // (uniform)
+      const int ch = r0 + tid;
+      const int v = ch < chunks ? rows[(long)ch * kSceneJudgeRow + c] : 0;
+      const int incl = wave_scan_incl_i32(v);
+      if (lane == 63) s_part[wave] = incl;
+      __syncthreads();
+      int first = carry + incl - v, total = 0;
+      for (int w = 0; w < kSjWaves; w++) { if (w < wave) first += s_part[w]; total += s_part[w]; }
+      carry += total;
+      __syncthreads();   // (s_part is written again in the next round)
+      if (ch < chunks) rows[(long)ch * kSceneJudgeRow + MOT_SCENE_CLASSES + c] = first;
+    }
+    if (tid == 0) s_total[c] = carry;
+  }
+}
+
+// the in-chunk ranking, a wave's share: the lane's rank among the points of its class inside the 64-point tile, and the tile's five counts into the LDS table
+__device__ __forceinline__ int sj_rank(int cls, int tile, int lane, unsigned long long below, int (*s_cnt)[MOT_SCENE_CLASSES]) {
+  const unsigned long long a0 = __ballot(cls & 1), a1 = __ballot(cls & 2), a2 = __ballot(cls & 4);
+  if (lane < MOT_SCENE_CLASSES) s_cnt[tile][lane] = __popcll(sj_lanes_of(lane, a0, a1, a2));
+  return __popcll(sj_lanes_of(cls, a0, a1, a2) & below);
+}
+// ... and thread c < 5 chains the chunk's tiles of class c, in index order, from where the chunk's first record of the class goes
+__device__ __forceinline__ void sj_chain(const int (*s_cnt)[MOT_SCENE_CLASSES], int (*s_at)[MOT_SCENE_CLASSES], int c, int run) {
+  for (int t = 0; t < kSjTiles; t++) { s_at[t][c] = run; run += s_cnt[t][c]; }
+}
+// one 16-byte record {x, y, z, index}: the point's bits, or (global) mot_track_place.h's sensor -> global step — fp32, left to right; the build has -ffp-contract=off:
+// the bits mot_export_track_points_dev writes
+__device__ __forceinline__ void sj_store_record(mot_track_point* __restrict__ at, bool vec_out, bool global, const EgoTf& m, const float4& q, int index) {
+  float4 o;
+  if (global) {
+    o.x = m.m[0] * q.x + m.m[1] * q.y + m.m[2] * q.z + m.m[3];
+    o.y = m.m[4] * q.x + m.m[5] * q.y + m.m[6] * q.z + m.m[7];
+    o.z = m.m[8] * q.x + m.m[9] * q.y + m.m[10] * q.z + m.m[11];
+  } else { o.x = q.x; o.y = q.y; o.z = q.z; }
+  o.w = __int_as_float(index);
+  if (vec_out) *reinterpret_cast<float4*>(at) = o;
+  else { float* p = reinterpret_cast<float*>(at); p[0] = o.x; p[1] = o.y; p[2] = o.z; p[3] = o.w; }
+}
+#endif

@@ -22,23 +22,9 @@
 // track slot outside [0, T) is not followed (the point then counts as dynamic, as in the splat kernel); chunk rows are indexed below the slot's chunk capacity; a
 // record is stored only below min(point_stride, selected records), a class byte only below class_stride.
 // Resources (tools/kernel_resources.py): no scratch; LDS 80 bytes (J1), 48 (J2), 1280 (J3); 68 / 13 / 101 VGPRs. Cost: profiles/scene_judge.md.
-#include "mot_scene_splat.h"   // the per-point step shared with the splat kernels
-
-static_assert(sizeof(mot_scene_segment) == 8 && sizeof(mot_track_point) == 16, "include/mot.h documents the sizes");
-static_assert(MOT_SCENE_CLASSES == 5 && MOT_SCENE_KNOWN < 8, "a class is three bits");
-
-constexpr int kSjWaves = kSceneBlock / 64;
-constexpr int kSjTiles = kSceneChunk / 64;   // tile k * kSjWaves + wave of a chunk: item k of that wave
-constexpr int kSjNone = 7;                   // the class bits of a lane without a point
-
-__device__ __forceinline__ int sj_count(const SceneSplatInput& in, int b) {
-  const int n = in.counts[b * kCountsStride + kCntElev];
-  return n < 0 ? 0 : (n < (int)in.cap ? n : (int)in.cap);
-}
-// the lanes of the wave that hold class c, from the ballots of the three class bits (a lane without a point holds kSjNone)
-__device__ __forceinline__ unsigned long long sj_lanes_of(int c, unsigned long long b0, unsigned long long b1, unsigned long long b2) {
-  return ((c & 1) ? b0 : ~b0) & ((c & 2) ? b1 : ~b1) & ((c & 4) ? b2 : ~b2);
-}
+// The class rule, the ballots, the scan over chunks, the tile chain and the record store live in mot_scene_judge.h: scene_judge_seq.hip (a recorded drive judged against
+// slot 0's grid) runs the same inline functions, so that the last frame of a drive gets these kernels' bytes.
+#include "mot_scene_judge.h"   // the class rule, the ballots, the scans and the record store shared with scene_judge_seq.hip (and, through it, mot_scene_splat.h)
 
 // ------------------------------------------------------------------------------------------ J1
 __global__ void MOT_SG_BOUNDS(kSceneBlock)
@@ -83,34 +69,14 @@ scene_judge_classify_kernel(SceneGridBuffers g, SceneSplatInput in, SceneJudgeBu
     }
     float gz;
     const int at = scene_point_cell(m, q[k], inv, valid && window_ok, window, W, &gz);   // (mot_scene_splat.h)
-    int c = MOT_SCENE_UNKNOWN;
-    if (dynamic) c = MOT_SCENE_MOVING;
-    else if (at >= 0) {
-      const uint2 h = *reinterpret_cast<const uint2*>(cells + at);   // {static_hits, dynamic_hits}
-      const unsigned long long s = h.x, d = h.y;
-      const bool trail = d > 0 && d * j.trail_den > (s + d) * j.trail_num;   // < 2^33 * 2^16: exact
-      c = trail ? MOT_SCENE_TRAIL : (h.x < j.min_static_hits ? MOT_SCENE_NEW : MOT_SCENE_KNOWN);
-    }
+    const int c = sj_class(dynamic, at, cells, j);
     if (valid) {
       cls_out[i] = (uint8_t)c;
       if (user && i < class_stride) user[i] = (uint8_t)c;
     }
-    const int bits = valid ? c : kSjNone;
-    const unsigned long long a0 = __ballot(bits & 1), a1 = __ballot(bits & 2), a2 = __ballot(bits & 4);
-#pragma unroll
-    for (int cc = 0; cc < MOT_SCENE_CLASSES; cc++) count[cc] += __popcll(sj_lanes_of(cc, a0, a1, a2));
+    sj_tally(valid ? c : kSjNone, count);
   }
-  if (lane == 0) {
-#pragma unroll
-    for (int cc = 0; cc < MOT_SCENE_CLASSES; cc++) s_cnt[wave][cc] = count[cc];
-  }
-  __syncthreads();
-  if (tid < MOT_SCENE_CLASSES) {
-    int sum = 0;
-#pragma unroll
-    for (int w = 0; w < kSjWaves; w++) sum += s_cnt[w][tid];
-    j.rows[((long)b * j.max_chunks + blockIdx.x) * kSceneJudgeRow + tid] = sum;
-  }
+  sj_store_counts(s_cnt, count, j.rows + ((long)b * j.max_chunks + blockIdx.x) * kSceneJudgeRow, tid, lane, wave);
 }
 
 // ------------------------------------------------------------------------------------------ J2
@@ -125,22 +91,7 @@ scene_judge_scan_kernel(SceneSplatInput in, SceneJudgeBuffers j, int b0, mot_sce
   int chunks = (n + kSceneChunk - 1) / kSceneChunk;
   if (chunks > j.max_chunks) chunks = j.max_chunks;
   int* __restrict__ rows = j.rows + (long)b * j.max_chunks * kSceneJudgeRow;
-  for (int c = 0; c < MOT_SCENE_CLASSES; c++) {
-    int carry = 0;   // the class's points in the chunks of earlier rounds
-    for (int r0 = 0; r0 < chunks; r0 += kSceneBlock) {   // (uniform)
-      const int ch = r0 + tid;
-      const int v = ch < chunks ? rows[(long)ch * kSceneJudgeRow + c] : 0;
-      const int incl = wave_scan_incl_i32(v);
-      if (lane == 63) s_part[wave] = incl;
-      __syncthreads();
-      int first = carry + incl - v, total = 0;
-      for (int w = 0; w < kSjWaves; w++) { if (w < wave) first += s_part[w]; total += s_part[w]; }
-      carry += total;
-      __syncthreads();   // (s_part is written again in the next round)
-      if (ch < chunks) rows[(long)ch * kSceneJudgeRow + MOT_SCENE_CLASSES + c] = first;
-    }
-    if (tid == 0) s_total[c] = carry;
-  }
+  sj_scan_chunks(rows, chunks, s_part, s_total, tid, lane, wave);
   __syncthreads();
   int first_of[MOT_SCENE_CLASSES];
   int run = 0;
@@ -196,15 +147,10 @@ scene_judge_scatter_kernel(SceneSplatInput in, SceneJudgeBuffers j, int b0, cons
   int rank[kSceneItems];
 #pragma unroll
   for (int k = 0; k < kSceneItems; k++) {   // tile k * 4 + wave of the chunk: points 64 * tile .. 64 * tile + 63
-    const unsigned long long a0 = __ballot(cls[k] & 1), a1 = __ballot(cls[k] & 2), a2 = __ballot(cls[k] & 4);
-    rank[k] = __popcll(sj_lanes_of(cls[k], a0, a1, a2) & below);
-    if (lane < MOT_SCENE_CLASSES) s_cnt[k * kSjWaves + wave][lane] = __popcll(sj_lanes_of(lane, a0, a1, a2));
+    rank[k] = sj_rank(cls[k], k * kSjWaves + wave, lane, below, s_cnt);
   }
   __syncthreads();
-  if (tid < MOT_SCENE_CLASSES) {   // the chunk's tiles in index order
-    int run = row[MOT_SCENE_CLASSES + tid];
-    for (int t = 0; t < kSjTiles; t++) { s_at[t][tid] = run; run += s_cnt[t][tid]; }
-  }
+  if (tid < MOT_SCENE_CLASSES) sj_chain(s_cnt, s_at, tid, row[MOT_SCENE_CLASSES + tid]);   // the chunk's tiles in index order
   __syncthreads();
   const EgoTf m = tf ? tf[kb] : EgoTf();
 #pragma unroll
@@ -213,15 +159,7 @@ scene_judge_scatter_kernel(SceneSplatInput in, SceneJudgeBuffers j, int b0, cons
     if (cls[k] >= MOT_SCENE_CLASSES || !((j.class_mask >> cls[k]) & 1)) continue;
     const long dst = (long)s_at[k * kSjWaves + wave][cls[k]] + rank[k];
     if (dst >= point_stride) continue;   // (dst < n while the rows are this call's; never a store outside the slot's records)
-    float4 o;
-    if (tf) {   // fp32, left to right; the build has -ffp-contract=off (mot_track_place.h's sensor -> global step: the bits mot_export_track_points_dev writes)
-      o.x = m.m[0] * q[k].x + m.m[1] * q[k].y + m.m[2] * q[k].z + m.m[3];
-      o.y = m.m[4] * q[k].x + m.m[5] * q[k].y + m.m[6] * q[k].z + m.m[7];
-      o.z = m.m[8] * q[k].x + m.m[9] * q[k].y + m.m[10] * q[k].z + m.m[11];
-    } else { o.x = q[k].x; o.y = q[k].y; o.z = q[k].z; }
-    o.w = __int_as_float((int)i);
-    if (vec_out) *reinterpret_cast<float4*>(out + dst) = o;
-    else { float* p = reinterpret_cast<float*>(out + dst); p[0] = o.x; p[1] = o.y; p[2] = o.z; p[3] = o.w; }
+    sj_store_record(out + dst, vec_out, tf != nullptr, m, q[k], (int)i);
   }
 }
 

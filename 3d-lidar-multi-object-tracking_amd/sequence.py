@@ -109,3 +109,44 @@ def play_fused(ctx, frames, dt_us: float = 1.0e5, t0: float = 1.0e9, slot_count:
     finally:
         ctx.synchronize()
         ctx.lib.mot_host_free(hp)
+
+
+def _torch_upload(host: np.ndarray):
+    import torch
+    d = torch.from_numpy(host).cuda()
+    return d.data_ptr(), d
+
+
+def play_static_map(ctx, frames, dt_us: float = 1.0e5, t0: float = 1.0e9, classes=("known",), frame: str = "global", min_static_hits: int = 1, trail=(1, 2),
+                    upload=None) -> list:
+    """A recorded drive into its static map on the SEQUENCE path: the drive is cut into pieces of at most `ctx.max_batch` frames, each piece goes through
+    `Context.sequence_products_dev(scene=True)` (one asynchronous call: stateless stages batched, tracker steps chained, every frame into stream 0's scene grid) and is
+    judged right behind its call with `Context.get_sequence_scene_points`. Needs `set_track_links(True)` and `set_scene_grid(...)` on the context.
+
+    EACH PIECE IS JUDGED AGAINST THE GRID SO FAR: the frames of piece p see every frame of pieces 0..p (their own piece with hindsight), not the pieces behind them.
+    A drive that fits one call (`max_batch >= len(frames)`) is judged against the whole drive.
+
+    frames: a sequence of (cloud, v, yaw), clouds (n, 4) float32. upload: host array -> (device pointer, an object that keeps the block alive); default: through torch.
+    Returns one `get_sequence_scene_points` dict per piece (totals, segments, xyz, index, classes) with `first_frame` added; with the defaults `xyz` of the pieces,
+    concatenated, is the drive's static map in the global frame — movers and their trails cut out."""
+    upload = upload or _torch_upload
+    frames = list(frames)
+    stride = ctx.max_points
+    out = []
+    for k0 in range(0, len(frames), ctx.max_batch):
+        piece = frames[k0: k0 + ctx.max_batch]
+        host = np.zeros((len(piece), stride, 4), np.float32)
+        n = []
+        for k, (cloud, _v, _yaw) in enumerate(piece):
+            a = np.asarray(cloud, np.float32).reshape(-1, 4)
+            if len(a) > stride:
+                raise ValueError(f"frame {k0 + k}: {len(a)} points, the context holds {stride}")
+            host[k, : len(a)] = a
+            n.append(len(a))
+        ptr, keep = upload(host)
+        ctx.sequence_products_dev(ptr, stride * 4, n, [t0 + (k0 + k) * dt_us for k in range(len(piece))], [p[1] for p in piece], [p[2] for p in piece], scene=True)
+        r = ctx.get_sequence_scene_points(len(piece), min_static_hits=min_static_hits, trail=trail, classes=classes, frame=frame)   # (synchronises: `keep` may go)
+        r["first_frame"] = k0
+        out.append(r)
+        del keep
+    return out

@@ -831,6 +831,49 @@ int mot_sequence_products_dev(mot_ctx* ctx, const float* d_xyzw, long frame_stri
                               const double* timestamps, const double* ego_v, const double* ego_yaw,
                               void* d_tracks, int max_per_frame, int32_t* d_counts, int products);
 
+/* ---------------------------------------------------------------- a drive's points judged against its grid: the static map in one call (additions within ABI v6)
+ * The sequence-mode twin of mot_export_scene_points_dev. Behind a mot_sequence_products_dev call with MOT_SEQ_SCENE, EVERY frame of that call is judged against
+ * slot 0's grid AS THE WHOLE DRIVE LEFT IT — with hindsight, on purpose: sequence mode is offline, and the first frames of a drive are not all NEW. The records come
+ * packed across frames, class-major, so all KNOWN points of the drive are ONE contiguous run in the global frame: the static map, movers and their trails cut out.
+ * Asynchronous, behind the sequence call on the context stream. The call READS the grid and consumes no step. Nothing is launched, written or allocated unless
+ * these calls are used. (The causal variant — every frame against the grid as it stood before that frame — is what interleaved frame-by-frame calls give.)
+ *
+ * VERDICTS. The five classes, the parameter domain and the class rules are exactly those of mot_export_scene_points_dev, applied to frame k (slot k) with frame k's
+ * own matrix. KIND of an owned point: the track's is_static AS STEP k LEFT IT (the bit rows the sequence call captured; id < 0: no owner, static; id >= max_tracks_ever
+ * or no bit: dynamic). CELL: tested against slot 0's header and grid as they stand — the final window and its validity (a drive whose last frame could not place its
+ * window: nothing takes part, every point is UNKNOWN or MOVING) — with the grid's own arithmetic: bit for bit the cell the point was counted in.
+ * LAYOUT, ONE block for the drive: the classes of class_mask in ascending order; inside a class the frames ascending; inside a frame the elevated cloud's input order
+ * (index strictly ascending, MOT_ORDER_ANY included). d_totals[c] = {first, count} is the drive's run of class c, d_segments[k * 5 + c] = {first, count} frame k's part
+ * of it, `first` an ABSOLUTE position in d_points; a class outside the mask gets first = -1 in both tables; counts are the TRUE counts for all five classes. A record
+ * whose position is at or beyond point_capacity is not stored, nothing is written beyond the capacity. frame: MOT_FRAME_SENSOR (the point's bits) or MOT_FRAME_GLOBAL
+ * (the bits mot_export_track_points_dev writes, with frame k's matrix). d_classes (may be NULL): d_classes[k * class_stride + i] = the class of point i of frame k,
+ * truncated at class_stride. d_points == NULL with point_capacity == 0 and mask 0 gives the counts alone.
+ * VALIDITY: served only while slots 0..frames-1 are the sequence slots of the LATEST mot_sequence_products_dev call that had MOT_SEQ_SCENE (MOT_SEQ_ACCUMULATE may have
+ * been set with it), frames in [1, frames of that call], links and grid on, and nothing has emptied or changed a grid or taken a slot since: a fused or stage-wise
+ * call, a tracker step from outside, mot_reset*, mot_stream_load, mot_set_scene_grid, mot_set_track_links, a later sequence call without MOT_SEQ_SCENE — MOT_E_STATE.
+ * mot_export_scene_points_dev keeps refusing sequence slots.
+ * REFUSALS, each before anything is launched, the caller's blocks untouched: MOT_E_STATE as above; MOT_E_ARG as for mot_export_scene_points_dev (params, mask,
+ * frame, null d_segments, a negative stride, null d_points with a capacity or a mask, a block off 4 bytes), for null d_totals, a negative capacity, frames outside
+ * [1, frames of the sequence call] and frames * max_points beyond 2^31 - 1 (positions are int32); MOT_E_HIP when the scratch cannot be had — all of its blocks or
+ * none, the next call tries again.
+ * mot_get_sequence_scene_points does the same to the host (synchronises): *n_points (the selected records), segments [frames][5] and totals [5] are always delivered;
+ * MOT_E_CAPACITY with nothing copied when points is given and point_capacity < *n_points, or classes is given and class_stride is below a frame's elevated count;
+ * either may be NULL. Frame k's class bytes go to classes[k * class_stride ..], as many as the frame has points.
+ *
+ * Scratch: that of mot_export_scene_points_dev (sized for max_batch slots, shared with it) and 20 bytes per slot for the (frame, class) places; the getter adds a
+ * table block at its first call and takes a block of the records' size for the duration of a call. Released with the grid and by mot_destroy.
+ * Kernels (csrc/scene_judge_seq.hip): classify over (chunks, frames) — per point one 4-byte gather of the kind bit row and one 8-byte gather of the cell's two
+ * counters —, a scan per frame, ONE workgroup that scans the frames per class, and the scatter; four launches whatever `frames` is. No global atomics, no workgroup
+ * waits on another, the output does not depend on scheduling. Cost: profiles/scene_judge_sequence.md (tools/time_scene_judge_sequence.py). */
+int mot_export_sequence_scene_points_dev(mot_ctx* ctx, int frames, const mot_scene_judge_params* params, int class_mask, int frame,
+        mot_track_point* d_points, long point_capacity /* ONE block for the drive */,
+        mot_scene_segment* d_segments /* [frames][5] */, mot_scene_segment* d_totals /* [5] */,
+        uint8_t* d_classes /* may be NULL */, long class_stride);
+int mot_get_sequence_scene_points(mot_ctx* ctx, int frames, const mot_scene_judge_params* params, int class_mask, int frame,
+        mot_track_point* points /* may be NULL */, long point_capacity, long* n_points,
+        mot_scene_segment* segments /* [frames][5] */, mot_scene_segment totals[5],
+        uint8_t* classes /* may be NULL */, long class_stride);
+
 /* on != 0: the fused entry points send their launch sequence (13 kernels with the tracker) as ONE hipGraph launch, captured once per launch geometry
  * (batch, chunks of the largest frame, tracker on / off, outputs); what changes per call without changing the geometry travels in the
  * device-resident argument block. For contexts somebody waits on frame by frame (one or a few streams): the host's part of a frame
