@@ -339,7 +339,7 @@ constexpr int kIndexWgLds = 64;               // fast path: label-kernel workgro
 __global__ void MOT_LAUNCH_BOUNDS(kIndexBlock)
 cluster_index_kernel(ClusterBuffers c) {
   __shared__ int s_start[kMaxClusters + 1];
-  __shared__ int s_part[kIndexWaves], s_gpart[kIndexWaves];
+  __shared__ int s_part[kIndexWaves * 2];   // the wave totals of the scan below: {points, groups} per wave
   __shared__ __attribute__((aligned(16))) uint2 s_raw[kGroupsLds];   // fast path: {cluster, points | groups << 16} tables [wg][64] then their prefixes; general path: group keys
   static_assert(kGroupsLds * sizeof(uint2) >= kIndexWgLds * kWgClusters * (sizeof(int2) + sizeof(int)), "LDS union too small");
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -367,7 +367,7 @@ cluster_index_kernel(ClusterBuffers c) {
     return;
   }
   B1B_T_BEGIN(c, b);
-  // exclusive scans of the cluster sizes in points and in groups (kMaxClusters / kIndexBlock clusters per thread)
+  // exclusive scans of the cluster sizes in points and in groups (kMaxClusters / kIndexBlock clusters per thread; block_scan_excl_i32, both under one barrier)
   {
     constexpr int kPer = kMaxClusters / kIndexBlock;
     int v[kPer], gv[kPer], sum = 0, gsum = 0;
@@ -378,11 +378,10 @@ cluster_index_kernel(ClusterBuffers c) {
       v[k] = (int)(unsigned)cg; gv[k] = (int)(cg >> 32);
       sum += v[k]; gsum += gv[k];
     }
-    const int incl = wave_scan_incl_i32(sum), gincl = wave_scan_incl_i32(gsum);
-    if (lane == 63) { s_part[wave] = incl; s_gpart[wave] = gincl; }
-    __syncthreads();
-    int run = incl - sum, grun = gincl - gsum;
-    for (int w2 = 0; w2 < wave; w2++) { run += s_part[w2]; grun += s_gpart[w2]; }
+    const int sums[2] = {sum, gsum};
+    int before[2], all[2];
+    block_scan_excl_i32<kIndexWaves, 2>(sums, s_part, before, all);   // (the totals are not used: they fold away)
+    int run = before[0], grun = before[1];
 #pragma unroll
     for (int k = 0; k < kPer; k++) {
       const int ci = tid * kPer + k;
@@ -926,6 +925,7 @@ cluster_gather_kernel(MotDevParams p, ClusterBuffers c) {
           lo[k] = s_colmin[col]; hi[k] = s_colmax[col];
           if (lo[k] != 0x7fffffff) cnt += (hi[k] != lo[k]) ? 2 : 1;
         }
+        // (mot_wave.h's block_scan_excl_i32, written out: the call costs this kernel an 80th VGPR, and it is on the benchmarked path — profiles/block_scan.md)
         const int incl = wave_scan_incl_i32(cnt);
         if (lane == 63) s_wsum[wave] = incl;
         __syncthreads();

@@ -54,19 +54,16 @@ __device__ __forceinline__ void sj_store_counts(int (*s_cnt)[MOT_SCENE_CLASSES],
   }
 }
 
-// rows[chunk][c] (counts) -> rows[chunk][5 + c]: per class the exclusive scan over the frame's chunks (the DPP wave scans of mot_wave.h), s_total[c] = the class's points
-// (readable behind the caller's barrier). Chunks tid, tid + 256, ... per thread; every lane takes part in every scan.
-__device__ __forceinline__ void sj_scan_chunks(int* __restrict__ rows, int chunks, int* s_part, int* s_total, int tid, int lane, int wave) {
+// rows[chunk][c] (counts) -> rows[chunk][5 + c]: per class the exclusive scan over the frame's chunks (block_scan_excl_i32 of mot_wave.h), s_total[c] = the class's points
+// (readable behind the caller's barrier). Chunks tid, tid + 256, ... per thread; every thread takes part in every scan.
+__device__ __forceinline__ void sj_scan_chunks(int* __restrict__ rows, int chunks, int* s_part, int* s_total, int tid) {
   for (int c = 0; c < MOT_SCENE_CLASSES; c++) {
     int carry = 0;   // the class's points in the chunks of earlier rounds
     for (int r0 = 0; r0 < chunks; r0 += kSceneBlock) {   // (uniform)
       const int ch = r0 + tid;
       const int v = ch < chunks ? rows[(long)ch * kSceneJudgeRow + c] : 0;
-      const int incl = wave_scan_incl_i32(v);
-      if (lane == 63) s_part[wave] = incl;
-      __syncthreads();
-      int first = carry + incl - v, total = 0;
-      for (int w = 0; w < kSjWaves; w++) { if (w < wave) first += s_part[w]; total += s_part[w]; }
+      int total;
+      const int first = carry + block_scan_excl_i32<kSjWaves>(v, s_part, total);
       carry += total;
       __syncthreads();   // (s_part is written again in the next round)
       if (ch < chunks) rows[(long)ch * kSceneJudgeRow + MOT_SCENE_CLASSES + c] = first;

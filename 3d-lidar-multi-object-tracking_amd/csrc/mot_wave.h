@@ -7,6 +7,14 @@
 // last wave): a DPP move reads nothing from a disabled lane, so a partial EXEC mask silently changes the result. Each primitive has two bodies
 // — DPP for gfx950, __shfl* for the emulator — and tests/primitive_cases.py holds both, lane by lane, to one restatement of the prose below
 // (tests/devcheck/primitives.hip; full waves only, as the contract says).
+//
+// ONE WORKGROUP collective stands on them: block_scan_excl_i32, the exclusive prefix sum of one or two ints per thread over the whole workgroup in
+// thread order, and the workgroup's totals. Its contract, on top of the one above: EVERY thread of the workgroup calls it, the same number of times
+// (it holds a __syncthreads()); blockDim.x == WAVES * 64, one-dimensional; a thread without an element hands in 0. The caller owns the WAVES * N
+// LDS words it parks the wave totals in. There is exactly ONE barrier inside, between parking the totals and reading them, and NONE at the end: a
+// caller who calls it again on the same words, or writes them for any other purpose, puts a __syncthreads() in between (the round loops do); before
+// the call the words must be free, i.e. a barrier lies between their last reader and the call. Sums are plain 32-bit adds (they wrap). It has one
+// body for both builds, written over wave_scan_incl_i32, and tests/primitive_cases.py holds it thread by thread at 128, 256, 512 and 1024 threads.
 #ifndef MOT_WAVE_H_
 #define MOT_WAVE_H_
 
@@ -88,6 +96,34 @@ __device__ __forceinline__ int wave_scan_incl_i32(int v) {
 }
 __device__ __forceinline__ int wave_sum_i32(int v) { return __shfl(wave_scan_incl_i32(v), 63, 64); }
 #endif
+
+// excl[c]: the sum of v[c] over the threads before this one; total[c]: over all WAVES * 64 threads (uniform). s_tot: WAVES * N ints of LDS, the
+// caller's (wave w's inclusive total of component c at s_tot[w * N + c]). A total the caller does not use folds away. Contract: the header comment
+template <int WAVES, int N>
+__device__ __forceinline__ void block_scan_excl_i32(const int (&v)[N], int* s_tot, int (&excl)[N], int (&total)[N]) {
+  const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
+  int incl[N];
+  for (int c = 0; c < N; c++) {   // (N is 1 or 2)
+    incl[c] = wave_scan_incl_i32(v[c]);
+    if (lane == 63) s_tot[wave * N + c] = incl[c];
+    excl[c] = incl[c] - v[c]; total[c] = 0;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int w = 0; w < WAVES; w++)
+    for (int c = 0; c < N; c++) { const int t = s_tot[w * N + c]; if (w < wave) excl[c] += t; total[c] += t; }
+}
+// one int per thread: returns the exclusive prefix
+template <int WAVES>
+__device__ __forceinline__ int block_scan_excl_i32(int v, int* s_tot, int& total) {
+  const int in[1] = {v};
+  int excl[1], tot[1];
+  block_scan_excl_i32<WAVES, 1>(in, s_tot, excl, tot);
+  total = tot[0];
+  return excl[0];
+}
+template <int WAVES>
+__device__ __forceinline__ int block_scan_excl_i32(int v, int* s_tot) { int total; return block_scan_excl_i32<WAVES>(v, s_tot, total); }
 
 // a value every lane of the wave holds alike, moved to a scalar register: addresses and branches that depend on it stay scalar
 __device__ __forceinline__ int wave_uniform_i32(int v) {

@@ -84,18 +84,14 @@ regroup_label_kernel(MotDevParams p, ClusterBuffers c, RegroupBuffers r) {
 __global__ void MOT_RG_BOUNDS(kRegroupDigits)
 regroup_scan_kernel(ClusterBuffers c, RegroupBuffers r) {
   __shared__ int s_part[kRegroupDigits / 64];
-  const int b = blockIdx.x, d = threadIdx.x, lane = d & 63, wave = d >> 6;
+  const int b = blockIdx.x, d = threadIdx.x;
   const int n = rg_count(c, b);
   int chunks = (n + kRgChunk - 1) / kRgChunk;
   if (chunks > c.max_wg) chunks = c.max_wg;
   int* __restrict__ h = r.hist + (long)b * c.max_wg * kRegroupDigits;
   int sum = 0;
   for (int ch = 0; ch < chunks; ch++) sum += h[ch * kRegroupDigits + d];
-  const int incl = wave_scan_incl_i32(sum);
-  if (lane == 63) s_part[wave] = incl;
-  __syncthreads();
-  int run = incl - sum;
-  for (int w = 0; w < wave; w++) run += s_part[w];
+  int run = block_scan_excl_i32<kRegroupDigits / 64>(sum, s_part);   // all points of smaller digits
   for (int ch = 0; ch < chunks; ch++) {
     const int v = h[ch * kRegroupDigits + d];
     h[ch * kRegroupDigits + d] = run;

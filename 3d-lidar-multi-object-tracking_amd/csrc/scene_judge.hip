@@ -10,7 +10,7 @@
 //                                    8-byte load of the cell's {static_hits, dynamic_hits}; neighbouring lanes mostly share a cell, so the loads coalesce by
 //                                    themselves. The 64-bit trail test, then the class as one byte to the library's scratch (and to the caller's class block), and
 //                                    the chunk's five counts — wave ballots on the three class bits, merged through LDS — as plain stores to the chunk's row
-//   J2  scene_judge_scan_kernel      one workgroup per slot: per class an exclusive scan of the chunks' counts (the DPP wave scans of mot_wave.h), the mask applied,
+//   J2  scene_judge_scan_kernel      one workgroup per slot: per class an exclusive scan of the chunks' counts (block_scan_excl_i32 of mot_wave.h), the mask applied,
 //                                    the segment table, and where every chunk's first record of every class goes
 //   J3  scene_judge_scatter_kernel   the grid of J1: class byte in, rank inside the 64-point tile by ballots on the class bits, the 32 tiles of a chunk chained
 //                                    through a small LDS table (five serial scans of 32 entries), the point and the global transform on request, one 16-byte store
@@ -86,12 +86,12 @@ __global__ void MOT_SG_BOUNDS(kSceneBlock)
 scene_judge_scan_kernel(SceneSplatInput in, SceneJudgeBuffers j, int b0, mot_scene_segment* __restrict__ segments) {
   __shared__ int s_part[kSjWaves];
   __shared__ int s_total[MOT_SCENE_CLASSES];
-  const int kb = blockIdx.x, b = b0 + kb, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int kb = blockIdx.x, b = b0 + kb, tid = threadIdx.x;
   const int n = sj_count(in, b);
   int chunks = (n + kSceneChunk - 1) / kSceneChunk;
   if (chunks > j.max_chunks) chunks = j.max_chunks;
   int* __restrict__ rows = j.rows + (long)b * j.max_chunks * kSceneJudgeRow;
-  sj_scan_chunks(rows, chunks, s_part, s_total, tid, lane, wave);
+  sj_scan_chunks(rows, chunks, s_part, s_total, tid);
   __syncthreads();
   int first_of[MOT_SCENE_CLASSES];
   int run = 0;

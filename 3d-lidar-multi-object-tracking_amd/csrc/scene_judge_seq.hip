@@ -11,7 +11,7 @@
 //                                        (ballots, merged through LDS) leave as plain stores
 //   S2  scene_judge_seq_scan_kernel      one workgroup per frame: per class the exclusive scan over the frame's chunks (sj_scan_chunks, scene_judge_scan_kernel's) and the
 //                                        frame's five totals
-//   S3  scene_judge_seq_bases_kernel     ONE workgroup: per class a scan over the frames, 256 frames a round, DPP wave scans, the carry in a register; classes ascending, so
+//   S3  scene_judge_seq_bases_kernel     ONE workgroup: per class a scan over the frames, 256 frames a round (block_scan_excl_i32), the carry in a register; classes ascending, so
 //                                        the start of a class's run is known when its turn comes. Every (frame, class) gets its drive-wide base; both tables are written
 //   S4  scene_judge_seq_scatter_kernel   the grid of S1: class byte in, rank inside the 64-point tile by ballots, the chunk's 32 tiles chained through the 32 x 5 LDS table
 //                                        from (drive-wide base + the chunk's place inside the frame), one 16-byte store per selected record below the capacity
@@ -83,11 +83,11 @@ __global__ void MOT_SG_BOUNDS(kSceneBlock)
 scene_judge_seq_scan_kernel(SceneSplatInput in, SceneJudgeBuffers j, int* __restrict__ totals) {
   __shared__ int s_part[kSjWaves];
   __shared__ int s_total[MOT_SCENE_CLASSES];
-  const int k = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int k = blockIdx.x, tid = threadIdx.x;
   const int n = sj_count(in, k);
   int chunks = (n + kSceneChunk - 1) / kSceneChunk;
   if (chunks > j.max_chunks) chunks = j.max_chunks;
-  sj_scan_chunks(j.rows + (long)k * j.max_chunks * kSceneJudgeRow, chunks, s_part, s_total, tid, lane, wave);
+  sj_scan_chunks(j.rows + (long)k * j.max_chunks * kSceneJudgeRow, chunks, s_part, s_total, tid);
   __syncthreads();
   if (tid < MOT_SCENE_CLASSES) totals[k * MOT_SCENE_CLASSES + tid] = s_total[tid];
 }
@@ -98,7 +98,7 @@ scene_judge_seq_scan_kernel(SceneSplatInput in, SceneJudgeBuffers j, int* __rest
 __global__ void MOT_SG_BOUNDS(kSceneBlock)
 scene_judge_seq_bases_kernel(SceneJudgeBuffers j, int* __restrict__ bases, int frames, mot_scene_segment* __restrict__ segments, mot_scene_segment* __restrict__ totals) {
   __shared__ int s_part[kSjWaves];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   int run = 0;   // the records of the selected classes below c
   for (int c = 0; c < MOT_SCENE_CLASSES; c++) {
     const bool picked = (j.class_mask >> c) & 1;
@@ -107,11 +107,8 @@ scene_judge_seq_bases_kernel(SceneJudgeBuffers j, int* __restrict__ bases, int f
     for (int k0 = 0; k0 < frames; k0 += kSceneBlock) {   // (uniform)
       const int k = k0 + tid;
       const int v = k < frames ? bases[k * MOT_SCENE_CLASSES + c] : 0;
-      const int incl = wave_scan_incl_i32(v);
-      if (lane == 63) s_part[wave] = incl;
-      __syncthreads();
-      int first = start + carry + incl - v, total = 0;
-      for (int w = 0; w < kSjWaves; w++) { if (w < wave) first += s_part[w]; total += s_part[w]; }
+      int total;
+      const int first = start + carry + block_scan_excl_i32<kSjWaves>(v, s_part, total);
       carry += total;
       __syncthreads();   // (s_part is written again in the next round)
       if (k < frames) {

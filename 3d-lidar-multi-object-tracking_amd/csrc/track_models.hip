@@ -7,7 +7,7 @@
 //
 //   M1  track_models_plan_kernel       one workgroup per stream, threads over the T rows (256 at a time, a running base between the rounds): the row, the step of
 //                                      the oldest logged observation, a binary search of the unrolled ring for the first point of that step or later (steps never
-//                                      decrease along the unrolled ring) -> count; a workgroup exclusive scan (DPP wave scan + four wave totals in LDS) -> first;
+//                                      decrease along the unrolled ring) -> count; a workgroup exclusive scan (block_scan_excl_i32, mot_wave.h) -> first;
 //                                      the 48-byte headers (extent 0) and the stream's two counts
 //   M2  track_models_transform_kernel  one workgroup of ONE WAVE per (row, stream) — a model is a few hundred to a few thousand records, and a stream has many: the
 //                                      parallelism is across models; rows without a model leave at once. The log, {step, px, py, c, s}, goes to LDS in tiles of 64
@@ -47,8 +47,8 @@ static_assert(sizeof(mot_track_model) == 48 && sizeof(mot_accum_point) == 16, "i
 // ------------------------------------------------------------------------------------------ M1
 __global__ void MOT_TM_BOUNDS(kTmPlanBlock)
 track_models_plan_kernel(TrackModelBuffers a, int b0, int flags, mot_track_model* __restrict__ models, int* __restrict__ counts) {
-  __shared__ int s_tot[kTmPlanWaves][2];
-  const int kb = blockIdx.x, b = b0 + kb, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __shared__ int s_tot[kTmPlanWaves * 2];
+  const int kb = blockIdx.x, b = b0 + kb, tid = threadIdx.x;
   const bool current = (flags & MOT_MODEL_CURRENT) != 0;
   const int latest = current ? a.latest[b] : 0;
   int base_records = 0, base_models = 0;
@@ -67,19 +67,13 @@ track_models_plan_kernel(TrackModelBuffers a, int b0, int flags, mot_track_model
         m.count = g.kept - tm_search<false>(a.points + at * a.K, g.ring0, a.K, 0, g.kept, oldest);
       }
     }
-    const int incl = wave_scan_incl_i32(m.count);
-    const int here = __popcll(__ballot(m.track_id >= 0));
-    if (lane == 63) { s_tot[wave][0] = incl; s_tot[wave][1] = here; }
-    __syncthreads();
-    int before = 0, all_records = 0, all_models = 0;
-#pragma unroll
-    for (int w = 0; w < kTmPlanWaves; w++) {
-      if (w < wave) before += s_tot[w][0];
-      all_records += s_tot[w][0]; all_models += s_tot[w][1];
-    }
-    if (m.track_id >= 0) m.first = base_records + before + incl - m.count;
+    // the records before this row's and, under the same barrier, the round's models (block_scan_excl_i32; only the total of the second is used)
+    const int v[2] = {m.count, m.track_id >= 0 ? 1 : 0};
+    int before[2], all[2];
+    block_scan_excl_i32<kTmPlanWaves, 2>(v, s_tot, before, all);
+    if (m.track_id >= 0) m.first = base_records + before[0];
     if (r < a.T) models[(long)kb * a.T + r] = m;
-    base_records += all_records; base_models += all_models;
+    base_records += all[0]; base_models += all[1];
     __syncthreads();   // (the totals are read: the next round may write them)
   }
   if (tid == 0) { counts[2 * kb] = base_models; counts[2 * kb + 1] = base_records; }

@@ -98,7 +98,7 @@ __global__ void MOT_TP_BOUNDS(kTpBlock)
 track_points_scan_kernel(TrackPointBuffers t, int b0, int rest, mot_track_segment* __restrict__ segs, int max_segments, int* __restrict__ counts_out) {
   constexpr int kPer = (kTrackPointKeys + kTpBlock - 1) / kTpBlock;   // 5
   __shared__ int s_part[kTpBlock / 64];
-  const int k = blockIdx.x, b = b0 + k, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int k = blockIdx.x, b = b0 + k, tid = threadIdx.x;
   const int n = tp_count(t, b);
   int chunks = (n + kTrackPointChunk - 1) / kTrackPointChunk;
   if (chunks > t.max_chunks) chunks = t.max_chunks;
@@ -111,12 +111,9 @@ track_points_scan_kernel(TrackPointBuffers t, int b0, int rest, mot_track_segmen
     const int key = q * kTpBlock + tid;
     int sum = 0;
     if (key <= R) for (int ch = 0; ch < chunks; ch++) sum += rows[(long)ch * kTrackPointKeys + key];
-    // exclusive prefix over the round's 256 keys
-    const int incl = wave_scan_incl_i32(sum);
-    if (lane == 63) s_part[wave] = incl;
-    __syncthreads();
-    int first = carry + incl - sum, total = 0;
-    for (int w = 0; w < kTpBlock / 64; w++) { if (w < wave) first += s_part[w]; total += s_part[w]; }
+    // exclusive prefix over the round's 256 keys (block_scan_excl_i32, mot_wave.h)
+    int total;
+    const int first = carry + block_scan_excl_i32<kTpBlock / 64>(sum, s_part, total);
     carry += total;
     __syncthreads();   // (s_part is written again in the next round)
     if (key > R) continue;

@@ -19,7 +19,7 @@
 //                                   predecessor's), and a run's length is what is left of it in the head's chunk plus the LEADING parts of the chunks behind, walked
 //                                   chunk by chunk up to the next head — 8 + 511 steps at the most, never 4096. Heads whose run holds min_points records are voxels,
 //                                   the others n_sparse; the raw extent as in the raw export (integer min / max). -> 48 bytes of result per row
-//   V2  track_voxels_pack_kernel    one workgroup per stream, threads over the T rows as the plan kernel: exclusive scan of the rows' voxel counts -> first, the 64-byte
+//   V2  track_voxels_pack_kernel    one workgroup per stream, threads over the T rows as the plan kernel: exclusive scan of the rows' voxel counts (block_scan_excl_i32) -> first, the 64-byte
 //                                   headers, the stream's two counts
 //   V3  track_voxels_write_kernel   V1's sort again (the same entries, hence the same order), for the models with a voxel below voxel_stride; not launched without a
 //                                   voxel block. The inverse permutation (16 bits per record) goes beside the entries, the records stream through tm_record a second
@@ -274,13 +274,9 @@ __device__ __forceinline__ void tv_model(const TrackModelBuffers& a, int b0, int
     return;
   }
   // ---- V3 only: the voxel number of this thread's first head, the records at their sorted position, the sums
-  const int incl = wave_scan_incl_i32(kept);
-  if (lane == 63) s_tot[wave][1] = incl;
-  __syncthreads();   // (... and every entry has been read: the coordinates take their place)
-  int voxel = incl - kept;
-#pragma unroll
-  for (int w = 0; w < kTvWaves; w++)
-    if (w < wave) voxel += s_tot[w][1];
+  // block_scan_excl_i32 parks its wave totals in the first kTvWaves words of the table: V3 writes nothing there but the column of n_outside, and
+  // that one was read before the barrier above. (Behind its barrier every entry has been read as well: the coordinates take their place)
+  int voxel = block_scan_excl_i32<kTvWaves>(kept, &s_tot[0][0]);
   tv_stream(a, at, g, count, axes, s_obs, [&](int i, const float4& q) {
     unsigned key;
     if (!tv_key(q, v, &key)) return;
@@ -324,8 +320,8 @@ track_voxels_count_kernel(TrackModelBuffers a, int b0, int flags, TrackVoxelArgs
 __global__ void MOT_TV_BOUNDS(kTvBlock)
 track_voxels_pack_kernel(int T, int K, const mot_track_model* __restrict__ plan, const TrackVoxelResult* __restrict__ res, mot_track_voxel_model* __restrict__ models,
                          int* __restrict__ counts) {
-  __shared__ int s_tot[kTvWaves][2];
-  const int kb = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __shared__ int s_tot[kTvWaves * 2];
+  const int kb = blockIdx.x, tid = threadIdx.x;
   int base_voxels = 0, base_models = 0;
   for (int r0 = 0; r0 < T; r0 += kTvBlock) {   // (the same rounds for every thread: the scan below is a collective)
     const int r = r0 + tid;
@@ -341,19 +337,13 @@ track_voxels_pack_kernel(int T, int K, const mot_track_model* __restrict__ plan,
         m.n_records = pm.count; m.n_outside = o.n_outside; m.n_sparse = o.n_sparse;
       }
     }
-    const int incl = wave_scan_incl_i32(m.count);
-    const int here = __popcll(__ballot(m.track_id >= 0));
-    if (lane == 63) { s_tot[wave][0] = incl; s_tot[wave][1] = here; }
-    __syncthreads();
-    int before = 0, all_voxels = 0, all_models = 0;
-#pragma unroll
-    for (int w = 0; w < kTvWaves; w++) {
-      if (w < wave) before += s_tot[w][0];
-      all_voxels += s_tot[w][0]; all_models += s_tot[w][1];
-    }
-    if (m.track_id >= 0) m.first = base_voxels + before + incl - m.count;
+    // the voxels before this row's and, under the same barrier, the round's models (block_scan_excl_i32; only the total of the second is used)
+    const int v[2] = {m.count, m.track_id >= 0 ? 1 : 0};
+    int before[2], all[2];
+    block_scan_excl_i32<kTvWaves, 2>(v, s_tot, before, all);
+    if (m.track_id >= 0) m.first = base_voxels + before[0];
     if (r < T) models[(long)kb * T + r] = m;
-    base_voxels += all_voxels; base_models += all_models;
+    base_voxels += all[0]; base_models += all[1];
     __syncthreads();   // (the totals are read: the next round may write them)
   }
   if (tid == 0) { counts[2 * kb] = base_models; counts[2 * kb + 1] = base_voxels; }

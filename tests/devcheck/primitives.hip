@@ -2,6 +2,7 @@
 // (tests/devcheck/libmot_primitives.so for gfx950, libmot_primitives_emu.so for the host; built by tests/devcheck/build_primitives.py),
 // like sweep.hip. It includes the product's headers, so it runs the very functions the kernels inline:
 //   mot_prim_wave     every primitive of mot_wave.h, per lane, nothing folded on the device (DPP body on gfx950, __shfl body on the host)
+//   mot_prim_block_scan   block_scan_excl_i32 of mot_wave.h, one workgroup of 128 / 256 / 512 / 1024 threads per case, as the call sites use it (rounds, carry, barrier)
 //   mot_prim_math     mot_atanf, mot_atan2f, mot_polar_cell_exact, mot_polar_bin_exact, mot_cart_cell of mot_math.h / mot_internal.h
 //   mot_prim_det5 / mot_prim_inv2 / mot_prim_wrap_pi   the tracker's scalar fp64 helpers of mot_track_prep.h
 //   mot_prim_box_fp64 the fp64 library calls of the box stage (box.hip, cluster_rect kernels: sqrt, atan2, cos, sin, each rounded to float)
@@ -208,5 +209,61 @@ extern "C" int mot_prim_box_fp64(const float* a, const float* b, long n, int mod
   if (ok && n) hipLaunchKernelGGL(prim_box_fp64_kernel, dim3(prim_blocks(n)), dim3(256), 0, 0, da, db, n, mode, d_out);
   const int rc = prim_finish(ok, out4n, d_out, (size_t)n * 16);
   (void)hipFree(da); (void)hipFree(db); (void)hipFree(d_out);
+  return rc;
+}
+
+// ------------------------------------------------------------------------------------------------------------------ the workgroup scan
+// block_scan_excl_i32 of mot_wave.h as its call sites use it: one workgroup of WAVES * 64 threads per case, `rounds` rounds chained through a carry, an LDS
+// array of exactly WAVES * N words, and the caller's barrier before the words are written again. v and excl: [case][round][thread][N]; totals: [case][round][N].
+template <int WAVES, int N>
+__global__ void MOT_LAUNCH_BOUNDS(WAVES * 64)
+prim_block_scan_kernel(const int* __restrict__ v, int rounds, int* __restrict__ excl, int* __restrict__ totals) {
+  __shared__ int s_tot[WAVES * N];
+  const int t = threadIdx.x;
+  int carry[N];
+#pragma unroll
+  for (int c = 0; c < N; c++) carry[c] = 0;
+  for (int r = 0; r < rounds; r++) {   // (uniform)
+    const long row = (long)blockIdx.x * rounds + r, at = (row * (WAVES * 64) + t) * N;
+    int in[N], before[N], all[N];
+#pragma unroll
+    for (int c = 0; c < N; c++) in[c] = v[at + c];
+    if constexpr (N == 1) before[0] = block_scan_excl_i32<WAVES>(in[0], s_tot, all[0]);   // (the single-value wrapper, as most call sites)
+    else block_scan_excl_i32<WAVES, N>(in, s_tot, before, all);
+#pragma unroll
+    for (int c = 0; c < N; c++) {
+      excl[at + c] = carry[c] + before[c];
+      if (t == 0) totals[row * N + c] = all[c];
+      carry[c] += all[c];
+    }
+    __syncthreads();   // (s_tot is written again in the next round)
+  }
+}
+
+template <int WAVES>
+static void prim_block_scan_launch(int n_cases, int n, int rounds, const int* v, int* excl, int* totals) {
+  if (n == 1) hipLaunchKernelGGL((prim_block_scan_kernel<WAVES, 1>), dim3((unsigned)n_cases), dim3(WAVES * 64), 0, 0, v, rounds, excl, totals);
+  else hipLaunchKernelGGL((prim_block_scan_kernel<WAVES, 2>), dim3((unsigned)n_cases), dim3(WAVES * 64), 0, 0, v, rounds, excl, totals);
+}
+
+// waves in {2, 4, 8, 16} (the block sizes of the product's call sites), n in {1, 2} components, rounds in {1, 3}
+extern "C" int mot_prim_block_scan(const int* v, int n_cases, int waves, int n, int rounds, int* excl, int* totals) {
+  if (!v || !excl || !totals || n_cases < 0 || n_cases > 4096 || (waves != 2 && waves != 4 && waves != 8 && waves != 16) || (n != 1 && n != 2) || (rounds != 1 && rounds != 3)) return 1;
+  const size_t words = (size_t)n_cases * rounds * waves * 64 * n, tot_words = (size_t)n_cases * rounds * n;
+  int *d_v, *d_excl, *d_tot;
+  bool ok = prim_upload(&d_v, v, words * 4);
+  ok = prim_upload(&d_excl, nullptr, words * 4) && ok;
+  ok = prim_upload(&d_tot, nullptr, tot_words * 4) && ok;
+  if (ok && n_cases) {
+    switch (waves) {
+      case 2: prim_block_scan_launch<2>(n_cases, n, rounds, d_v, d_excl, d_tot); break;
+      case 4: prim_block_scan_launch<4>(n_cases, n, rounds, d_v, d_excl, d_tot); break;
+      case 8: prim_block_scan_launch<8>(n_cases, n, rounds, d_v, d_excl, d_tot); break;
+      default: prim_block_scan_launch<16>(n_cases, n, rounds, d_v, d_excl, d_tot); break;
+    }
+  }
+  int rc = prim_finish(ok, excl, d_excl, words * 4);
+  if (rc == 0 && tot_words && hipMemcpy(totals, d_tot, tot_words * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = 3;
+  (void)hipFree(d_v); (void)hipFree(d_excl); (void)hipFree(d_tot);
   return rc;
 }

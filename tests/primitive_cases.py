@@ -4,6 +4,8 @@ library to run as an argument; the cases that compare two builds take the host b
 
   wave_case      every primitive of csrc/mot_wave.h, lane by lane, against a numpy restatement of the header's PROSE (not of either body): integer ops
                  exact, sums in float64 along the documented tree (partner at lane distance 1, 2, 4, 8: IEEE-exact, so bit for bit), NaN equal to NaN
+  block_scan_case  the workgroup collective of the same header, block_scan_excl_i32, thread by thread against numpy's cumsum in wrapping int32: 128 to 1024 threads, one
+                 and two components, one round and three rounds chained through the caller's carry and barrier (one body for both builds, over wave_scan_incl_i32)
   math_case      mot_atanf / mot_atan2f / the exact polar cell and bin / the Cartesian cell as compiled for the device, against the host build of the
                  same file (which tests/test_math_exact.py ties to glibc), bit for bit
   det5_case, wrap_pi_case, inv2_case   the tracker's scalar fp64 helpers (csrc/mot_track_prep.h) against the oracle's own (oracle/mot_oracle_track.c)
@@ -31,6 +33,7 @@ vp = lambda a: a.ctypes.data_as(C.c_void_p)
 def _load(path):
     L = C.CDLL(path)
     L.mot_prim_wave.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    L.mot_prim_block_scan.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.mot_prim_math.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p]
     for fn in (L.mot_prim_det5, L.mot_prim_inv2, L.mot_prim_wrap_pi):
         fn.argtypes = [C.c_void_p, C.c_long, C.c_void_p]
@@ -221,6 +224,68 @@ def wave_case(lib):
     sel = np.broadcast_to(np.tile(idx[0, 0] == 0, 16)[None, :], got["row_sum"].shape)
     assert sel.any() and same_bits(got["row_sum8"][sel], got["row_sum"][sel]).all()
     return len(cases)
+
+
+# ------------------------------------------------------------------------------------------------------------------ 1b the workgroup scan
+BLOCK_SCAN_WAVES = (2, 4, 8, 16)     # 128, 256, 512, 1024 threads: the block sizes of the call sites in csrc/
+BLOCK_SCAN_ROUNDS = (1, 3)
+
+
+def block_scan_values(waves, rounds):
+    """[(what, values (rounds, waves * 64))] for one component; the rounds of a case are chained through the caller's carry"""
+    rng = np.random.default_rng(20241020 + 100 * waves + rounds)
+    T = waves * 64
+    shape = (rounds, T)
+    out = [("all zeros", np.zeros(shape, np.int64)), ("all ones", np.ones(shape, np.int64))]
+    edges = sorted({0, 63, 64, T - 1} | {64 * w for w in range(waves)} | {64 * w + 63 for w in range(waves)})
+    for k, t in enumerate(edges):    # (the round moves with the position, so that with three rounds the value also travels through the carry)
+        v = np.zeros(shape, np.int64)
+        v[k % rounds, t] = 5 + k
+        out.append(("a single value at thread %d of round %d" % (t, k % rounds), v))
+    w, r = np.arange(T) // 64, np.arange(rounds)[:, None]
+    out.append(("a constant per wave", 1 + 3 * w[None, :] * (w[None, :] + 2) + 1000 * r))    # strictly convex in the wave: no two orders of the waves give the same prefixes
+    for s in range(3):
+        out.append(("random in [0, 2^20] %d" % s, rng.integers(0, 2 ** 20, shape, endpoint=True)))
+        out.append(("random of both signs %d" % s, rng.integers(-2 ** 20, 2 ** 20, shape, endpoint=True)))
+    out.append(("sparse: most threads hand in 0", rng.integers(1, 9, shape) * (rng.integers(0, 8, shape) == 0)))
+    out.append(("the running sum passes 2^31", rng.integers(2 ** 29, 2 ** 30, shape)))
+    out.append(("the running sum passes 2^31 both ways", rng.integers(2 ** 29, INT_MAX, shape) * rng.choice([1, 1, -1], shape)))
+    out.append(("all INT_MAX", np.full(shape, INT_MAX, np.int64)))
+    return out
+
+
+def block_scan_reference(v):
+    """v (cases, rounds, threads, n) int32 -> what csrc/mot_wave.h promises, the rounds chained by `carry += total`: the exclusive running sum over rounds x threads and
+    each round's total, per component, in 32-bit two's complement (the sums wrap)"""
+    n_cases, rounds, T, n = v.shape
+    u = v.astype(np.int64).astype(u32)
+    flat = np.moveaxis(u, -1, 1).reshape(n_cases, n, rounds * T)
+    excl = (np.cumsum(flat, -1, dtype=u32) - flat).reshape(n_cases, n, rounds, T)
+    return np.ascontiguousarray(np.moveaxis(excl, 1, -1)).view(i32), np.ascontiguousarray(u.sum(2, dtype=u32)).view(i32)
+
+
+def block_scan_case(lib):
+    """block_scan_excl_i32 thread by thread at every block size of the product, one and two components, one round and three chained rounds"""
+    total = 0
+    for waves, rounds, n in itertools.product(BLOCK_SCAN_WAVES, BLOCK_SCAN_ROUNDS, (1, 2)):
+        vals = block_scan_values(waves, rounds)
+        names = [what for what, _ in vals]
+        cols = [np.stack([a for _, a in vals])]
+        if n == 2:   # the second component: the NEXT case's values, so that the two columns of a case always differ (and come from different generators)
+            cols.append(np.roll(cols[0], -1, 0))
+            assert (cols[0] != cols[1]).reshape(len(vals), -1).any(1).all()
+        v = np.ascontiguousarray(np.stack(cols, -1).astype(np.int64).astype(u32).view(i32))      # (cases, rounds, threads, n)
+        assert v.shape == (len(vals), rounds, waves * 64, n)
+        excl, tot = np.full(v.shape, -77, i32), np.full((len(vals), rounds, n), -77, i32)
+        assert lib.mot_prim_block_scan(vp(v), len(vals), waves, n, rounds, vp(excl), vp(tot)) == 0
+        want_excl, want_tot = block_scan_reference(v)
+        what = "%d waves, %d component(s), %d round(s)" % (waves, n, rounds)
+        ok = excl == want_excl
+        assert ok.all(), (what, [names[i] for i in np.unique(np.argwhere(~ok)[:, 0])[:5]], first_bad(ok, excl, want_excl))
+        ok = tot == want_tot
+        assert ok.all(), (what, "totals", [names[i] for i in np.unique(np.argwhere(~ok)[:, 0])[:5]], first_bad(ok, tot, want_tot))
+        total += len(vals)
+    return total
 
 
 # ------------------------------------------------------------------------------------------------------------------ 2 the exact fp32 math

@@ -14,6 +14,11 @@ def test_primitives_wave_and_row_on_the_host_build():
     assert P.wave_case(P.host_lib()) > 500
 
 
+def test_primitives_block_scan_on_the_host_build():
+    """... and under the emulator's other thread orders and its dirty LDS: the barrier inside the primitive and the caller's one are what make it right"""
+    assert P.block_scan_case(P.host_lib()) > 300
+
+
 def test_primitives_exact_math_on_the_host_build(mot):
     import build_emu
     assert P.math_case(mot, P.host_lib(), P.host_lib(), ctx_lib_path=build_emu.build()) >= 1 << 22

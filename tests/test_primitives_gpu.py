@@ -13,6 +13,11 @@ def test_primitives_wave_and_row_on_device():
     assert P.wave_case(P.device_lib()) > 500
 
 
+def test_primitives_block_scan_on_device():
+    """block_scan_excl_i32 at 128, 256, 512 and 1024 threads, one and two components, one and three chained rounds, thread by thread against numpy"""
+    assert P.block_scan_case(P.device_lib()) > 300
+
+
 def test_primitives_exact_math_device_equals_host(mot, hip_lib):
     """mot_atanf / mot_atan2f / exact polar cell and bin / Cartesian cell: gfx950 == host build (== glibc, tests/test_math_exact.py), bit for bit,
     on the MotDevParams of the two presets and of the polar range at ratio 4"""
