@@ -63,7 +63,7 @@ extern "C" int mot_set_scene_grid(mot_ctx* c, const mot_scene_params* p) {
   if (!(p->cell >= 0.05f && p->cell <= 10.f)) return fail(c, MOT_E_ARG, who, ": cell must be finite and in [0.05, 10] metres");   // (NaN fails both compares)
   const int W = p->size;
   if (W < 64 || W > 2048 || (W & (W - 1))) return fail(c, MOT_E_ARG, who, ": size must be a power of two in [64, 2048]");
-  if (!c->track_links) return fail(c, MOT_E_STATE, who, ": track links are off (mot_set_track_links)");
+  MOT_TRY(check_links_on(c, who));
   if (W == c->scene_W && p->cell == c->scene_cell) return MOT_OK;
   // the new blocks first: a failure leaves the mode, an earlier geometry included, as it was
   const bool had_ring = c->sg_ring.base != nullptr;
@@ -101,32 +101,19 @@ extern "C" int mot_accumulate_scene(mot_ctx* c, int batch) {
   MOT_TRY(check_scene_on(c, who));
   if (batch < 1 || batch > c->batch) return fail(c, MOT_E_ARG, who, ": batch out of range");
   for (int b = 0; b < batch; b++) {   // every slot before anything is launched or counted
-    if (!c->track_links || !c->res.point_tracks_valid(b))
-      return fail(c, MOT_E_STATE, who, ": the slot's cloud, boxes and tracker step do not come from one fused call (a stage-wise call took the slot, the tracker was fed from outside, "
-                                       "or no fused call ran the tracker since the links were turned on)");
+    MOT_TRY(check_point_tracks(c, b, who));
     if (c->res.sequence_frame(b)) return fail(c, MOT_E_STATE, who, ": the slots hold the frames of ONE stream (mot_sequence_dev); mot_sequence_products_dev(MOT_SEQ_SCENE) takes a drive's frames into "
                                                                               "the grid inside the sequence call");
     if (c->res.scene_done(b)) return fail(c, MOT_E_STATE, who, ": a slot of the batch was already taken into its grid for its current step, or was reset / loaded since that step");
   }
-  // the matrices the slots' boxes took and the slots' step stamps, in one stream-ordered copy ahead of the kernels
-  char* raw;
-  MOT_TRY(c->sg_ring.acquire(c, &raw));
-  memcpy(raw, c->link_tf.data(), (size_t)batch * sizeof(EgoTf));
-  memcpy(raw + (size_t)batch * sizeof(EgoTf), c->scene_step.data(), (size_t)batch * sizeof(int));
-  MOT_TRY(c->sg_ring.commit(c, c->d_sg_args, 0, (size_t)batch * (sizeof(EgoTf) + sizeof(int)), c->stream));
-  const EgoTf* d_tf = reinterpret_cast<const EgoTf*>(c->d_sg_args);
-  const int* d_steps = reinterpret_cast<const int*>(d_tf + batch);
-  SceneSplatInput in;
-  in.ids = c->d_point_track; in.elevated = c->d_elev; in.cap = c->cap; in.counts = c->d_counts; in.slot_of = c->d_slot_of; in.out = c->d_tout;
-  in.T = c->max_tracks_total; in.E = c->max_tracks_ever;
+  const EgoTf* d_tf; const int* d_steps;   // the matrices the slots' boxes took and the slots' step stamps
+  MOT_TRY(send_link_tf(c, &c->sg_ring, c->d_sg_args, 0, batch, &c->scene_step, &d_tf, &d_steps));
+  SceneSplatInput in = scene_input(c, true);
   const SceneGridBuffers g = scene_buffers(c);
-  for (int k0 = 0; k0 < batch;) {   // one launch per run of slots of one cloud layout (launch_track_points, mot_api_tracks.hip)
-    int k1 = k0 + 1;
-    while (k1 < batch && c->res.elev_packed_at(k1) == c->res.elev_packed_at(k0)) k1++;
-    in.elevated_packed = c->res.elev_packed_at(k0) ? 1 : 0;
+  for_layout_runs(c, 0, batch, [&](int k0, int k1, int packed) {
+    in.elevated_packed = packed;
     mot_launch_scene_accumulate(g, in, k0, k1 - k0, c->max_points, d_tf + k0, d_steps + k0, c->stream);
-    k0 = k1;
-  }
+  });
   MOT_HIP(c, hipGetLastError());
   for (int b = 0; b < batch; b++) { c->scene_step[b]++; c->res.scene_taken(b); }
   return MOT_OK;
@@ -143,7 +130,7 @@ static SceneSeqBuffers seq_scene_buffers(const mot_ctx* c) {
 }
 int seq_scene_ready(mot_ctx* c, const char* who, int frames) {
   MOT_TRY(check_scene_on(c, who));
-  if (!c->track_links) return fail(c, MOT_E_STATE, who, ": track links are off (mot_set_track_links)");
+  MOT_TRY(check_links_on(c, who));
   const size_t row_bytes = (size_t)((c->max_tracks_ever + 31) / 32) * sizeof(unsigned);
   if (!c->d_sgs_win || !c->d_sgs_static) {
     int rc = dev_alloc(c, &c->d_sgs_win, ((size_t)c->batch + 1) * sizeof(SceneSeqFrame));
@@ -163,12 +150,8 @@ void seq_scene_capture(mot_ctx* c, int frame) {
   mot_launch_scene_seq_capture(c->d_counts, c->d_owner, c->d_slot_of, c->d_tout, c->max_tracks_total, c->max_tracks_ever, seq_scene_buffers(c), frame, c->stream);
 }
 int seq_scene_append(mot_ctx* c, int frames, int max_n) {
-  SceneSplatInput in;
-  in.ids = c->d_point_track; in.elevated = c->d_elev; in.cap = c->cap; in.counts = c->d_counts; in.slot_of = nullptr; in.out = nullptr;
-  in.T = c->max_tracks_total; in.E = c->max_tracks_ever;
-  in.elevated_packed = c->res.elev_packed_at(0) ? 1 : 0;   // (one fused call filled the slots: one layout)
   // frame k's matrix is entry k of the call's own argument block (what link_tf[k] keeps on the host): later calls rewrite it behind these kernels, stream-ordered
-  mot_launch_scene_sequence(scene_buffers(c), in, seq_scene_buffers(c), frames, max_n, c->d_ego, c->stream);
+  mot_launch_scene_sequence(scene_buffers(c), scene_input(c, false), seq_scene_buffers(c), frames, max_n, c->d_ego, c->stream);   // (slot 0's layout: one fused call filled the slots)
   MOT_HIP(c, hipGetLastError());
   c->scene_step[0] += frames;   // (a frame refused for capacity has no points to add and counts)
   c->res.sequence_scene_taken(frames);
@@ -214,9 +197,7 @@ extern "C" int mot_get_scene_grid(mot_ctx* c, int slot, mot_scene_cell* cells, i
 // The validity of mot_accumulate_scene without its once-per-step clause: the step may have been taken or not, but a grid emptied since (the setter, a reset, a load)
 // no longer belongs to the step the slot holds.
 static int check_judge_slot(mot_ctx* c, int b, const char* who) {
-  if (!c->track_links || !c->res.point_tracks_valid(b))
-    return fail(c, MOT_E_STATE, who, ": the slot's cloud, boxes and tracker step do not come from one fused call (a stage-wise call took the slot, the tracker was fed from outside, "
-                                     "or no fused call ran the tracker since the links were turned on)");
+  MOT_TRY(check_point_tracks(c, b, who));
   if (c->res.sequence_frame(b)) return fail(c, MOT_E_STATE, who, ": the slots hold the frames of ONE stream (mot_sequence_dev)");
   if (!c->res.scene_judgeable(b)) return fail(c, MOT_E_STATE, who, ": the slot's grid was emptied (mot_set_scene_grid, a reset or a load) since the step the slot holds");
   return MOT_OK;
@@ -247,30 +228,19 @@ static int ensure_judge(mot_ctx* c, bool host_stage) {
   if (host_stage) MOT_TRY(dev_alloc(c, &c->d_sj_stage, (size_t)c->cap * sizeof(mot_track_point) + 48 + (size_t)c->cap));
   return MOT_OK;
 }
-// the kernels over slots first .. first + n - 1, block k of the caller's buffers for slot first + k; one launch per run of slots of one cloud layout (launch_track_points)
+// the kernels over slots first .. first + n - 1, block k of the caller's buffers for slot first + k; one launch per run of slots of one cloud layout (for_layout_runs)
 static int launch_judge(mot_ctx* c, int first, int n, const mot_scene_judge_params* p, int class_mask, int frame, mot_track_point* d_points, long point_stride,
                         mot_scene_segment* d_segments, uint8_t* d_classes, long class_stride) {
-  // the matrices the slots' boxes took, in one stream-ordered copy ahead of the kernels (the cell test needs them in either frame)
-  char* raw;
-  MOT_TRY(c->sg_ring.acquire(c, &raw));
-  memcpy(raw, c->link_tf.data() + first, (size_t)n * sizeof(EgoTf));
-  MOT_TRY(c->sg_ring.commit(c, c->d_sj_args, 0, (size_t)n * sizeof(EgoTf), c->stream));
-  const EgoTf* d_tf = reinterpret_cast<const EgoTf*>(c->d_sj_args);
-  SceneSplatInput in;
-  in.ids = c->d_point_track; in.elevated = c->d_elev; in.cap = c->cap; in.counts = c->d_counts; in.slot_of = c->d_slot_of; in.out = c->d_tout;
-  in.T = c->max_tracks_total; in.E = c->max_tracks_ever;
-  SceneJudgeBuffers j;
-  j.cls = c->d_sj_cls; j.rows = c->d_sj_rows; j.max_chunks = c->sj_chunks;
-  j.min_static_hits = p->min_static_hits; j.trail_num = p->trail_num; j.trail_den = p->trail_den; j.class_mask = class_mask;
+  const EgoTf* d_tf;   // the matrices the slots' boxes took (the cell test needs them in either frame)
+  MOT_TRY(send_link_tf(c, &c->sg_ring, c->d_sj_args, first, n, nullptr, &d_tf));
+  SceneSplatInput in = scene_input(c, true);
+  const SceneJudgeBuffers j = judge_buffers(c, p, class_mask);
   const SceneGridBuffers g = scene_buffers(c);
-  for (int k0 = 0; k0 < n;) {
-    int k1 = k0 + 1;
-    while (k1 < n && c->res.elev_packed_at(first + k1) == c->res.elev_packed_at(first + k0)) k1++;
-    in.elevated_packed = c->res.elev_packed_at(first + k0) ? 1 : 0;
+  for_layout_runs(c, first, n, [&](int k0, int k1, int packed) {
+    in.elevated_packed = packed;
     mot_launch_scene_judge(g, in, j, first + k0, k1 - k0, c->max_points, d_tf + k0, frame == MOT_FRAME_GLOBAL, d_points ? d_points + (long)k0 * point_stride : nullptr, point_stride,
                            d_segments + (long)k0 * MOT_SCENE_CLASSES, d_classes ? d_classes + (long)k0 * class_stride : nullptr, class_stride, c->stream);
-    k0 = k1;
-  }
+  });
   MOT_HIP(c, hipGetLastError());
   return MOT_OK;
 }
@@ -332,7 +302,7 @@ extern "C" int mot_get_scene_points(mot_ctx* c, int slot, const mot_scene_judge_
 // Served while Residency::sequence_scene_frames() vouches for the slots and for slot 0's grid: the frames of the latest MOT_SEQ_SCENE call, nothing taken, emptied or
 // changed since. The judge's scratch (ensure_judge: sized for max_batch slots) and [max_batch][5] bases of the call's own; all of it or none.
 static int check_seq_judge(mot_ctx* c, const char* who, int frames) {
-  if (!c->track_links) return fail(c, MOT_E_STATE, who, ": track links are off (mot_set_track_links)");
+  MOT_TRY(check_links_on(c, who));
   const int held = c->res.sequence_scene_frames();
   if (!held || !c->d_sgs_static)
     return fail(c, MOT_E_STATE, who, ": slots 0 .. frames - 1 are not the frames of the latest mot_sequence_products_dev(MOT_SEQ_SCENE) call with stream 0's grid as that call left it "
@@ -359,22 +329,13 @@ static int ensure_seq_judge(mot_ctx* c, bool host_stage) {
   return MOT_OK;
 }
 struct SeqJudgeLaunch { SceneSplatInput in; SceneJudgeBuffers j; const EgoTf* d_tf; };
-// classify, the two scans and both tables; the matrices the frames' boxes took, in one stream-ordered copy ahead of the kernels (the cell test needs them in either frame)
+// classify, the two scans and both tables; the matrices the frames' boxes took go ahead of the kernels (the cell test needs them in either frame)
 static int launch_seq_judge_count(mot_ctx* c, int frames, const mot_scene_judge_params* p, int class_mask, mot_scene_segment* d_segments, mot_scene_segment* d_totals,
                                   uint8_t* d_classes, long class_stride, SeqJudgeLaunch* L) {
-  char* raw;
-  MOT_TRY(c->sg_ring.acquire(c, &raw));
-  memcpy(raw, c->link_tf.data(), (size_t)frames * sizeof(EgoTf));
-  MOT_TRY(c->sg_ring.commit(c, c->d_sj_args, 0, (size_t)frames * sizeof(EgoTf), c->stream));
-  L->d_tf = reinterpret_cast<const EgoTf*>(c->d_sj_args);
-  SceneSplatInput& in = L->in;
-  in.ids = c->d_point_track; in.elevated = c->d_elev; in.cap = c->cap; in.counts = c->d_counts; in.slot_of = nullptr; in.out = nullptr;   // (the kind comes from the captured bits)
-  in.T = c->max_tracks_total; in.E = c->max_tracks_ever;
-  in.elevated_packed = c->res.elev_packed_at(0) ? 1 : 0;   // (one layout: check_seq_judge)
-  SceneJudgeBuffers& j = L->j;
-  j.cls = c->d_sj_cls; j.rows = c->d_sj_rows; j.max_chunks = c->sj_chunks;
-  j.min_static_hits = p->min_static_hits; j.trail_num = p->trail_num; j.trail_den = p->trail_den; j.class_mask = class_mask;
-  mot_launch_scene_judge_seq_count(scene_buffers(c), in, j, seq_scene_buffers(c), c->d_sjs_base, frames, c->max_points, L->d_tf, d_segments, d_totals, d_classes, class_stride, c->stream);
+  MOT_TRY(send_link_tf(c, &c->sg_ring, c->d_sj_args, 0, frames, nullptr, &L->d_tf));
+  L->in = scene_input(c, false);   // (slot 0's layout is every frame's: check_seq_judge)
+  L->j = judge_buffers(c, p, class_mask);
+  mot_launch_scene_judge_seq_count(scene_buffers(c), L->in, L->j, seq_scene_buffers(c), c->d_sjs_base, frames, c->max_points, L->d_tf, d_segments, d_totals, d_classes, class_stride, c->stream);
   MOT_HIP(c, hipGetLastError());
   return MOT_OK;
 }

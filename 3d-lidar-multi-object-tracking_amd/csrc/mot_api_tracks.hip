@@ -266,14 +266,6 @@ extern "C" int mot_get_box_tracks(mot_ctx* c, int slot, int32_t* box_track, int 
   return MOT_OK;
 }
 
-static int check_point_tracks(mot_ctx* c, int slot, const char* who) {
-  if (!c->track_links) return fail(c, MOT_E_STATE, who, ": track links are off (mot_set_track_links)");
-  if (!c->res.point_tracks_valid(slot))
-    return fail(c, MOT_E_STATE, who, ": the slot's cloud, boxes and tracker step do not come from one fused call (a stage-wise call took the slot, the tracker was fed from outside, "
-                                     "or no fused call ran the tracker since the links were turned on)");
-  return MOT_OK;
-}
-
 extern "C" int mot_get_point_tracks(mot_ctx* c, int slot, int32_t* ids, int capacity, int* n_elevated) {
   if (!c) return MOT_E_ARG;
   MOT_GUARD(c);
@@ -327,29 +319,17 @@ static int check_track_points_args(mot_ctx* c, const char* who, int flags, int f
   if (frame != MOT_FRAME_GLOBAL && frame != MOT_FRAME_SENSOR) return fail(c, MOT_E_ARG, who, ": frame must be MOT_FRAME_GLOBAL or MOT_FRAME_SENSOR");
   return MOT_OK;
 }
-// the four kernels over slots first .. first + n - 1, block k of the caller's buffers for slot first + k. The slots of one launch share the layout of their clouds (12- or
-// 16-byte points: slots filled by fused calls under different mot_set_fused_outputs may differ), so a batch goes out as one launch per run of slots of one layout — one, as a rule.
+// the four kernels over slots first .. first + n - 1, block k of the caller's buffers for slot first + k; one launch per run of slots of one cloud layout (for_layout_runs)
 static int launch_track_points(mot_ctx* c, int first, int n, int flags, int frame, mot_track_point* d_points, long point_stride, mot_track_segment* d_segments, int max_segments,
                                int* d_counts) {
   const EgoTf* tf = nullptr;
-  if (frame == MOT_FRAME_GLOBAL) {   // the matrices the slots' boxes took, in one stream-ordered copy ahead of the kernels
-    char* raw;
-    MOT_TRY(c->tp_tf_ring.acquire(c, &raw));
-    memcpy(raw, c->link_tf.data() + first, (size_t)n * sizeof(EgoTf));
-    MOT_TRY(c->tp_tf_ring.commit(c, c->d_tp_tf, 0, (size_t)n * sizeof(EgoTf), c->stream));
-    tf = c->d_tp_tf;
-  }
-  TrackPointBuffers t;
-  t.ids = c->d_point_track; t.elevated = c->d_elev; t.cap = c->cap; t.counts = c->d_counts; t.owner = c->d_owner;
-  t.seg_id = c->d_tp_seg_id; t.seg_boxes = c->d_tp_seg_boxes; t.seg_n = c->d_tp_seg_n; t.rows = c->d_tp_rows; t.max_chunks = c->tp_chunks;
-  for (int k0 = 0; k0 < n;) {
-    int k1 = k0 + 1;
-    while (k1 < n && c->res.elev_packed_at(first + k1) == c->res.elev_packed_at(first + k0)) k1++;
-    t.elevated_packed = c->res.elev_packed_at(first + k0) ? 1 : 0;
+  if (frame == MOT_FRAME_GLOBAL) MOT_TRY(send_link_tf(c, &c->tp_tf_ring, c->d_tp_tf, first, n, nullptr, &tf));
+  TrackPointBuffers t = track_point_buffers(c);
+  for_layout_runs(c, first, n, [&](int k0, int k1, int packed) {
+    t.elevated_packed = packed;
     mot_launch_track_points(t, first + k0, k1 - k0, c->max_points, flags & MOT_TRACK_POINTS_REST, tf ? tf + k0 : nullptr, d_points + (long)k0 * point_stride, point_stride,
                             d_segments + (long)k0 * max_segments, max_segments, d_counts + 2 * k0, c->stream);
-    k0 = k1;
-  }
+  });
   MOT_HIP(c, hipGetLastError());
   return MOT_OK;
 }
@@ -382,11 +362,8 @@ extern "C" int mot_get_track_points(mot_ctx* c, int slot, int flags, int frame, 
   mot_track_segment* d_seg = reinterpret_cast<mot_track_segment*>(c->d_tp_stage + (size_t)c->cap * sizeof(mot_track_point));
   int* d_cnt = reinterpret_cast<int*>(d_seg + kTrackPointKeys);
   MOT_TRY(launch_track_points(c, slot, 1, flags, frame, d_pts, c->cap, d_seg, kTrackPointKeys, d_cnt));
-  char* pin;
-  MOT_TRY(pinned_scratch(c, 16, &pin));
-  int* h = reinterpret_cast<int*>(pin);
-  MOT_HIP(c, hipMemcpyAsync(h, d_cnt, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  MOT_HIP(c, hipStreamSynchronize(c->stream));
+  int h[2];
+  MOT_TRY(read_counts(c, d_cnt, 2, h));
   const int ns = h[0], np = h[1];
   if (ns < 0 || ns > kTrackPointKeys || np < 0 || np > c->cap) return fail(c, MOT_E_STATE, who, ": inconsistent counts");
   *n_segments = ns; *n_points = np;
@@ -441,7 +418,7 @@ extern "C" int mot_set_track_accumulation(mot_ctx* c, int points_per_track, int 
   }
   if (!pow2_in(K, 64, 1 << 20)) return fail(c, MOT_E_ARG, who, ": points_per_track must be 0 (off) or a power of two in [64, 2^20]");
   if (O != 0 && !pow2_in(O, 1, 4096)) return fail(c, MOT_E_ARG, who, ": obs_per_track must be 0 or a power of two in [1, 4096]");
-  if (!c->track_links) return fail(c, MOT_E_STATE, who, ": track links are off (mot_set_track_links)");
+  MOT_TRY(check_links_on(c, who));
   if (K == c->accum_K && O == c->accum_O) return MOT_OK;
   // the new tables first: a failure leaves the mode, an earlier geometry included, as it was
   const size_t rows_n = (size_t)c->batch * c->max_tracks_total;
@@ -470,6 +447,14 @@ extern "C" int mot_set_track_accumulation(mot_ctx* c, int points_per_track, int 
 
 static int check_accum_on(mot_ctx* c, const char* who) { return c->accum_K ? MOT_OK : fail(c, MOT_E_STATE, who, ": the per-track accumulators are off (mot_set_track_accumulation)"); }
 
+// the accumulators as the kernels see them: every stream's tables, i.e. stream 0's for a recorded drive (steps: the live launch's stamps, set per run)
+static TrackAccumBuffers accum_buffers(const mot_ctx* c) {
+  TrackAccumBuffers a;
+  a.rows = c->d_ta_rows; a.points = c->d_ta_points; a.obs = c->d_ta_obs; a.plan = c->d_ta_plan; a.slot_of = c->d_slot_of; a.out = c->d_tout; a.steps = nullptr;
+  a.T = c->max_tracks_total; a.E = c->max_tracks_ever; a.K = c->accum_K; a.O = c->accum_O;
+  return a;
+}
+
 extern "C" int mot_accumulate_track_points(mot_ctx* c, int batch) {
   if (!c) return MOT_E_ARG;
   MOT_GUARD(c);
@@ -482,27 +467,15 @@ extern "C" int mot_accumulate_track_points(mot_ctx* c, int batch) {
     if (c->res.accumulated(b)) return fail(c, MOT_E_STATE, who, ": a slot of the batch was already accumulated for its current step, or was reset / loaded since that step");
   }
   MOT_TRY(ensure_track_points(c, false));
-  // the matrices the slots' boxes took and the slots' step stamps, in one stream-ordered copy ahead of the kernels
-  char* raw;
-  MOT_TRY(c->tp_tf_ring.acquire(c, &raw));
-  memcpy(raw, c->link_tf.data(), (size_t)batch * sizeof(EgoTf));
-  memcpy(raw + (size_t)batch * sizeof(EgoTf), c->accum_step.data(), (size_t)batch * sizeof(int));
-  MOT_TRY(c->tp_tf_ring.commit(c, c->d_tp_tf, 0, (size_t)batch * (sizeof(EgoTf) + sizeof(int)), c->stream));
-  TrackPointBuffers t;
-  t.ids = c->d_point_track; t.elevated = c->d_elev; t.cap = c->cap; t.counts = c->d_counts; t.owner = c->d_owner;
-  t.seg_id = c->d_tp_seg_id; t.seg_boxes = c->d_tp_seg_boxes; t.seg_n = c->d_tp_seg_n; t.rows = c->d_tp_rows; t.max_chunks = c->tp_chunks;
-  TrackAccumBuffers a;
-  a.rows = c->d_ta_rows; a.points = c->d_ta_points; a.obs = c->d_ta_obs; a.plan = c->d_ta_plan; a.slot_of = c->d_slot_of; a.out = c->d_tout;
-  a.T = c->max_tracks_total; a.E = c->max_tracks_ever; a.K = c->accum_K; a.O = c->accum_O;
-  const int* d_steps = reinterpret_cast<const int*>(c->d_tp_tf + batch);
-  for (int k0 = 0; k0 < batch;) {   // one launch per run of slots of one cloud layout (launch_track_points)
-    int k1 = k0 + 1;
-    while (k1 < batch && c->res.elev_packed_at(k1) == c->res.elev_packed_at(k0)) k1++;
-    t.elevated_packed = c->res.elev_packed_at(k0) ? 1 : 0;
+  const EgoTf* d_tf; const int* d_steps;   // the matrices the slots' boxes took and the slots' step stamps
+  MOT_TRY(send_link_tf(c, &c->tp_tf_ring, c->d_tp_tf, 0, batch, &c->accum_step, &d_tf, &d_steps));
+  TrackPointBuffers t = track_point_buffers(c);
+  TrackAccumBuffers a = accum_buffers(c);
+  for_layout_runs(c, 0, batch, [&](int k0, int k1, int packed) {
+    t.elevated_packed = packed;
     a.steps = d_steps + k0;
-    mot_launch_track_accum(t, a, k0, k1 - k0, c->max_points, c->d_tp_tf + k0, c->stream);
-    k0 = k1;
-  }
+    mot_launch_track_accum(t, a, k0, k1 - k0, c->max_points, d_tf + k0, c->stream);
+  });
   MOT_HIP(c, hipGetLastError());
   for (int b = 0; b < batch; b++) { c->accum_step[b]++; c->res.step_accumulated(b); }
   return MOT_OK;
@@ -511,15 +484,9 @@ extern "C" int mot_accumulate_track_points(mot_ctx* c, int batch) {
 // ---------------------------------------------------------------------------------------- the accumulators fed by sequence mode (track_accum_seq.hip)
 // mot_sequence_accumulate_dev is mot_sequence_dev's body (mot_api.hip) with these three hooks. The scratch of the feature's own — the capture table and the plan,
 // 72 KB per slot — is taken at the first call, both blocks or neither (a failure leaves the live allocations as they were), and goes with the accumulators.
-static TrackAccumBuffers seq_accum_buffers(const mot_ctx* c) {   // stream 0's rows, rings, slot map and records
-  TrackAccumBuffers a;
-  a.rows = c->d_ta_rows; a.points = c->d_ta_points; a.obs = c->d_ta_obs; a.plan = c->d_ta_plan; a.slot_of = c->d_slot_of; a.out = c->d_tout; a.steps = nullptr;
-  a.T = c->max_tracks_total; a.E = c->max_tracks_ever; a.K = c->accum_K; a.O = c->accum_O;
-  return a;
-}
 int seq_accum_ready(mot_ctx* c, const char* who) {
   MOT_TRY(check_accum_on(c, who));
-  if (!c->track_links) return fail(c, MOT_E_STATE, who, ": track links are off (mot_set_track_links)");
+  MOT_TRY(check_links_on(c, who));
   MOT_TRY(ensure_track_points(c, false));
   if (c->d_tas_cap && c->d_tas_seg) return MOT_OK;
   const size_t n = (size_t)c->batch * kMaxBoxesPerFrame;
@@ -532,15 +499,12 @@ int seq_accum_ready(mot_ctx* c, const char* who) {
   }
   return rc;
 }
-void seq_accum_capture(mot_ctx* c, int frame) { mot_launch_track_accum_capture(c->d_counts, c->d_owner, seq_accum_buffers(c), c->d_tas_cap, frame, c->stream); }
+void seq_accum_capture(mot_ctx* c, int frame) { mot_launch_track_accum_capture(c->d_counts, c->d_owner, accum_buffers(c), c->d_tas_cap, frame, c->stream); }
 int seq_accum_append(mot_ctx* c, int frames, int max_n) {
-  TrackPointBuffers t;
-  t.ids = c->d_point_track; t.elevated = c->d_elev; t.cap = c->cap; t.counts = c->d_counts; t.owner = c->d_owner;
-  t.seg_id = c->d_tp_seg_id; t.seg_boxes = c->d_tp_seg_boxes; t.seg_n = c->d_tp_seg_n; t.rows = c->d_tp_rows; t.max_chunks = c->tp_chunks;
-  t.elevated_packed = c->res.elev_packed_at(0) ? 1 : 0;   // (one fused call filled the slots: one layout)
+  const TrackPointBuffers t = track_point_buffers(c);   // (slot 0's layout: one fused call filled the slots)
   const TrackAccumSeqBuffers s = {c->d_tas_cap, c->d_tas_seg, c->accum_step[0]};
   // frame k's matrix is entry k of the call's own argument block (what link_tf[k] keeps on the host): later calls rewrite it behind these kernels, stream-ordered
-  mot_launch_track_accum_sequence(t, seq_accum_buffers(c), s, frames, max_n, c->d_ego, c->stream);
+  mot_launch_track_accum_sequence(t, accum_buffers(c), s, frames, max_n, c->d_ego, c->stream);
   MOT_HIP(c, hipGetLastError());
   c->accum_step[0] += frames;   // (a frame refused for capacity appended nothing and counts)
   c->res.sequence_accumulated(frames);
@@ -679,24 +643,15 @@ extern "C" int mot_get_track_models(mot_ctx* c, int slot, int flags, mot_track_m
   int* d_cnt = reinterpret_cast<int*>(d_mod + T);
   mot_launch_track_models_plan(a, slot, 1, flags, d_mod, d_cnt, c->stream);
   MOT_HIP(c, hipGetLastError());
-  char* pin;
-  MOT_TRY(pinned_scratch(c, 16, &pin));
-  int* h = reinterpret_cast<int*>(pin);
-  MOT_HIP(c, hipMemcpyAsync(h, d_cnt, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  MOT_HIP(c, hipStreamSynchronize(c->stream));
+  int h[2];
+  MOT_TRY(read_counts(c, d_cnt, 2, h));
   const int np = h[1];
   if (h[0] < 0 || h[0] > T || np < 0) return fail(c, MOT_E_STATE, who, ": inconsistent counts");
   *n_models = T; *n_points = np;
   if (models && T > max_models) return fail(c, MOT_E_CAPACITY, "more models (max_tracks_total) than the caller's buffer holds");
   if (points && np > point_capacity) return fail(c, MOT_E_CAPACITY, "more records than the caller's point buffer holds");
   const bool want_points = points && np > 0;
-  if (want_points && c->tm_points_cap < (size_t)np) {   // (the stream is drained: nothing reads the old block)
-    MOT_TRY(release(c, &c->d_tm_points));
-    c->tm_points_cap = 0;
-    const size_t want = ((size_t)np + 65535) & ~(size_t)65535;
-    MOT_TRY(dev_alloc(c, &c->d_tm_points, want * sizeof(mot_accum_point)));
-    c->tm_points_cap = want;
-  }
+  if (want_points) MOT_TRY(grow_stage(c, &c->d_tm_points, &c->tm_points_cap, (size_t)np, sizeof(mot_accum_point)));
   mot_launch_track_models_transform(a, slot, 1, flags, want_points ? c->d_tm_points : nullptr, want_points ? (long)np : 0, d_mod, c->stream);   // (the extents, with or without records)
   MOT_HIP(c, hipGetLastError());
   if (models) MOT_HIP(c, hipMemcpyAsync(models, d_mod, (size_t)T * sizeof(mot_track_model), hipMemcpyDeviceToHost, c->stream));
@@ -778,24 +733,15 @@ extern "C" int mot_get_track_model_voxels(mot_ctx* c, int slot, int flags, const
   mot_launch_track_models_plan(a, slot, 1, flags, s.plan, s.plan_counts, c->stream);
   mot_launch_track_voxels_count(a, slot, 1, flags, v, s.plan, s.res, d_mod, d_cnt, c->stream);
   MOT_HIP(c, hipGetLastError());
-  char* pin;
-  MOT_TRY(pinned_scratch(c, 16, &pin));
-  int* h = reinterpret_cast<int*>(pin);
-  MOT_HIP(c, hipMemcpyAsync(h, d_cnt, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  MOT_HIP(c, hipStreamSynchronize(c->stream));
+  int h[2];
+  MOT_TRY(read_counts(c, d_cnt, 2, h));
   const int nv = h[1];
   if (h[0] < 0 || h[0] > T || nv < 0) return fail(c, MOT_E_STATE, who, ": inconsistent counts");
   *n_models = T; *n_voxels = nv;
   if (models && T > max_models) return fail(c, MOT_E_CAPACITY, "more models (max_tracks_total) than the caller's buffer holds");
   if (voxels && nv > voxel_capacity) return fail(c, MOT_E_CAPACITY, "more voxels than the caller's voxel buffer holds");
   const bool want_voxels = voxels && nv > 0;
-  if (want_voxels && c->tv_voxels_cap < (size_t)nv) {   // (the stream is drained: nothing reads the old block)
-    MOT_TRY(release(c, &c->d_tv_voxels));
-    c->tv_voxels_cap = 0;
-    const size_t want = ((size_t)nv + 65535) & ~(size_t)65535;
-    MOT_TRY(dev_alloc(c, &c->d_tv_voxels, want * sizeof(mot_model_voxel)));
-    c->tv_voxels_cap = want;
-  }
+  if (want_voxels) MOT_TRY(grow_stage(c, &c->d_tv_voxels, &c->tv_voxels_cap, (size_t)nv, sizeof(mot_model_voxel)));
   if (want_voxels) {
     mot_launch_track_voxels_write(a, slot, 1, flags, v, s.plan, c->d_tv_voxels, (long)nv, d_mod, c->stream);
     MOT_HIP(c, hipGetLastError());

@@ -1,6 +1,7 @@
 // mot_host.h — what the host-only translation units of the C-ABI share (mot_api.hip: life cycle, setters, launch sequence, ingest; mot_api_stages.hip: stage-wise calls and
-// getters; mot_api_tracks.hip: tracker, exports, snapshots; mot_api_scene.hip: the scene grid; mot_gather.hip: the RCCL gather): the context, the record of slot residency, and the ONE owner of every device /
-// page-locked allocation, event and captured graph of a context ("ownership", below). No kernel includes this.
+// getters; mot_api_tracks.hip: tracker, exports, snapshots; mot_api_scene.hip: the scene grid; mot_gather.hip: the RCCL gather): the context, the record of slot residency, the ONE owner of every device /
+// page-locked allocation, event and captured graph of a context ("ownership", below), and the ONE owner of each view of the elevated cloud and of each step around a
+// launch that the track and scene calls share (at the end). No kernel includes this.
 #ifndef MOT_HOST_H_
 #define MOT_HOST_H_
 #include "mot_internal.h"
@@ -455,6 +456,84 @@ int seq_accum_append(mot_ctx* c, int frames, int max_n);
 int seq_scene_ready(mot_ctx* c, const char* who, int frames);
 void seq_scene_capture(mot_ctx* c, int frame);
 int seq_scene_append(mot_ctx* c, int frames, int max_n);
+
+// ---------------------------------------------------------------------------------------- the elevated cloud and its links as the track and scene kernels see them
+// ONE owner for each view and for each step around a launch that mot_api_tracks.hip and mot_api_scene.hip share. The views carry slot 0's cloud layout (what a
+// recorded drive has throughout: one fused call filled its slots); a launch over live slots sets elevated_packed per run of for_layout_runs.
+inline int check_links_on(mot_ctx* c, const char* who) { return c->track_links ? MOT_OK : fail(c, MOT_E_STATE, who, ": track links are off (mot_set_track_links)"); }
+// the slot's per-point ids belong to the cloud it holds. THE test of every call that reads them (accumulators and scene grid cannot be on with the links off, so
+// their callers never see the first message)
+inline int check_point_tracks(mot_ctx* c, int slot, const char* who) {
+  MOT_TRY(check_links_on(c, who));
+  if (!c->res.point_tracks_valid(slot))
+    return fail(c, MOT_E_STATE, who, ": the slot's cloud, boxes and tracker step do not come from one fused call (a stage-wise call took the slot, the tracker was fed from outside, "
+                                     "or no fused call ran the tracker since the links were turned on)");
+  return MOT_OK;
+}
+inline TrackPointBuffers track_point_buffers(const mot_ctx* c) {
+  TrackPointBuffers t;
+  t.ids = c->d_point_track; t.elevated = c->d_elev; t.elevated_packed = c->res.elev_packed_at(0) ? 1 : 0; t.cap = c->cap; t.counts = c->d_counts; t.owner = c->d_owner;
+  t.seg_id = c->d_tp_seg_id; t.seg_boxes = c->d_tp_seg_boxes; t.seg_n = c->d_tp_seg_n; t.rows = c->d_tp_rows; t.max_chunks = c->tp_chunks;
+  return t;
+}
+// live: the kind of an owned point comes from the slot's map and records; recorded (a drive's frames): from the captured bits, slot_of / out are not read
+inline SceneSplatInput scene_input(const mot_ctx* c, bool live) {
+  SceneSplatInput in;
+  in.ids = c->d_point_track; in.elevated = c->d_elev; in.elevated_packed = c->res.elev_packed_at(0) ? 1 : 0; in.cap = c->cap; in.counts = c->d_counts;
+  in.slot_of = live ? c->d_slot_of : nullptr; in.out = live ? c->d_tout : nullptr;
+  in.T = c->max_tracks_total; in.E = c->max_tracks_ever;
+  return in;
+}
+inline SceneJudgeBuffers judge_buffers(const mot_ctx* c, const mot_scene_judge_params* p, int class_mask) {
+  SceneJudgeBuffers j;
+  j.cls = c->d_sj_cls; j.rows = c->d_sj_rows; j.max_chunks = c->sj_chunks;
+  j.min_static_hits = p->min_static_hits; j.trail_num = p->trail_num; j.trail_den = p->trail_den; j.class_mask = class_mask;
+  return j;
+}
+// fn(k0, k1, packed) once per run [first + k0, first + k1) of slots whose clouds share a layout (12- or 16-byte points: slots filled by fused calls under different
+// mot_set_fused_outputs may differ), k0 / k1 counted from `first`: a batch goes out as one launch per run — one, as a rule
+template <class Fn> inline void for_layout_runs(const mot_ctx* c, int first, int n, Fn fn) {
+  for (int k0 = 0; k0 < n;) {
+    const bool packed = c->res.elev_packed_at(first + k0);
+    int k1 = k0 + 1;
+    while (k1 < n && c->res.elev_packed_at(first + k1) == packed) k1++;
+    fn(k0, k1, packed ? 1 : 0);
+    k0 = k1;
+  }
+}
+// The matrices the boxes of slots first .. first + n - 1 took (link_tf) and, with `stamps`, those slots' step stamps behind them: through `ring` into `d_block` in ONE
+// stream-ordered copy ahead of the kernels that read them. *d_tf / *d_stamps: where they lie on the device
+inline int send_link_tf(mot_ctx* c, PinnedRing* ring, void* d_block, int first, int n, const std::vector<int>* stamps, const EgoTf** d_tf, const int** d_stamps = nullptr) {
+  char* raw;
+  MOT_TRY(ring->acquire(c, &raw));
+  size_t bytes = (size_t)n * sizeof(EgoTf);
+  memcpy(raw, c->link_tf.data() + first, bytes);
+  if (stamps) { memcpy(raw + bytes, stamps->data() + first, (size_t)n * sizeof(int)); bytes += (size_t)n * sizeof(int); }
+  MOT_TRY(ring->commit(c, d_block, 0, bytes, c->stream));
+  *d_tf = static_cast<const EgoTf*>(d_block);
+  if (stamps) *d_stamps = reinterpret_cast<const int*>(*d_tf + n);
+  return MOT_OK;
+}
+// a getter's grow-only staging block: at least n elements, in steps of 64 Ki; the old block goes first (the caller has drained the stream: nothing reads it)
+inline int grow_stage_as(mot_ctx* c, void** p, size_t* cap, size_t n, size_t elem_bytes, const char* what) {
+  if (*cap >= n) return MOT_OK;
+  MOT_TRY(own_release(c, p));
+  *cap = 0;
+  const size_t want = (n + 65535) & ~(size_t)65535;
+  MOT_TRY(own_alloc(c, p, want * elem_bytes, kOwnDev, what));
+  *cap = want;
+  return MOT_OK;
+}
+#define grow_stage(c, p, cap, n, elem_bytes) grow_stage_as((c), reinterpret_cast<void**>(p), (cap), (n), (elem_bytes), "hipMalloc(" #p ")")
+// a getter's counts (at most four ints) back through the page-locked scratch, the stream drained; the range checks are the caller's
+inline int read_counts(mot_ctx* c, const int* d_cnt, int n_ints, int* host_out) {
+  char* pin;
+  MOT_TRY(pinned_scratch(c, 16, &pin));
+  MOT_HIP(c, hipMemcpyAsync(pin, d_cnt, (size_t)n_ints * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  MOT_HIP(c, hipStreamSynchronize(c->stream));
+  memcpy(host_out, pin, (size_t)n_ints * sizeof(int));
+  return MOT_OK;
+}
 // head of a packed live-track block: one count per slot, padded to 16 bytes; the records follow (mot_export_tracks_packed_dev, mot_gather)
 inline long mot_packed_head_bytes(int batch) { return ((long)batch * 4 + 15) & ~15l; }
 #endif  // MOT_HOST_H_

@@ -138,6 +138,17 @@ constexpr int kCountsStride = 12;                  // ints per frame in `counts`
 enum { kCntElev = 0, kCntGround = 1, kCntDropped = 2, kCntClusters = 3, kCntBoxes = 4, kCntUndef = 5, kCntFlags = 6, kCntPoly = 7, kCntGroups = 8,
        kCntIrregular = 9 };   // kCntGroups, kCntIrregular: label kernel -> index kernel, zero between launches
 enum { kFlagClusterOverflow = 1, kFlagBoxOverflow = 2, kFlagRngExhausted = 4, kFlagHullOverflow = 8, kFlagGroupOverflow = 16 };
+// boxes of frame b's owner row, as every kernel that walks the row counts them: a frame the box stage refused has no owners (link.hip: its points read -1 throughout)
+MOT_HD int mot_owner_boxes(const int* counts, int b) {
+  const int* cnt = counts + (long)b * kCountsStride;
+  const int M = cnt[kCntFlags] != 0 ? 0 : cnt[kCntBoxes];
+  return M < 0 ? 0 : (M > kMaxBoxesPerFrame ? kMaxBoxesPerFrame : M);
+}
+// workgroups per frame of a launch that takes `chunk` points a workgroup, over frames of at most max_n points: at least one, at most what the scratch has rows for
+inline int mot_launch_chunks(int max_n, int chunk, int max_chunks = 0x7fffffff) {
+  const int chunks = (max_n + chunk - 1) / chunk;
+  return chunks < 1 ? 1 : (chunks > max_chunks ? max_chunks : chunks);
+}
 
 struct alignas(64) ClusterStats {   // per cluster, accumulated by the label kernel, reset by the finalize kernel. A cache line each: the five
                                // atomics of a commit go to ONE line and no two clusters share one (40-byte records: the label kernel alone

@@ -1,6 +1,7 @@
 // mot_scene_judge.h — device helpers the judge kernels of scene_judge.hip (every slot against its own grid) and scene_judge_seq.hip (a recorded drive against slot 0's
-// grid) share: THE class rule of a cell, the ballots that count and rank a wave's points by class, the scan over a frame's chunks, the chain over a chunk's tiles and the
-// record store. One definition, so that the last frame of a drive gets the very bytes the frame-by-frame route gives it (include/mot.h). Product code.
+// grid) share: THE class rule of a cell, the ballots that count and rank a wave's points by class, the scan over a frame's chunks, the chain over a chunk's tiles, the
+// record store, and the two bodies built from them — sj_classify_body and sj_scatter_body, each the ONE text of a live and a recorded kernel. One definition, so that
+// the last frame of a drive gets the very bytes the frame-by-frame route gives it (include/mot.h). Product code.
 #ifndef MOT_SCENE_JUDGE_H_
 #define MOT_SCENE_JUDGE_H_
 #include "mot_scene_splat.h"   // the per-point step shared with the splat kernels
@@ -12,9 +13,10 @@ constexpr int kSjWaves = kSceneBlock / 64;
 constexpr int kSjTiles = kSceneChunk / 64;   // tile k * kSjWaves + wave of a chunk: item k of that wave
 constexpr int kSjNone = 7;                   // the class bits of a lane without a point
 
-__device__ __forceinline__ int sj_count(const SceneSplatInput& in, int b) {
-  const int n = in.counts[b * kCountsStride + kCntElev];
-  return n < 0 ? 0 : (n < (int)in.cap ? n : (int)in.cap);
+// the chunks of frame `slot` that the judge has rows for (the frame's points: scene_count, mot_scene_splat.h)
+__device__ __forceinline__ int sj_chunks(const SceneSplatInput& in, const SceneJudgeBuffers& j, int slot) {
+  const int chunks = (scene_count(in, slot) + kSceneChunk - 1) / kSceneChunk;
+  return chunks > j.max_chunks ? j.max_chunks : chunks;
 }
 // the lanes of the wave that hold class c, from the ballots of the three class bits (a lane without a point holds kSjNone)
 __device__ __forceinline__ unsigned long long sj_lanes_of(int c, unsigned long long b0, unsigned long long b1, unsigned long long b2) {
@@ -94,5 +96,93 @@ __device__ __forceinline__ void sj_store_record(mot_track_point* __restrict__ at
   o.w = __int_as_float(index);
   if (vec_out) *reinterpret_cast<float4*>(at) = o;
   else { float* p = reinterpret_cast<float*>(at); p[0] = o.x; p[1] = o.y; p[2] = o.z; p[3] = o.w; }
+}
+
+// THE classify body: chunk blockIdx.x of frame `slot` judged against the grid of slot `of`. What the two kernels decide for themselves and hand in:
+//   live (scene_judge_classify_kernel)          of = slot = b: the slot's own header, validity and cells; kind = SceneKindLive; the caller's class block at kb
+//   recorded (scene_judge_seq_classify_kernel)  of = 0, slot = k: slot 0's header, validity and cells; kind = SceneKindRecorded of frame k; the class block at k
+// The kind is asked of EVERY valid owned point — MOVING needs no cell (the splat body asks only points inside the window). `user`: the frame's share of the
+// caller's class block, or null. Every thread of a workgroup that passes the exit reaches every ballot and the barrier of sj_store_counts.
+template <class Kind>
+__device__ __forceinline__ void sj_classify_body(const SceneGridBuffers& g, const SceneSplatInput& in, const SceneJudgeBuffers& j, int of, int slot, const EgoTf* __restrict__ tf,
+                                                 const Kind& kind, uint8_t* __restrict__ user, long class_stride, int (*s_cnt)[MOT_SCENE_CLASSES]) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int W = g.W;
+  const int n = scene_count(in, slot);
+  const long base = (long)blockIdx.x * kSceneChunk;
+  if (base >= n || (int)blockIdx.x >= j.max_chunks) return;   // (uniform over the workgroup)
+  const int oi = g.hdr[of].origin_i, oj = g.hdr[of].origin_j;
+  const bool window_ok = g.prev[of].ok != 0;   // the latest accepted step (the drive's last frame) placed its window; 0 after the setter, a reset or a load
+  const EgoTf m = *tf;
+  const float inv = g.inv;
+  const SceneCell* __restrict__ cells = g.cells + (long)of * W * W;
+  uint8_t* __restrict__ cls_out = j.cls + (long)slot * in.cap;
+  int id[kSceneItems];
+  float4 q[kSceneItems];
+  scene_load_points(in, slot, base, n, tid, id, q);
+  const SceneRect window = {oi, oi + W, oj, oj + W};
+  int count[MOT_SCENE_CLASSES] = {0, 0, 0, 0, 0};   // of this wave (uniform)
+#pragma unroll
+  for (int k = 0; k < kSceneItems; k++) {
+    const long i = base + k * kSceneBlock + tid;
+    const bool valid = i < n;
+    const int dynamic = (valid && id[k] >= 0) ? kind.dynamic(id[k]) : 0;
+    float gz;
+    const int at = scene_point_cell(m, q[k], inv, valid && window_ok, window, W, &gz);   // (mot_scene_splat.h: the cell the point would be counted in)
+    const int c = sj_class(dynamic, at, cells, j);
+    if (valid) {
+      cls_out[i] = (uint8_t)c;
+      if (user && i < class_stride) user[i] = (uint8_t)c;
+    }
+    sj_tally(valid ? c : kSjNone, count);
+  }
+  sj_store_counts(s_cnt, count, j.rows + ((long)slot * j.max_chunks + blockIdx.x) * kSceneJudgeRow, tid, lane, wave);
+}
+
+// THE scatter body (no kind: it reads the classify body's bytes): the selected records of chunk blockIdx.x of frame `slot` into `out`, below `lim`.
+//   live (scene_judge_scatter_kernel)          kDrive = false: the chain starts at row[5 + c]; out = the caller's block kb, lim = point_stride, dst >= lim is skipped
+//   recorded (scene_judge_seq_scatter_kernel)  kDrive = true: the chain starts at bases[c] + row[5 + c] (bases: frame k's five drive-wide places); out = the drive's ONE
+//                                              block, lim = its capacity, dst < 0 || dst >= lim is skipped
+// tf: the frame's matrix (entry kb / k of what the launch was given) when the records are global, else null. Only the points of selected classes are loaded.
+template <bool kDrive>
+__device__ __forceinline__ void sj_scatter_body(const SceneSplatInput& in, const SceneJudgeBuffers& j, int slot, const int* __restrict__ bases, const EgoTf* __restrict__ tf,
+                                                mot_track_point* __restrict__ out, long lim, int (*s_cnt)[MOT_SCENE_CLASSES], int (*s_at)[MOT_SCENE_CLASSES]) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int n = scene_count(in, slot);
+  const long base = (long)blockIdx.x * kSceneChunk;
+  if (base >= n || (int)blockIdx.x >= j.max_chunks) return;   // (uniform over the workgroup)
+  const uint8_t* __restrict__ cls_in = j.cls + (long)slot * in.cap;
+  const float4* __restrict__ cloud = in.elevated + (long)slot * in.cap;
+  const int* __restrict__ row = j.rows + ((long)slot * j.max_chunks + blockIdx.x) * kSceneJudgeRow;
+  const bool vec_out = (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+  int cls[kSceneItems];
+  float4 q[kSceneItems];
+#pragma unroll
+  for (int k = 0; k < kSceneItems; k++) {
+    const long i = base + k * kSceneBlock + tid;
+    cls[k] = i < n ? (int)cls_in[i] : kSjNone;
+  }
+#pragma unroll
+  for (int k = 0; k < kSceneItems; k++) {   // the points of the selected classes alone
+    const long i = base + k * kSceneBlock + tid;
+    q[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (cls[k] < MOT_SCENE_CLASSES && ((j.class_mask >> cls[k]) & 1)) q[k] = mot_load_xyz(cloud, i, in.elevated_packed);
+  }
+  const unsigned long long below = (1ull << lane) - 1ull;
+  int rank[kSceneItems];
+#pragma unroll
+  for (int k = 0; k < kSceneItems; k++) rank[k] = sj_rank(cls[k], k * kSjWaves + wave, lane, below, s_cnt);   // tile k * 4 + wave of the chunk: points 64 * tile .. 64 * tile + 63
+  __syncthreads();
+  if (tid < MOT_SCENE_CLASSES) sj_chain(s_cnt, s_at, tid, kDrive ? bases[tid] + row[MOT_SCENE_CLASSES + tid] : row[MOT_SCENE_CLASSES + tid]);   // the chunk's tiles in index order
+  __syncthreads();
+  const EgoTf m = tf ? *tf : EgoTf();
+#pragma unroll
+  for (int k = 0; k < kSceneItems; k++) {
+    const long i = base + k * kSceneBlock + tid;
+    if (cls[k] >= MOT_SCENE_CLASSES || !((j.class_mask >> cls[k]) & 1)) continue;
+    const long dst = (long)s_at[k * kSjWaves + wave][cls[k]] + rank[k];
+    if ((kDrive && dst < 0) || dst >= lim) continue;   // never a store outside the slot's records / the caller's block (live: dst < n while the rows are this call's)
+    sj_store_record(out + dst, vec_out, tf != nullptr, m, q[k], (int)i);
+  }
 }
 #endif

@@ -1,6 +1,7 @@
-// mot_scene_splat.h — device helpers the splat kernels of scene_grid.hip (one step per slot) and scene_grid_seq.hip (a recorded drive in one launch) share: the window a
-// matrix asks for, THE per-point step (transform, cell test, storage index) and the wave's merged adds. One definition, so that a drive taken in one call bins the
-// very bits the frame-by-frame route bins (include/mot.h, rolling static-scene grid). Product code.
+// mot_scene_splat.h — what the splat kernels of scene_grid.hip (one step per slot) and scene_grid_seq.hip (a recorded drive in one launch) share: the window a matrix
+// asks for, a frame's points as every scene kernel loads them, the KIND of an owned point (one rule per form), THE per-point step (transform, cell test, storage
+// index), the wave's merged adds and scene_splat_body, the ONE body of both splat kernels. One definition, so that a drive taken in one call bins the very bits the
+// frame-by-frame route bins (include/mot.h, rolling static-scene grid). Product code.
 #ifndef MOT_SCENE_SPLAT_H_
 #define MOT_SCENE_SPLAT_H_
 #include "mot_internal.h"
@@ -32,6 +33,44 @@ __device__ __forceinline__ bool scene_window(const EgoTf& m, float inv, int W, i
   *oj = (int)floorf(c) - W / 2;
   return true;
 }
+
+// ---- a frame's points: slot `slot` of the elevated cloud, as the splat, classify and scatter kernels of both forms see them
+// the clamped count (never beyond the slot: the counts are the device's)
+__device__ __forceinline__ int scene_count(const SceneSplatInput& in, int slot) {
+  const int n = in.counts[slot * kCountsStride + kCntElev];
+  return n < 0 ? 0 : (n < (int)in.cap ? n : (int)in.cap);
+}
+// id[] / q[] of a thread's kSceneItems points of the chunk from `base`; a lane beyond n holds id -1 and a zero point
+__device__ __forceinline__ void scene_load_points(const SceneSplatInput& in, int slot, long base, int n, int tid, int (&id)[kSceneItems], float4 (&q)[kSceneItems]) {
+  const int* __restrict__ ids = in.ids + (long)slot * in.cap;
+  const float4* __restrict__ cloud = in.elevated + (long)slot * in.cap;
+#pragma unroll
+  for (int k = 0; k < kSceneItems; k++) {
+    const long i = base + k * kSceneBlock + tid;
+    id[k] = -1;
+    q[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (i < n) { id[k] = ids[i]; q[k] = mot_load_xyz(cloud, i, in.elevated_packed); }
+  }
+}
+
+// ---- the grid's KIND rule for an OWNED point (id >= 0; a point without owner is static): is its owner something other than a track flagged static? An id or a
+// track slot that is out of range is not followed and counts as dynamic. Splat and classify of a form ask the same struct.
+// live: slot b's map id -> track slot -> is_static as the step left it (two dependent gathers)
+struct SceneKindLive {
+  const int* __restrict__ slot_of; const mot_track* __restrict__ out; int E, T;
+  __device__ __forceinline__ SceneKindLive(const SceneSplatInput& in, int b) : slot_of(in.slot_of + (long)b * in.E), out(in.out + (long)b * in.T), E(in.E), T(in.T) {}
+  __device__ __forceinline__ int dynamic(int id) const {
+    if (id >= E) return 1;
+    const int r = slot_of[id];
+    return (r >= 0 && r < T) ? out[r].is_static == 0 : 1;
+  }
+};
+// recorded: bit `id` of frame k's row of the table scene_seq_capture_kernel filled behind step k (one gather; a slot outside [0, T) set no bit)
+struct SceneKindRecorded {
+  const unsigned* __restrict__ flagged; int E;
+  __device__ __forceinline__ SceneKindRecorded(const SceneSplatInput& in, const SceneSeqBuffers& s, int k) : flagged(s.is_static + (long)k * s.words), E(in.E) {}
+  __device__ __forceinline__ int dynamic(int id) const { return id >= E ? 1 : ((flagged[id >> 5] >> (id & 31)) & 1u) == 0u; }
+};
 
 // global cells [lo_i, hi_i) x [lo_j, hi_j) whose adds count: a step's window, or what is left of it once the later windows of a drive are known (may be empty)
 struct SceneRect { int lo_i, hi_i, lo_j, hi_j; };
@@ -98,5 +137,39 @@ __device__ __forceinline__ void scene_count_wave(mot_scene_header* __restrict__ 
     if (n_dynamic) atomicAdd(&hdr->n_dynamic, (unsigned)n_dynamic);
     if (n_outside) atomicAdd(&hdr->n_outside, (unsigned)n_outside);
   }
+}
+
+// THE splat body: chunk blockIdx.x of frame `slot` into `cells`. What the two kernels decide for themselves and hand in:
+//   live (scene_splat_kernel)          rect = the slot's window from its header, ok = prev[b].ok (and workgroup (0, b) moves prev[b]'s origin on, in the kernel);
+//                                      kSeenMax = false: last_seen is stored plainly; count = true: the counters are always added; cells and header are slot b's
+//   recorded (scene_seq_splat_kernel)  rect = R[k], ok = s.win[k + 1].ok (a frame that is not the last has left, in the kernel, when nothing of it survives);
+//                                      kSeenMax = true: last_seen by atomicMax; count = the frame is the last one; cells and header are slot 0's
+// The kind is asked only of a point that is `inside`: no gather for a point that adds nothing (the classify body asks every valid point: MOVING needs no cell).
+// No exit on max_chunks here (the judge's bodies have one): the launch's grid is the chunk count. Every lane of a wave reaches every scene_add_wave.
+template <bool kSeenMax, class Kind>
+__device__ __forceinline__ void scene_splat_body(const SceneSplatInput& in, int slot, const EgoTf* __restrict__ tf, float inv, bool window_ok, const SceneRect& rect, int W,
+                                                 const Kind& kind, SceneCell* __restrict__ cells, int stamp, mot_scene_header* __restrict__ hdr, bool count) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int n = scene_count(in, slot);
+  const long base = (long)blockIdx.x * kSceneChunk;
+  if (base >= n) return;   // (uniform over the workgroup)
+  const EgoTf m = *tf;
+  int id[kSceneItems];
+  float4 q[kSceneItems];
+  scene_load_points(in, slot, base, n, tid, id, q);
+  int n_static = 0, n_dynamic = 0, n_outside = 0;
+#pragma unroll
+  for (int k = 0; k < kSceneItems; k++) {
+    const long i = base + k * kSceneBlock + tid;
+    const bool valid = i < n;
+    float gz;
+    const int at = scene_point_cell(m, q[k], inv, valid && window_ok, rect, W, &gz);
+    const bool inside = at >= 0;
+    const int dynamic = (inside && id[k] >= 0) ? kind.dynamic(id[k]) : 0;
+    n_static += inside && !dynamic; n_dynamic += inside && dynamic; n_outside += valid && !inside;
+    // what the point adds to: (storage index, kind), -1: nothing
+    scene_add_wave<kSeenMax>(cells, inside ? ((at << 1) | dynamic) : -1, gz, stamp, lane);
+  }
+  if (count) scene_count_wave(hdr, n_static, n_dynamic, n_outside, lane);   // (uniform over the launch's row of workgroups)
 }
 #endif

@@ -24,6 +24,11 @@ __device__ __forceinline__ int tp_count(const TrackPointBuffers& t, int b) {
   const int n = t.counts[b * kCountsStride + kCntElev];
   return n < 0 ? 0 : (n < (int)t.cap ? n : (int)t.cap);
 }
+// ... and the chunks of them that t.rows has a row for
+__device__ __forceinline__ int tp_chunks(const TrackPointBuffers& t, int b) {
+  const int chunks = (tp_count(t, b) + kTrackPointChunk - 1) / kTrackPointChunk;
+  return chunks > t.max_chunks ? t.max_chunks : chunks;
+}
 __device__ __forceinline__ int tp_segments(const TrackPointBuffers& t, int b) {
   const int r = t.seg_n[b];
   return r < 0 ? 0 : (r < kMaxBoxesPerFrame ? r : kMaxBoxesPerFrame);

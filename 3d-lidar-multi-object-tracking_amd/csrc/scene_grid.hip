@@ -12,7 +12,8 @@
 //                             transform, the cell test, and for an owned point the two dependent gathers id -> track slot -> is_static (track_accum_plan's reads).
 //                             Then, wave by wave, ONE lane per run of neighbouring lanes with the same (cell, kind) adds the run's length and its largest z
 //                             (MOT_SCENE_MERGE, below); the three counters of the step are summed per wave first. Workgroup (0, b) moves the previous origin on.
-//                             The per-point step and the merged adds are scene_point_cell / scene_add_wave of mot_scene_splat.h, shared with scene_grid_seq.hip
+//                             The kernel decides the slot's window, validity, stamp and cells and moves the origin on; everything per point is scene_splat_body of
+//                             mot_scene_splat.h (kind: SceneKindLive), the ONE body it shares with scene_seq_splat_kernel of scene_grid_seq.hip
 //   G2  scene_export_kernel   the torus unrolled into the caller's block, one 16-byte load and one 16-byte store a cell; the z image converted; the header copied
 //   --  scene_reset_kernel    headers and previous origins of a run of slots back to "no step yet" (the setter, the resets, mot_stream_load; the cells by a memset)
 //
@@ -28,7 +29,7 @@
 // storage index is (gi & (W - 1)) + (gj & (W - 1)) * W < W^2 by construction, the slot offset b * W^2 with b below the launch's batch <= max_batch. Point and id loads stay
 // below min(count, cap) of the slot; an id outside [0, E) or a track slot outside [0, T) is not followed (the point then counts as dynamic: an owner that is not static).
 // Resources (tools/kernel_resources.py): no LDS, no scratch.
-#include "mot_scene_splat.h"   // the window rule, the per-point step and the merged adds, shared with scene_grid_seq.hip
+#include "mot_scene_splat.h"   // the window rule, the kind rules, the per-point step, the merged adds and the splat body, shared with scene_grid_seq.hip
 
 static_assert(sizeof(mot_scene_cell) == 16 && sizeof(SceneCell) == 16 && sizeof(mot_scene_header) == 32 && sizeof(SceneWindow) == 16, "include/mot.h documents the sizes");
 
@@ -67,53 +68,13 @@ scene_scroll_kernel(SceneGridBuffers g, int b0, const EgoTf* __restrict__ tf, co
 // ------------------------------------------------------------------------------------------ G1
 __global__ void MOT_SG_BOUNDS(kSceneBlock)
 scene_splat_kernel(SceneGridBuffers g, SceneSplatInput in, int b0, const EgoTf* __restrict__ tf, const int* __restrict__ steps) {
-  const int kb = blockIdx.y, b = b0 + kb, tid = threadIdx.x, lane = tid & 63;
+  const int kb = blockIdx.y, b = b0 + kb;
   const int W = g.W;
   mot_scene_header* __restrict__ hdr = g.hdr + b;
   const int oi = hdr->origin_i, oj = hdr->origin_j;
-  if (blockIdx.x == 0 && tid == 0) { g.prev[b].oi = oi; g.prev[b].oj = oj; }   // (G0 of the next step reads them; nobody in this launch does)
-  int n = in.counts[b * kCountsStride + kCntElev];
-  n = n < 0 ? 0 : (n < (int)in.cap ? n : (int)in.cap);
-  const long base = (long)blockIdx.x * kSceneChunk;
-  if (base >= n) return;   // (uniform over the workgroup)
-  const bool window_ok = g.prev[b].ok != 0;
-  const int stamp = steps[kb] + 1;
-  const EgoTf m = tf[kb];
-  const float inv = g.inv;
-  const int* __restrict__ ids = in.ids + (long)b * in.cap;
-  const float4* __restrict__ cloud = in.elevated + (long)b * in.cap;
-  SceneCell* __restrict__ cells = g.cells + (long)b * W * W;
-  int id[kSceneItems];
-  float4 q[kSceneItems];
-#pragma unroll
-  for (int k = 0; k < kSceneItems; k++) {
-    const long i = base + k * kSceneBlock + tid;
-    id[k] = -1;
-    q[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (i < n) { id[k] = ids[i]; q[k] = mot_load_xyz(cloud, i, in.elevated_packed); }
-  }
-  int n_static = 0, n_dynamic = 0, n_outside = 0;
+  if (blockIdx.x == 0 && threadIdx.x == 0) { g.prev[b].oi = oi; g.prev[b].oj = oj; }   // (G0 of the next step reads them; nobody in this launch does)
   const SceneRect window = {oi, oi + W, oj, oj + W};
-#pragma unroll
-  for (int k = 0; k < kSceneItems; k++) {
-    const long i = base + k * kSceneBlock + tid;
-    const bool valid = i < n;
-    float gz;
-    const int at = scene_point_cell(m, q[k], inv, valid && window_ok, window, W, &gz);   // (mot_scene_splat.h)
-    const bool inside = at >= 0;
-    int dynamic = 0;
-    if (inside && id[k] >= 0) {
-      dynamic = 1;
-      if (id[k] < in.E) {
-        const int r = in.slot_of[(long)b * in.E + id[k]];
-        if (r >= 0 && r < in.T) dynamic = in.out[(long)b * in.T + r].is_static == 0;
-      }
-    }
-    n_static += inside && !dynamic; n_dynamic += inside && dynamic; n_outside += valid && !inside;
-    // what the point adds to: (storage index, kind), -1: nothing. Every lane of the wave is here (no divergent exit above)
-    scene_add_wave<false>(cells, inside ? ((at << 1) | dynamic) : -1, gz, stamp, lane);
-  }
-  scene_count_wave(hdr, n_static, n_dynamic, n_outside, lane);
+  scene_splat_body<false>(in, b, tf + kb, g.inv, g.prev[b].ok != 0, window, W, SceneKindLive(in, b), g.cells + (long)b * W * W, steps[kb] + 1, hdr, true);
 }
 
 // ------------------------------------------------------------------------------------------ G2
@@ -148,8 +109,7 @@ scene_reset_kernel(SceneGridBuffers g, int first, int n) {
 
 // ------------------------------------------------------------------------------------------ host
 void mot_launch_scene_accumulate(const SceneGridBuffers& g, const SceneSplatInput& in, int first, int batch, int max_n, const EgoTf* tf, const int* steps, hipStream_t stream) {
-  int chunks = (max_n + kSceneChunk - 1) / kSceneChunk;
-  if (chunks < 1) chunks = 1;   // (workgroup 0 of a frame also moves the previous origin on)
+  const int chunks = mot_launch_chunks(max_n, kSceneChunk);   // (at least one: workgroup 0 of a frame also moves the previous origin on)
   hipLaunchKernelGGL(scene_scroll_kernel, dim3(kSceneScrollBlocks, batch), dim3(kSceneBlock), 0, stream, g, first, tf, steps);
   hipLaunchKernelGGL(scene_splat_kernel, dim3(chunks, batch), dim3(kSceneBlock), 0, stream, g, in, first, tf, steps);
 }

@@ -17,10 +17,11 @@
 //   Q1  scene_seq_windows_kernel   ONE workgroup: ok[k] and o[k] of every frame from the matrices (the carry through invalid windows is a last-valid scan), the suffix
 //                                  maxima / minima -> R[-1 .. F - 1]; the final header (the last frame's origin and stamp, counters 0) and the final previous origin
 //   Q2  scene_seq_clear_kernel     the columns and rows of the torus outside R[-1] (one run each: the window minus a rectangle inside it), or everything
-//   Q3  scene_seq_splat_kernel     grid (chunks, frames), chunk index fastest: scene_splat_kernel's body (mot_scene_splat.h: the same per-point step, the same merged adds)
-//                                  with frame k's matrix, stamp, validity and rectangle; the kind from the captured bits; last_seen by atomicMax of stamp + 1, since
-//                                  several frames hit a cell in one launch. Only frame F - 1 feeds the header's counters (against its own window = R[F - 1]). A frame
-//                                  with an invalid window or an empty rectangle leaves at once, frame F - 1 never does
+//   Q3  scene_seq_splat_kernel     grid (chunks, frames), chunk index fastest: scene_splat_body (mot_scene_splat.h), the ONE body it shares with scene_splat_kernel.
+//                                  The kernel decides what differs: frame k's matrix, stamp, validity and rectangle; the kind from the captured bits
+//                                  (SceneKindRecorded); last_seen by atomicMax of stamp + 1, since several frames hit a cell in one launch; only frame F - 1 feeds the
+//                                  header's counters (against its own window = R[F - 1]). A frame with an invalid window or an empty rectangle leaves at once,
+//                                  frame F - 1 never does
 //
 // INTEGER ATOMICS ONLY (adds, maxima, one OR); nobody waits for another workgroup; Q1's two scans hand values over inside one workgroup across __syncthreads().
 // INDEX SAFETY as in scene_grid.hip: the storage index is masked, point and id loads stay below min(count, cap) of the frame's slot, an id outside [0, E) is not looked up
@@ -37,9 +38,7 @@ constexpr int kSeqIntMax = 2147483647, kSeqIntMin = -2147483647 - 1;
 __global__ void MOT_SG_BOUNDS(kSceneBlock)
 scene_seq_capture_kernel(const int* __restrict__ counts, const int* __restrict__ owner, const int* __restrict__ slot_of, const mot_track* __restrict__ out, int T, int E,
                          SceneSeqBuffers s, int k) {
-  const int* __restrict__ cnt = counts + (long)k * kCountsStride;
-  int M = cnt[kCntFlags] != 0 ? 0 : cnt[kCntBoxes];   // (a frame the box stage refused has no owners: link.hip)
-  M = M < 0 ? 0 : (M > kMaxBoxesPerFrame ? kMaxBoxesPerFrame : M);
+  const int M = mot_owner_boxes(counts, k);
   unsigned* __restrict__ row = s.is_static + (long)k * s.words;
   for (int i = threadIdx.x; i < M; i += kSceneBlock) {
     const int id = owner[(long)k * kMaxBoxesPerFrame + i];
@@ -137,49 +136,13 @@ scene_seq_clear_kernel(SceneGridBuffers g, SceneSeqBuffers s) {
 // ------------------------------------------------------------------------------------------ Q3
 __global__ void MOT_SG_BOUNDS(kSceneBlock)
 scene_seq_splat_kernel(SceneGridBuffers g, SceneSplatInput in, SceneSeqBuffers s, const EgoTf* __restrict__ tf, int frames) {
-  const int k = blockIdx.y, tid = threadIdx.x, lane = tid & 63;   // frame k lives in slot k; the grid is slot 0's
-  const int W = g.W;
+  const int k = blockIdx.y;   // frame k lives in slot k; the grid is slot 0's
   const SceneSeqFrame f = s.win[k + 1];
   const bool last = k == frames - 1;
   const bool window_ok = f.ok != 0;
   if (!last && (!window_ok || f.hi_i <= f.lo_i || f.hi_j <= f.lo_j)) return;   // nothing of the frame survives the drive; the last frame's counters are due either way
-  int n = in.counts[k * kCountsStride + kCntElev];
-  n = n < 0 ? 0 : (n < (int)in.cap ? n : (int)in.cap);
-  const long base = (long)blockIdx.x * kSceneChunk;
-  if (base >= n) return;   // (uniform over the workgroup)
-  const int stamp = s.step0 + k + 1;
-  const EgoTf m = tf[k];
-  const float inv = g.inv;
   const SceneRect rect = {f.lo_i, f.hi_i, f.lo_j, f.hi_j};
-  const int* __restrict__ ids = in.ids + (long)k * in.cap;
-  const float4* __restrict__ cloud = in.elevated + (long)k * in.cap;
-  const unsigned* __restrict__ flagged = s.is_static + (long)k * s.words;
-  int id[kSceneItems];
-  float4 q[kSceneItems];
-#pragma unroll
-  for (int j = 0; j < kSceneItems; j++) {
-    const long i = base + j * kSceneBlock + tid;
-    id[j] = -1;
-    q[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (i < n) { id[j] = ids[i]; q[j] = mot_load_xyz(cloud, i, in.elevated_packed); }
-  }
-  int n_static = 0, n_dynamic = 0, n_outside = 0;
-#pragma unroll
-  for (int j = 0; j < kSceneItems; j++) {
-    const long i = base + j * kSceneBlock + tid;
-    const bool valid = i < n;
-    float gz;
-    const int at = scene_point_cell(m, q[j], inv, valid && window_ok, rect, W, &gz);
-    const bool inside = at >= 0;
-    int dynamic = 0;
-    if (inside && id[j] >= 0) {   // scene_splat_kernel's cases: beyond E dynamic, a slot outside [0, T) dynamic (Q0 set no bit), else is_static == 0
-      dynamic = 1;
-      if (id[j] < in.E) dynamic = ((flagged[id[j] >> 5] >> (id[j] & 31)) & 1u) == 0u;
-    }
-    n_static += inside && !dynamic; n_dynamic += inside && dynamic; n_outside += valid && !inside;
-    scene_add_wave<true>(g.cells, inside ? ((at << 1) | dynamic) : -1, gz, stamp, lane);   // (every lane of the wave is here)
-  }
-  if (last) scene_count_wave(g.hdr, n_static, n_dynamic, n_outside, lane);   // (uniform over the launch's row of workgroups)
+  scene_splat_body<true>(in, k, tf + k, g.inv, window_ok, rect, g.W, SceneKindRecorded(in, s, k), g.cells, s.step0 + k + 1, g.hdr, last);
 }
 
 // ------------------------------------------------------------------------------------------ host
@@ -188,8 +151,7 @@ void mot_launch_scene_seq_capture(const int* counts, const int* owner, const int
   hipLaunchKernelGGL(scene_seq_capture_kernel, dim3(1), dim3(kSceneBlock), 0, stream, counts, owner, slot_of, out, T, E, s, frame);
 }
 void mot_launch_scene_sequence(const SceneGridBuffers& g, const SceneSplatInput& in, const SceneSeqBuffers& s, int frames, int max_n, const EgoTf* tf, hipStream_t stream) {
-  int chunks = (max_n + kSceneChunk - 1) / kSceneChunk;
-  if (chunks < 1) chunks = 1;
+  const int chunks = mot_launch_chunks(max_n, kSceneChunk);
   hipLaunchKernelGGL(scene_seq_windows_kernel, dim3(1), dim3(kSceneBlock), 0, stream, g, s, tf, frames);
   hipLaunchKernelGGL(scene_seq_clear_kernel, dim3(kSceneSeqClearBlocks), dim3(kSceneBlock), 0, stream, g, s);
   hipLaunchKernelGGL(scene_seq_splat_kernel, dim3(chunks, frames), dim3(kSceneBlock), 0, stream, g, in, s, tf, frames);

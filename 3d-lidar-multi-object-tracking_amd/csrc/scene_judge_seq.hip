@@ -4,17 +4,16 @@
 // call (slot k = frame k of stream 0) against slot 0's grid AS IT STANDS, i.e. with hindsight, and pack the records class-major over the whole drive into ONE block of
 // the caller's: the KNOWN points of all frames are one contiguous run — the static map (include/mot.h, "a drive's points judged against its grid"). The grid is only READ.
 //
-//   S1  scene_judge_seq_classify_kernel  grid (ceil(N_e / 2048), frames), chunk index fastest, 256 threads, 8 points a thread — scene_judge_classify_kernel's geometry and
-//                                        body with three differences: the kind of an owned point is ONE 4-byte gather from frame k's row of the captured bit table
-//                                        (scene_seq_capture_kernel: flagged static as step k left it; scene_seq_splat_kernel's cases), the matrix is frame k's, and the
-//                                        window, its validity and the cells (ONE 8-byte gather of the two counters) are slot 0's. The class byte and the chunk's five counts
-//                                        (ballots, merged through LDS) leave as plain stores
+//   S1  scene_judge_seq_classify_kernel  grid (ceil(N_e / 2048), frames), chunk index fastest, 256 threads, 8 points a thread — scene_judge_classify_kernel's geometry, and
+//                                        its body: sj_classify_body (mot_scene_judge.h). The kernel hands in what differs: the kind of an owned point is ONE 4-byte gather
+//                                        from frame k's row of the captured bit table (SceneKindRecorded: flagged static as step k left it), the matrix and the class
+//                                        block are frame k's, and the window, its validity and the cells (ONE 8-byte gather of the two counters) are slot 0's
 //   S2  scene_judge_seq_scan_kernel      one workgroup per frame: per class the exclusive scan over the frame's chunks (sj_scan_chunks, scene_judge_scan_kernel's) and the
 //                                        frame's five totals
 //   S3  scene_judge_seq_bases_kernel     ONE workgroup: per class a scan over the frames, 256 frames a round (block_scan_excl_i32), the carry in a register; classes ascending, so
 //                                        the start of a class's run is known when its turn comes. Every (frame, class) gets its drive-wide base; both tables are written
-//   S4  scene_judge_seq_scatter_kernel   the grid of S1: class byte in, rank inside the 64-point tile by ballots, the chunk's 32 tiles chained through the 32 x 5 LDS table
-//                                        from (drive-wide base + the chunk's place inside the frame), one 16-byte store per selected record below the capacity
+//   S4  scene_judge_seq_scatter_kernel   the grid of S1, sj_scatter_body<true>: class byte in, rank inside the 64-point tile by ballots, the chunk's 32 tiles chained through the
+//                                        32 x 5 LDS table from (drive-wide base + the chunk's place inside the frame), one 16-byte store per selected record below the capacity
 //
 // Four launches whatever `frames` is (three for the counts alone). No global atomics, no workgroup waits on another, every count and place is a sum of integers over a
 // fixed set: the output does not depend on the order in which workgroups or waves run.
@@ -30,51 +29,8 @@ __global__ void MOT_SG_BOUNDS(kSceneBlock)
 scene_judge_seq_classify_kernel(SceneGridBuffers g, SceneSplatInput in, SceneJudgeBuffers j, SceneSeqBuffers s, const EgoTf* __restrict__ tf, uint8_t* __restrict__ classes,
                                 long class_stride) {
   __shared__ int s_cnt[kSjWaves][MOT_SCENE_CLASSES];
-  const int k = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;   // frame k lives in slot k; grid, header and validity are slot 0's
-  const int W = g.W;
-  const int n = sj_count(in, k);
-  const long base = (long)blockIdx.x * kSceneChunk;
-  if (base >= n || (int)blockIdx.x >= j.max_chunks) return;   // (uniform over the workgroup)
-  const int oi = g.hdr[0].origin_i, oj = g.hdr[0].origin_j;
-  const bool window_ok = g.prev[0].ok != 0;   // the drive's last frame placed its window
-  const EgoTf m = tf[k];
-  const float inv = g.inv;
-  const int* __restrict__ ids = in.ids + (long)k * in.cap;
-  const float4* __restrict__ cloud = in.elevated + (long)k * in.cap;
-  const unsigned* __restrict__ flagged = s.is_static + (long)k * s.words;
-  const SceneCell* __restrict__ cells = g.cells;
-  uint8_t* __restrict__ cls_out = j.cls + (long)k * in.cap;
-  uint8_t* __restrict__ user = classes ? classes + (long)k * class_stride : nullptr;
-  int id[kSceneItems];
-  float4 q[kSceneItems];
-#pragma unroll
-  for (int t = 0; t < kSceneItems; t++) {
-    const long i = base + t * kSceneBlock + tid;
-    id[t] = -1;
-    q[t] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (i < n) { id[t] = ids[i]; q[t] = mot_load_xyz(cloud, i, in.elevated_packed); }
-  }
-  const SceneRect window = {oi, oi + W, oj, oj + W};
-  int count[MOT_SCENE_CLASSES] = {0, 0, 0, 0, 0};   // of this wave (uniform)
-#pragma unroll
-  for (int t = 0; t < kSceneItems; t++) {
-    const long i = base + t * kSceneBlock + tid;
-    const bool valid = i < n;
-    int dynamic = 0;
-    if (valid && id[t] >= 0) {   // scene_seq_splat_kernel's cases: beyond E dynamic, no bit (a slot outside [0, T) set none) dynamic
-      dynamic = 1;
-      if (id[t] < in.E) dynamic = ((flagged[id[t] >> 5] >> (id[t] & 31)) & 1u) == 0u;
-    }
-    float gz;
-    const int at = scene_point_cell(m, q[t], inv, valid && window_ok, window, W, &gz);   // (mot_scene_splat.h)
-    const int c = sj_class(dynamic, at, cells, j);
-    if (valid) {
-      cls_out[i] = (uint8_t)c;
-      if (user && i < class_stride) user[i] = (uint8_t)c;
-    }
-    sj_tally(valid ? c : kSjNone, count);
-  }
-  sj_store_counts(s_cnt, count, j.rows + ((long)k * j.max_chunks + blockIdx.x) * kSceneJudgeRow, tid, lane, wave);
+  const int k = blockIdx.y;   // frame k lives in slot k; grid, header and validity are slot 0's
+  sj_classify_body(g, in, j, 0, k, tf + k, SceneKindRecorded(in, s, k), classes ? classes + (long)k * class_stride : nullptr, class_stride, s_cnt);
 }
 
 // ------------------------------------------------------------------------------------------ S2
@@ -84,10 +40,7 @@ scene_judge_seq_scan_kernel(SceneSplatInput in, SceneJudgeBuffers j, int* __rest
   __shared__ int s_part[kSjWaves];
   __shared__ int s_total[MOT_SCENE_CLASSES];
   const int k = blockIdx.x, tid = threadIdx.x;
-  const int n = sj_count(in, k);
-  int chunks = (n + kSceneChunk - 1) / kSceneChunk;
-  if (chunks > j.max_chunks) chunks = j.max_chunks;
-  sj_scan_chunks(j.rows + (long)k * j.max_chunks * kSceneJudgeRow, chunks, s_part, s_total, tid);
+  sj_scan_chunks(j.rows + (long)k * j.max_chunks * kSceneJudgeRow, sj_chunks(in, j, k), s_part, s_total, tid);
   __syncthreads();
   if (tid < MOT_SCENE_CLASSES) totals[k * MOT_SCENE_CLASSES + tid] = s_total[tid];
 }
@@ -131,59 +84,19 @@ scene_judge_seq_scatter_kernel(SceneSplatInput in, SceneJudgeBuffers j, const in
                                long capacity) {
   __shared__ int s_cnt[kSjTiles][MOT_SCENE_CLASSES];   // points of (tile, class)
   __shared__ int s_at[kSjTiles][MOT_SCENE_CLASSES];    // where the tile's first record of the class goes
-  const int k = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int n = sj_count(in, k);
-  const long base = (long)blockIdx.x * kSceneChunk;
-  if (base >= n || (int)blockIdx.x >= j.max_chunks) return;   // (uniform over the workgroup)
-  const uint8_t* __restrict__ cls_in = j.cls + (long)k * in.cap;
-  const float4* __restrict__ cloud = in.elevated + (long)k * in.cap;
-  const int* __restrict__ row = j.rows + ((long)k * j.max_chunks + blockIdx.x) * kSceneJudgeRow;
-  const bool vec_out = (reinterpret_cast<uintptr_t>(out) & 15) == 0;
-  int cls[kSceneItems];
-  float4 q[kSceneItems];
-#pragma unroll
-  for (int t = 0; t < kSceneItems; t++) {
-    const long i = base + t * kSceneBlock + tid;
-    cls[t] = i < n ? (int)cls_in[i] : kSjNone;
-  }
-#pragma unroll
-  for (int t = 0; t < kSceneItems; t++) {   // the points of the selected classes alone
-    const long i = base + t * kSceneBlock + tid;
-    q[t] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (cls[t] < MOT_SCENE_CLASSES && ((j.class_mask >> cls[t]) & 1)) q[t] = mot_load_xyz(cloud, i, in.elevated_packed);
-  }
-  const unsigned long long below = (1ull << lane) - 1ull;
-  int rank[kSceneItems];
-#pragma unroll
-  for (int t = 0; t < kSceneItems; t++) rank[t] = sj_rank(cls[t], t * kSjWaves + wave, lane, below, s_cnt);   // tile t * 4 + wave of the chunk
-  __syncthreads();
-  if (tid < MOT_SCENE_CLASSES) sj_chain(s_cnt, s_at, tid, bases[k * MOT_SCENE_CLASSES + tid] + row[MOT_SCENE_CLASSES + tid]);   // the chunk's tiles in index order
-  __syncthreads();
-  const EgoTf m = tf ? tf[k] : EgoTf();
-#pragma unroll
-  for (int t = 0; t < kSceneItems; t++) {
-    const long i = base + t * kSceneBlock + tid;
-    if (cls[t] >= MOT_SCENE_CLASSES || !((j.class_mask >> cls[t]) & 1)) continue;
-    const long dst = (long)s_at[t * kSjWaves + wave][cls[t]] + rank[t];
-    if (dst < 0 || dst >= capacity) continue;   // never a store outside the caller's block
-    sj_store_record(out + dst, vec_out, tf != nullptr, m, q[t], (int)i);
-  }
+  const int k = blockIdx.y;
+  sj_scatter_body<true>(in, j, k, bases + k * MOT_SCENE_CLASSES, tf ? tf + k : nullptr, out, capacity, s_cnt, s_at);
 }
 
 // ------------------------------------------------------------------------------------------ host
-static int seq_judge_chunks(const SceneJudgeBuffers& j, int max_n) {
-  int chunks = (max_n + kSceneChunk - 1) / kSceneChunk;
-  if (chunks < 1) chunks = 1;
-  return chunks > j.max_chunks ? j.max_chunks : chunks;
-}
 void mot_launch_scene_judge_seq_count(const SceneGridBuffers& g, const SceneSplatInput& in, const SceneJudgeBuffers& j, const SceneSeqBuffers& s, int* bases, int frames, int max_n,
                                       const EgoTf* tf, mot_scene_segment* segments, mot_scene_segment* totals, uint8_t* classes, long class_stride, hipStream_t stream) {
-  hipLaunchKernelGGL(scene_judge_seq_classify_kernel, dim3(seq_judge_chunks(j, max_n), frames), dim3(kSceneBlock), 0, stream, g, in, j, s, tf, classes, class_stride);
+  hipLaunchKernelGGL(scene_judge_seq_classify_kernel, dim3(mot_launch_chunks(max_n, kSceneChunk, j.max_chunks), frames), dim3(kSceneBlock), 0, stream, g, in, j, s, tf, classes, class_stride);
   hipLaunchKernelGGL(scene_judge_seq_scan_kernel, dim3(frames), dim3(kSceneBlock), 0, stream, in, j, bases);
   hipLaunchKernelGGL(scene_judge_seq_bases_kernel, dim3(1), dim3(kSceneBlock), 0, stream, j, bases, frames, segments, totals);
 }
 void mot_launch_scene_judge_seq_scatter(const SceneSplatInput& in, const SceneJudgeBuffers& j, const int* bases, int frames, int max_n, const EgoTf* tf, int global,
                                         mot_track_point* points, long capacity, hipStream_t stream) {
   if (!j.class_mask || !points || capacity <= 0) return;
-  hipLaunchKernelGGL(scene_judge_seq_scatter_kernel, dim3(seq_judge_chunks(j, max_n), frames), dim3(kSceneBlock), 0, stream, in, j, bases, global ? tf : nullptr, points, capacity);
+  hipLaunchKernelGGL(scene_judge_seq_scatter_kernel, dim3(mot_launch_chunks(max_n, kSceneChunk, j.max_chunks), frames), dim3(kSceneBlock), 0, stream, in, j, bases, global ? tf : nullptr, points, capacity);
 }

@@ -28,9 +28,7 @@ static_assert(sizeof(mot_accum_row) == 32 && sizeof(mot_accum_point) == 16 && si
 __global__ void MOT_TP_BOUNDS(kTpBlock)
 track_accum_plan_kernel(TrackPointBuffers t, TrackAccumBuffers a, int b0) {
   const int kb = blockIdx.x, b = b0 + kb, tid = threadIdx.x;
-  const int n = tp_count(t, b);
-  int chunks = (n + kTrackPointChunk - 1) / kTrackPointChunk;
-  if (chunks > t.max_chunks) chunks = t.max_chunks;
+  const int chunks = tp_chunks(t, b);
   const int R = tp_segments(t, b);
   const int step = a.steps[kb];
   int* __restrict__ rows = t.rows + (long)b * t.max_chunks * kTrackPointKeys;
@@ -104,9 +102,7 @@ track_accum_clear_kernel(mot_accum_row* __restrict__ rows, long first, long n) {
 
 // ------------------------------------------------------------------------------------------ host
 void mot_launch_track_accum(const TrackPointBuffers& t, const TrackAccumBuffers& a, int first, int batch, int max_n, const EgoTf* tf, hipStream_t stream) {
-  int chunks = (max_n + kTrackPointChunk - 1) / kTrackPointChunk;
-  if (chunks < 1) chunks = 1;
-  if (chunks > t.max_chunks) chunks = t.max_chunks;
+  const int chunks = mot_launch_chunks(max_n, kTrackPointChunk, t.max_chunks);
   mot_launch_track_point_counts(t, first, batch, max_n, stream);
   hipLaunchKernelGGL(track_accum_plan_kernel, dim3(batch), dim3(kTpBlock), 0, stream, t, a, first);
   hipLaunchKernelGGL(track_accum_scatter_kernel, dim3(chunks, batch), dim3(kTpBlock), 0, stream, t, a, first, tf);

@@ -35,17 +35,10 @@
 
 static_assert(sizeof(TrackAccumCapture) == 40 && sizeof(TrackAccumSeqSeg) == 32, "mot_internal.h documents the sizes");
 
-// boxes of a frame's owner row, as track_points_table_kernel counts them: a frame the box stage refused has no owners
-__device__ __forceinline__ int tas_boxes(const int* __restrict__ counts, int b) {
-  const int* __restrict__ cnt = counts + (long)b * kCountsStride;
-  const int M = cnt[kCntFlags] != 0 ? 0 : cnt[kCntBoxes];
-  return M < 0 ? 0 : (M > kMaxBoxesPerFrame ? kMaxBoxesPerFrame : M);
-}
-
 // ------------------------------------------------------------------------------------------ S0
 __global__ void MOT_TP_BOUNDS(kTpBlock)
 track_accum_capture_kernel(const int* __restrict__ counts, const int* __restrict__ owner, TrackAccumBuffers a, TrackAccumCapture* __restrict__ cap, int k) {
-  const int M = tas_boxes(counts, k);
+  const int M = mot_owner_boxes(counts, k);
   for (int i = threadIdx.x; i < M; i += kTpBlock) {
     const int id = owner[(long)k * kMaxBoxesPerFrame + i];
     const int r = (id >= 0 && id < a.E) ? a.slot_of[id] : -1;   // (stream 0's map and records)
@@ -65,12 +58,10 @@ __global__ void MOT_TP_BOUNDS(kTpBlock)
 track_accum_seq_segments_kernel(TrackPointBuffers t, TrackAccumSeqBuffers s, int T) {
   __shared__ int s_own[kMaxBoxesPerFrame];
   const int b = blockIdx.x, tid = threadIdx.x;
-  const int M = tas_boxes(t.counts, b);
+  const int M = mot_owner_boxes(t.counts, b);
   for (int i = tid; i < M; i += kTpBlock) s_own[i] = t.owner[(long)b * kMaxBoxesPerFrame + i];
   __syncthreads();
-  const int n = tp_count(t, b);
-  int chunks = (n + kTrackPointChunk - 1) / kTrackPointChunk;
-  if (chunks > t.max_chunks) chunks = t.max_chunks;
+  const int chunks = tp_chunks(t, b);
   const int R = tp_segments(t, b);
   int* __restrict__ rows = t.rows + (long)b * t.max_chunks * kTrackPointKeys;
   for (int key = tid; key < R; key += kTpBlock) {
@@ -165,9 +156,7 @@ void mot_launch_track_accum_capture(const int* counts, const int* owner, const T
 }
 void mot_launch_track_accum_sequence(const TrackPointBuffers& t, const TrackAccumBuffers& a, const TrackAccumSeqBuffers& s, int frames, int max_n, const EgoTf* tf,
                                      hipStream_t stream) {
-  int chunks = (max_n + kTrackPointChunk - 1) / kTrackPointChunk;
-  if (chunks < 1) chunks = 1;
-  if (chunks > t.max_chunks) chunks = t.max_chunks;
+  const int chunks = mot_launch_chunks(max_n, kTrackPointChunk, t.max_chunks);
   mot_launch_track_point_counts(t, 0, frames, max_n, stream);
   hipLaunchKernelGGL(track_accum_seq_segments_kernel, dim3(frames), dim3(kTpBlock), 0, stream, t, s, a.T);
   hipLaunchKernelGGL(track_accum_seq_plan_kernel, dim3(1), dim3(kTpBlock), 0, stream, t, a, s, frames);

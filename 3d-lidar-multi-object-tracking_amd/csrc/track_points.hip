@@ -29,10 +29,7 @@ track_points_table_kernel(TrackPointBuffers t, int b0) {
   __shared__ int s_first[kMaxBoxesPerFrame];   // 1: the first box of the row that carries this id
   __shared__ int s_n;
   const int b = b0 + blockIdx.x, tid = threadIdx.x;
-  const int* __restrict__ cnt = t.counts + (long)b * kCountsStride;
-  // a frame the box stage refused has no owners (link.hip: its points read -1 throughout)
-  int M = cnt[kCntFlags] != 0 ? 0 : cnt[kCntBoxes];
-  M = M < 0 ? 0 : (M > kMaxBoxesPerFrame ? kMaxBoxesPerFrame : M);
+  const int M = mot_owner_boxes(t.counts, b);
   if (tid == 0) s_n = 0;
   for (int i = tid; i < M; i += kTpBlock) s_own[i] = t.owner[(long)b * kMaxBoxesPerFrame + i];
   __syncthreads();
@@ -99,9 +96,7 @@ track_points_scan_kernel(TrackPointBuffers t, int b0, int rest, mot_track_segmen
   constexpr int kPer = (kTrackPointKeys + kTpBlock - 1) / kTpBlock;   // 5
   __shared__ int s_part[kTpBlock / 64];
   const int k = blockIdx.x, b = b0 + k, tid = threadIdx.x;
-  const int n = tp_count(t, b);
-  int chunks = (n + kTrackPointChunk - 1) / kTrackPointChunk;
-  if (chunks > t.max_chunks) chunks = t.max_chunks;
+  const int chunks = tp_chunks(t, b);
   const int R = tp_segments(t, b);
   int* __restrict__ rows = t.rows + (long)b * t.max_chunks * kTrackPointKeys;
   mot_track_segment* __restrict__ out = segs + (long)k * max_segments;
@@ -158,17 +153,13 @@ track_points_scatter_kernel(TrackPointBuffers t, int b0, int rest, const EgoTf* 
 
 // ------------------------------------------------------------------------------------------ host
 void mot_launch_track_point_counts(const TrackPointBuffers& t, int first, int batch, int max_n, hipStream_t stream) {
-  int chunks = (max_n + kTrackPointChunk - 1) / kTrackPointChunk;
-  if (chunks < 1) chunks = 1;
-  if (chunks > t.max_chunks) chunks = t.max_chunks;
+  const int chunks = mot_launch_chunks(max_n, kTrackPointChunk, t.max_chunks);
   hipLaunchKernelGGL(track_points_table_kernel, dim3(batch), dim3(kTpBlock), 0, stream, t, first);
   hipLaunchKernelGGL(track_points_count_kernel, dim3(chunks, batch), dim3(kTpBlock), 0, stream, t, first);
 }
 void mot_launch_track_points(const TrackPointBuffers& t, int first, int batch, int max_n, int rest, const EgoTf* tf, mot_track_point* points, long point_stride,
                              mot_track_segment* segs, int max_segments, int* counts_out, hipStream_t stream) {
-  int chunks = (max_n + kTrackPointChunk - 1) / kTrackPointChunk;
-  if (chunks < 1) chunks = 1;
-  if (chunks > t.max_chunks) chunks = t.max_chunks;
+  const int chunks = mot_launch_chunks(max_n, kTrackPointChunk, t.max_chunks);
   const dim3 grid(chunks, batch);
   mot_launch_track_point_counts(t, first, batch, max_n, stream);
   hipLaunchKernelGGL(track_points_scan_kernel, dim3(batch), dim3(kTpBlock), 0, stream, t, first, rest, segs, max_segments, counts_out);
