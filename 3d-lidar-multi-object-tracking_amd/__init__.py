@@ -104,6 +104,9 @@ SCENE_UNKNOWN, SCENE_MOVING, SCENE_TRAIL, SCENE_NEW, SCENE_KNOWN, SCENE_CLASSES 
 SCENE_CLASS_NAMES = ("unknown", "moving", "trail", "new", "known")
 SCENE_SEGMENT_DTYPE = np.dtype([("first", "i4"), ("count", "i4")])
 assert SCENE_SEGMENT_DTYPE.itemsize == 8
+# struct mot_scene_voxel_header of mot_export_sequence_scene_voxels_dev / mot_get_sequence_scene_voxels (voxel-thinned static map of a recorded drive)
+SCENE_VOXEL_HEADER_DTYPE = np.dtype([("n_records", "i4"), ("n_beyond", "i4"), ("n_outside", "i4"), ("n_voxels", "i4"), ("n_sparse", "i4"), ("n_stored", "i4"), ("reserved", "i4", 2)])
+assert SCENE_VOXEL_HEADER_DTYPE.itemsize == 32
 
 
 class MotSceneJudgeParams(C.Structure):
@@ -164,6 +167,7 @@ EXPORTS = (
     "mot_export_track_models_dev", "mot_get_track_models", "mot_export_track_model_voxels_dev", "mot_get_track_model_voxels",
     "mot_set_scene_grid", "mot_accumulate_scene", "mot_export_scene_grid_dev", "mot_get_scene_grid", "mot_sequence_products_dev",
     "mot_export_scene_points_dev", "mot_get_scene_points", "mot_export_sequence_scene_points_dev", "mot_get_sequence_scene_points",
+    "mot_export_sequence_scene_voxels_dev", "mot_get_sequence_scene_voxels",
     "mot_gather_unique_id", "mot_gather_create", "mot_gather_contribute", "mot_gather_result", "mot_gather_synchronize", "mot_gather_destroy", "mot_gather_last_error",
 )
 ABI_VERSION = 6
@@ -514,6 +518,35 @@ class Context:
         pts = pts[: n.value]
         return dict(totals=tot, segments=seg[:F], xyz=pts["xyz"].copy(), index=pts["index"].copy(),
                     classes=[cls[k, : int(elevated[k])].copy() for k in range(F)] if with_classes else None)
+
+    def export_sequence_scene_voxels_dev(self, frames: int, leaf, d_voxels_ptr: int, voxel_capacity: int, d_header_ptr: int, d_totals_ptr: int = 0, min_points: int = 1,
+                                         min_static_hits: int = 1, trail=(1, 2), classes=("known",), record_capacity=None):
+        """the records export_sequence_scene_points_dev(frame="global") would give for `classes`, thinned on the device to one record per occupied voxel of edge `leaf`
+        (a float, or three) of a lattice anchored at the global origin (mot_export_sequence_scene_voxels_dev) -> caller's device blocks: 16-byte voxels
+        (MODEL_VOXEL_DTYPE: the centroid of the cell's records and their number, in ascending (i_z, i_y, i_x); voxels with fewer than min_points records are dropped),
+        the 32-byte header (SCENE_VOXEL_HEADER_DTYPE) and, if given, d_totals[c] = {first, count} of the judge call. record_capacity: the records that take part at
+        the most (None: frames * max_points); the library's scratch grows to 40 bytes a record of it. Reads the grid; asynchronous"""
+        p = MotSceneJudgeParams(int(min_static_hits), int(trail[0]), int(trail[1])); v = voxel_params(leaf, min_points)
+        cap = int(frames) * self.max_points if record_capacity is None else int(record_capacity)
+        self._ck(self.lib.mot_export_sequence_scene_voxels_dev(self._h, int(frames), C.byref(p), _scene_mask(classes), C.byref(v), C.c_long(cap), C.c_void_p(d_voxels_ptr or None),
+                                                               C.c_long(voxel_capacity), C.c_void_p(d_header_ptr or None), C.c_void_p(d_totals_ptr or None)))
+
+    def get_sequence_scene_voxels(self, frames: int, leaf, min_points: int = 1, min_static_hits: int = 1, trail=(1, 2), classes=("known",), record_capacity=None) -> dict:
+        """the same on the host (mot_get_sequence_scene_voxels): xyz [n, 3] and count [n] of the kept voxels in ascending (i_z, i_y, i_x), header (a
+        SCENE_VOXEL_HEADER_DTYPE record), totals [5] (SCENE_SEGMENT_DTYPE). With the defaults: the drive's static map, one point a voxel. The records are sorted
+        ONCE: the judge's counts alone (mot_get_sequence_scene_points without buffers: classify and two scans) bound the voxels by the selected records, then one
+        voxel call fills a buffer of that size"""
+        p = MotSceneJudgeParams(int(min_static_hits), int(trail[0]), int(trail[1])); v = voxel_params(leaf, min_points)
+        mask, F = _scene_mask(classes), int(frames)
+        cap = C.c_long(F * self.max_points if record_capacity is None else int(record_capacity))
+        hdr = np.zeros(1, SCENE_VOXEL_HEADER_DTYPE); tot = np.zeros(SCENE_CLASSES, SCENE_SEGMENT_DTYPE); n = C.c_long(0)
+        seg = np.zeros((max(F, 1), SCENE_CLASSES), SCENE_SEGMENT_DTYPE)
+        self._ck(self.lib.mot_get_sequence_scene_points(self._h, F, C.byref(p), mask, MOT_FRAME_GLOBAL, None, C.c_long(0), C.byref(n), _vp(seg), _vp(tot), None, C.c_long(0)))
+        bound = max(min(n.value, cap.value), 0)   # a voxel holds a record or more
+        vox = np.zeros(max(bound, 1), MODEL_VOXEL_DTYPE)
+        self._ck(self.lib.mot_get_sequence_scene_voxels(self._h, F, C.byref(p), mask, C.byref(v), cap, _vp(vox), C.c_long(bound), C.byref(n), _vp(hdr), _vp(tot)))
+        vox = vox[: n.value]
+        return dict(xyz=vox["xyz"].copy(), count=vox["count"].copy(), header=hdr[0].copy(), totals=tot)
 
     def get_scene_grid(self, slot: int = 0, cells: bool = True) -> dict:
         """one slot's grid on the host (mot_get_scene_grid): header (a SCENE_HEADER_DTYPE record) and cells [size, size] indexed (v, u) (SCENE_CELL_DTYPE;

@@ -1,5 +1,5 @@
 // mot_api_scene.hip — host side of the C-ABI (include/mot.h), the rolling static-scene grid: the setter and what it owns, the per-slot step counters, the state
-// checks of mot_accumulate_scene, the two readers, the frame's points and a recorded drive's points judged against the grid. Kernels: scene_grid.hip, scene_grid_seq.hip, scene_judge.hip, scene_judge_seq.hip. Context and helpers: mot_host.h.
+// checks of mot_accumulate_scene, the two readers, the frame's points and a recorded drive's points judged against the grid, the drive's static map thinned to voxels. Kernels: scene_grid.hip, scene_grid_seq.hip, scene_judge.hip, scene_judge_seq.hip, scene_voxels_seq.hip. Context and helpers: mot_host.h.
 #include "mot_host.h"
 
 // The setter owns the feature's memory: cells, headers, previous origins, the argument block and its ring of page-locked staging blocks are allocated together and
@@ -21,6 +21,7 @@ static int seq_scene_release(mot_ctx* c) {
 static int judge_release(mot_ctx* c) {
   MOT_TRY(release(c, &c->d_sj_cls)); MOT_TRY(release(c, &c->d_sj_rows)); MOT_TRY(release(c, &c->d_sj_args));
   MOT_TRY(release(c, &c->d_sjs_base)); MOT_TRY(release(c, &c->d_sjs_stage));   // (the drive's judge: its bases and its getter's staging block)
+  MOT_TRY(release(c, &c->d_sv_scratch)); c->sv_cap = -1; MOT_TRY(release(c, &c->d_sv_stage));   // (the drive's voxels: scene_voxels_seq.hip)
   return release(c, &c->d_sj_stage);
 }
 static size_t scene_arg_bytes(const mot_ctx* c) { return (size_t)c->batch * (sizeof(EgoTf) + sizeof(int)); }   // [batch] matrices, then [batch] step stamps
@@ -415,5 +416,125 @@ extern "C" int mot_get_sequence_scene_points(mot_ctx* c, int frames, const mot_s
     for (int k = 0; k < frames; k++)
       if (elevated[k] > 0) MOT_HIP(c, hipMemcpyAsync(classes + (size_t)k * class_stride, c->d_sj_cls + (size_t)k * c->cap, (size_t)elevated[k], hipMemcpyDeviceToHost, c->stream));
   MOT_HIP(c, hipStreamSynchronize(c->stream));
+  return MOT_OK;
+}
+
+// ---------------------------------------------------------------------------------------- the drive's static map thinned to a voxel grid (scene_voxels_seq.hip)
+// The validity, the scratch and the count launches are the drive judge's (above); ONE block of this feature's own, laid out by mot_scene_voxel_scratch_bytes for the
+// largest record_capacity asked so far. Growing it drains the stream first (nothing may still read the old block). All of the scratch or none.
+static int check_voxel_args(mot_ctx* c, const char* who, const mot_voxel_params* v, long record_capacity, long voxel_capacity) {
+  if (!v) return fail(c, MOT_E_ARG, who, ": null voxel params");
+  const float leaf[3] = {v->leaf_x, v->leaf_y, v->leaf_z};
+  for (float l : leaf)
+    if (!(l >= 1e-2f && l <= 1e3f)) return fail(c, MOT_E_ARG, who, ": every leaf must be finite and in [1e-2, 1e3] metres");   // (NaN fails both compares)
+  if (v->min_points < 1 || v->min_points > (1 << 30)) return fail(c, MOT_E_ARG, who, ": min_points must lie in [1, 2^30]");
+  if (record_capacity < 0 || record_capacity > 2147483647L) return fail(c, MOT_E_ARG, who, ": record_capacity must lie in [0, 2^31 - 1] (positions are int32)");
+  if (voxel_capacity < 0) return fail(c, MOT_E_ARG, who, ": negative voxel_capacity");
+  return MOT_OK;
+}
+static int ensure_seq_voxels(mot_ctx* c, long record_capacity, bool host_stage) {
+  const bool had_judge = c->d_sj_cls && c->d_sj_rows && c->d_sj_args, had_base = c->d_sjs_base != nullptr, had_stage = c->d_sv_stage != nullptr;
+  MOT_TRY(ensure_seq_judge(c, false));
+  int rc = MOT_OK;
+  bool had_scratch = c->d_sv_scratch != nullptr;   // (a block large enough for this call stays whatever fails behind it)
+  if (c->sv_cap < record_capacity) {
+    had_scratch = false;
+    if (c->d_sv_scratch) {
+      MOT_HIP(c, hipStreamSynchronize(c->stream));
+      MOT_TRY(release(c, &c->d_sv_scratch));
+      c->sv_cap = -1;
+    }
+    rc = dev_alloc(c, &c->d_sv_scratch, mot_scene_voxel_scratch_bytes(record_capacity, c->batch));
+    if (!rc) c->sv_cap = record_capacity;
+  }
+  if (!rc && host_stage) rc = dev_alloc(c, &c->d_sv_stage, 96);
+  if (rc) {   // all blocks or none: what this call took goes back
+    const std::string why = c->err;
+    if (!had_scratch) { (void)release(c, &c->d_sv_scratch); c->sv_cap = -1; }
+    if (!had_stage) (void)release(c, &c->d_sv_stage);
+    if (!had_base) (void)release(c, &c->d_sjs_base);
+    if (!had_judge) { (void)release(c, &c->d_sj_cls); (void)release(c, &c->d_sj_rows); (void)release(c, &c->d_sj_args); }
+    c->err = why;
+    return rc;
+  }
+  return MOT_OK;
+}
+static SceneVoxelBuffers voxel_buffers(const mot_ctx* c, long record_capacity) {
+  SceneVoxelBuffers v;
+  (void)mot_scene_voxel_scratch_bytes(c->sv_cap, c->batch, &v, c->d_sv_scratch);
+  v.cap = (int)record_capacity;
+  v.tiles = (int)((record_capacity + 2047) / 2048); if (v.tiles < 1) v.tiles = 1;
+  return v;
+}
+// the judge's count launches into the scratch's two tables, then the keys, the sort, the runs and the header
+static int launch_seq_voxels_count(mot_ctx* c, int frames, const mot_scene_judge_params* p, int class_mask, const mot_voxel_params* vp, const SceneVoxelBuffers& v,
+                                   long voxel_capacity, mot_scene_voxel_header* d_header, mot_scene_segment* d_totals) {
+  SeqJudgeLaunch L;
+  mot_scene_segment* tab = const_cast<mot_scene_segment*>(v.tab);
+  MOT_TRY(launch_seq_judge_count(c, frames, p, class_mask, tab, tab + (size_t)frames * MOT_SCENE_CLASSES, nullptr, 0, &L));
+  const SceneVoxelArgs a = {1.0f / vp->leaf_x, 1.0f / vp->leaf_y, 1.0f / vp->leaf_z, vp->min_points};
+  mot_launch_scene_voxels_seq_count(L.in, L.j, c->d_sjs_base, frames, c->max_points, L.d_tf, v, a, voxel_capacity, d_header, d_totals, c->stream);
+  MOT_HIP(c, hipGetLastError());
+  return MOT_OK;
+}
+
+extern "C" int mot_export_sequence_scene_voxels_dev(mot_ctx* c, int frames, const mot_scene_judge_params* p, int class_mask, const mot_voxel_params* voxel, long record_capacity,
+                                                    mot_model_voxel* d_voxels, long voxel_capacity, mot_scene_voxel_header* d_header, mot_scene_segment* d_totals) {
+  if (!c) return MOT_E_ARG;
+  MOT_GUARD(c);
+  const char* who = "mot_export_sequence_scene_voxels_dev";
+  MOT_TRY(check_scene_on(c, who));
+  MOT_TRY(check_judge_args(c, who, p, class_mask, MOT_FRAME_GLOBAL));
+  MOT_TRY(check_voxel_args(c, who, voxel, record_capacity, voxel_capacity));
+  if (!d_header || (!d_voxels && voxel_capacity > 0) || ((size_t)d_voxels & 15) || (((size_t)d_header | (size_t)d_totals) & 3))
+    return fail(c, MOT_E_ARG, who, ": bad argument (null header, null voxels with a capacity, voxels off 16 bytes, header or totals off 4 bytes)");
+  MOT_TRY(check_seq_judge(c, who, frames));
+  MOT_TRY(ensure_seq_voxels(c, record_capacity, false));
+  const SceneVoxelBuffers v = voxel_buffers(c, record_capacity);
+  MOT_TRY(launch_seq_voxels_count(c, frames, p, class_mask, voxel, v, voxel_capacity, d_header, d_totals));
+  mot_launch_scene_voxels_seq_write(v, d_voxels, voxel_capacity, c->stream);
+  MOT_HIP(c, hipGetLastError());
+  return MOT_OK;
+}
+
+extern "C" int mot_get_sequence_scene_voxels(mot_ctx* c, int frames, const mot_scene_judge_params* p, int class_mask, const mot_voxel_params* voxel, long record_capacity,
+                                             mot_model_voxel* voxels, long voxel_capacity, long* n_voxels, mot_scene_voxel_header* header, mot_scene_segment totals[5]) {
+  if (!c) return MOT_E_ARG;
+  MOT_GUARD(c);
+  const char* who = "mot_get_sequence_scene_voxels";
+  MOT_TRY(check_scene_on(c, who));
+  MOT_TRY(check_judge_args(c, who, p, class_mask, MOT_FRAME_GLOBAL));
+  MOT_TRY(check_voxel_args(c, who, voxel, record_capacity, voxel_capacity));
+  if (!n_voxels || !header) return fail(c, MOT_E_ARG, who, ": null count or header");
+  MOT_TRY(check_seq_judge(c, who, frames));
+  MOT_TRY(ensure_seq_voxels(c, record_capacity, true));
+  const SceneVoxelBuffers v = voxel_buffers(c, record_capacity);
+  // the counts first (they are always delivered); what fits the caller's buffer is decided here, and the voxels are written into a block of their own size
+  mot_scene_voxel_header* d_hdr = reinterpret_cast<mot_scene_voxel_header*>(c->d_sv_stage);
+  mot_scene_segment* d_tot = reinterpret_cast<mot_scene_segment*>(c->d_sv_stage + sizeof(mot_scene_voxel_header));
+  const size_t table = sizeof(mot_scene_voxel_header) + MOT_SCENE_CLASSES * sizeof(mot_scene_segment);
+  MOT_TRY(launch_seq_voxels_count(c, frames, p, class_mask, voxel, v, voxel_capacity, d_hdr, d_tot));
+  char* pin;
+  MOT_TRY(pinned_scratch(c, table, &pin));
+  MOT_HIP(c, hipMemcpyAsync(pin, d_hdr, table, hipMemcpyDeviceToHost, c->stream));
+  MOT_HIP(c, hipStreamSynchronize(c->stream));
+  const mot_scene_voxel_header* h = reinterpret_cast<const mot_scene_voxel_header*>(pin);
+  const long nv = h->n_voxels;
+  if (nv < 0 || nv > record_capacity || h->n_records < 0) return fail(c, MOT_E_STATE, who, ": inconsistent counts");
+  memcpy(header, h, sizeof(mot_scene_voxel_header));
+  header->n_stored = (voxels && nv <= voxel_capacity) ? (int32_t)nv : 0;   // what this call copies to the caller: all of the voxels or none
+  if (totals) memcpy(totals, pin + sizeof(mot_scene_voxel_header), MOT_SCENE_CLASSES * sizeof(mot_scene_segment));
+  *n_voxels = nv;
+  if (voxels && nv > voxel_capacity) return fail(c, MOT_E_CAPACITY, "more voxels than the caller's buffer holds");
+  if (voxels && nv > 0) {   // a block of this call's own, as large as the voxels (a getter's convenience: the export is the hot path)
+    mot_model_voxel* d_vox = nullptr;
+    MOT_TRY(dev_alloc(c, &d_vox, (size_t)nv * sizeof(mot_model_voxel)));
+    mot_launch_scene_voxels_seq_write(v, d_vox, nv, c->stream);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(voxels, d_vox, (size_t)nv * sizeof(mot_model_voxel), hipMemcpyDeviceToHost, c->stream);
+    const hipError_t e2 = hipStreamSynchronize(c->stream);
+    MOT_TRY(release(c, &d_vox));
+    MOT_HIP_AS(c, "mot_get_sequence_scene_voxels: the voxels", e != hipSuccess ? e : e2);
+  }
   return MOT_OK;
 }

@@ -299,6 +299,10 @@ struct mot_ctx {
   // mot_export_sequence_scene_points_dev / mot_get_sequence_scene_points (scene_judge_seq.hip): the judge's scratch above, and at the first call of these
   int* d_sjs_base = nullptr;               // [batch][5] a frame's points per class, then where its first record of the class goes in the drive's block
   char* d_sjs_stage = nullptr;             // the getter: [batch][5] + [5] segments before they go to the host (allocated at ITS first call)
+  // mot_export_sequence_scene_voxels_dev / mot_get_sequence_scene_voxels (scene_voxels_seq.hip): the drive judge's scratch above, and ONE block of their own
+  char* d_sv_scratch = nullptr;            // mot_scene_voxel_scratch_bytes(sv_cap, batch): keys, payloads, staged records, the sort's table, the plan, the judge's two tables
+  long sv_cap = -1;                        // the record capacity the block was laid out for (grown on demand; -1: none)
+  char* d_sv_stage = nullptr;              // the getter: the header and [5] totals before they go to the host (allocated at ITS first call)
   std::vector<EgoTf> link_tf;          // [batch] the matrix every slot's boxes took in its last fused call with the tracker, kept while links are on (host side)
   Vec2d* d_cp = nullptr;
   TrackItem* d_items = nullptr;

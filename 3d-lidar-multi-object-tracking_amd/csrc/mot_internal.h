@@ -542,16 +542,47 @@ void mot_launch_scene_judge_seq_count(const SceneGridBuffers& g, const SceneSpla
 void mot_launch_scene_judge_seq_scatter(const SceneSplatInput& in, const SceneJudgeBuffers& j, const int* bases, int frames, int max_n, const EgoTf* tf, int global,
                                         mot_track_point* points, long capacity, hipStream_t stream);
 
-#ifdef MOT_HIPEMU
-#define MOT_WAVE_SYNC() ((void)__ballot(1))
-#else
-#define MOT_WAVE_SYNC()                                       \
-  do {                                                        \
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");    \
-    __builtin_amdgcn_wave_barrier();                          \
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");    \
-  } while (0)
-#endif
+// Voxel-thinned static map of a recorded drive (scene_voxels_seq.hip, mot_export_sequence_scene_voxels_dev): behind mot_launch_scene_judge_seq_count with the same j and
+// bases and `tab` as its two tables. The selected records of the drive, in the order of mot_launch_scene_judge_seq_scatter (global frame), are keyed by cell, sorted
+// (mot_sort.h), cut into runs and reduced to one centroid and one count per kept voxel. All of it is library scratch, sized by `cap` records (the call's
+// record_capacity, at least 1 of room): see mot_scene_voxel_scratch_bytes.
+constexpr int kSceneVoxelKeyBits = 56;     // bits of a key that decide the order: 54 of the cell, and two of the all-ones key of a record outside the lattice
+constexpr int kSceneVoxelPlan = 8;         // ints: n_records, records in play, runs, n_outside, n_voxels
+struct SceneVoxelArgs { float inv_x, inv_y, inv_z; int min_points; };   // 1.0f / leaf, computed once on the host in fp32
+struct SceneVoxelBuffers {
+  unsigned long long* key[2];  // [cap] each: the keys at their record position / ping-pong of the sort; the buffer the sort leaves free holds the run table
+  unsigned* val[2];            // [cap] each: the record position a key came from
+  float4* staged;              // [cap] the records at their record position
+  int* table;                  // [256][tiles] the sort's digit table
+  int* totals;                 // [256]
+  int* part;                   // [3][tiles] per tile: run heads, records outside the lattice, kept runs
+  int* plan;                   // [kSceneVoxelPlan]
+  const mot_scene_segment* tab;// [frames][5] segments, then [5] totals: what the count launches wrote
+  int cap, tiles;              // tiles = ceil(cap / 2048), at least 1
+};
+inline size_t mot_scene_voxel_scratch_bytes(long cap, int batch, SceneVoxelBuffers* at = nullptr, char* base = nullptr) {
+  const size_t n = (size_t)((cap < 1 ? 1 : cap) + 3) & ~(size_t)3;   // (every block starts 16-byte aligned)
+  const size_t tiles = (n + 2047) / 2048;
+  size_t o = 0;
+  auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 15) & ~(size_t)15; return at; };
+  const size_t k0 = take(8 * n), k1 = take(8 * n), st = take(16 * n), v0 = take(4 * n), v1 = take(4 * n);
+  const size_t tb = take(4 * 256 * tiles), tt = take(4 * 256), pt = take(4 * 3 * tiles), pl = take(4 * kSceneVoxelPlan);
+  const size_t sg = take(sizeof(mot_scene_segment) * MOT_SCENE_CLASSES * ((size_t)batch + 1));
+  if (at && base) {
+    at->key[0] = reinterpret_cast<unsigned long long*>(base + k0); at->key[1] = reinterpret_cast<unsigned long long*>(base + k1); at->staged = reinterpret_cast<float4*>(base + st);
+    at->val[0] = reinterpret_cast<unsigned*>(base + v0); at->val[1] = reinterpret_cast<unsigned*>(base + v1); at->table = reinterpret_cast<int*>(base + tb);
+    at->totals = reinterpret_cast<int*>(base + tt); at->part = reinterpret_cast<int*>(base + pt); at->plan = reinterpret_cast<int*>(base + pl);
+    at->tab = reinterpret_cast<const mot_scene_segment*>(base + sg);
+  }
+  return o;
+}
+// keys, the sort, runs, kept voxels and the header (d_totals may be null); then — with room for voxels — one wave per run writes the centroids. The write launch
+// reads what the count launches left in the scratch: it may follow them later on the same stream (the getter sizes its block in between)
+void mot_launch_scene_voxels_seq_count(const SceneSplatInput& in, const SceneJudgeBuffers& j, const int* bases, int frames, int max_n, const EgoTf* tf, const SceneVoxelBuffers& v,
+                                       const SceneVoxelArgs& a, long voxel_capacity, mot_scene_voxel_header* header, mot_scene_segment* totals, hipStream_t stream);
+void mot_launch_scene_voxels_seq_write(const SceneVoxelBuffers& v, mot_model_voxel* voxels, long voxel_capacity, hipStream_t stream);
+
+#include "mot_wave_sync.h"   // MOT_WAVE_SYNC (shared with mot_wave.h)
 
 void mot_launch_ground(const MotDevParams& p, const GroundBuffers& g, int batch, int max_n, hipStream_t stream);
 void mot_launch_noop(int batch, hipStream_t stream);   // measurement only: an empty one-workgroup-per-frame launch (mot_debug_skip_kernels)

@@ -85,8 +85,8 @@ __device__ __forceinline__ void sj_chain(const int (*s_cnt)[MOT_SCENE_CLASSES], 
   for (int t = 0; t < kSjTiles; t++) { s_at[t][c] = run; run += s_cnt[t][c]; }
 }
 // one 16-byte record {x, y, z, index}: the point's bits, or (global) mot_track_place.h's sensor -> global step — fp32, left to right; the build has -ffp-contract=off:
-// the bits mot_export_track_points_dev writes
-__device__ __forceinline__ void sj_store_record(mot_track_point* __restrict__ at, bool vec_out, bool global, const EgoTf& m, const float4& q, int index) {
+// the bits mot_export_track_points_dev writes. THE record expression: the voxel kernels (scene_voxels_seq.hip) take their coordinates from it as well
+__device__ __forceinline__ float4 sj_record(bool global, const EgoTf& m, const float4& q, int index) {
   float4 o;
   if (global) {
     o.x = m.m[0] * q.x + m.m[1] * q.y + m.m[2] * q.z + m.m[3];
@@ -94,9 +94,16 @@ __device__ __forceinline__ void sj_store_record(mot_track_point* __restrict__ at
     o.z = m.m[8] * q.x + m.m[9] * q.y + m.m[10] * q.z + m.m[11];
   } else { o.x = q.x; o.y = q.y; o.z = q.z; }
   o.w = __int_as_float(index);
-  if (vec_out) *reinterpret_cast<float4*>(at) = o;
-  else { float* p = reinterpret_cast<float*>(at); p[0] = o.x; p[1] = o.y; p[2] = o.z; p[3] = o.w; }
+  return o;
 }
+// where the scatter body's records go: the caller's block, one 16-byte store where it is aligned
+struct SjRecordStore {
+  mot_track_point* __restrict__ out; bool vec_out;
+  __device__ __forceinline__ void operator()(long dst, const float4& o) const {
+    if (vec_out) *reinterpret_cast<float4*>(out + dst) = o;
+    else { float* p = reinterpret_cast<float*>(out + dst); p[0] = o.x; p[1] = o.y; p[2] = o.z; p[3] = o.w; }
+  }
+};
 
 // THE classify body: chunk blockIdx.x of frame `slot` judged against the grid of slot `of`. What the two kernels decide for themselves and hand in:
 //   live (scene_judge_classify_kernel)          of = slot = b: the slot's own header, validity and cells; kind = SceneKindLive; the caller's class block at kb
@@ -144,9 +151,10 @@ __device__ __forceinline__ void sj_classify_body(const SceneGridBuffers& g, cons
 //   recorded (scene_judge_seq_scatter_kernel)  kDrive = true: the chain starts at bases[c] + row[5 + c] (bases: frame k's five drive-wide places); out = the drive's ONE
 //                                              block, lim = its capacity, dst < 0 || dst >= lim is skipped
 // tf: the frame's matrix (entry kb / k of what the launch was given) when the records are global, else null. Only the points of selected classes are loaded.
-template <bool kDrive>
+// sink(dst, record): what is done with the record of place dst < lim — the two scatter kernels store it (SjRecordStore), the voxel key kernel keeps its cell as well.
+template <bool kDrive, class Sink>
 __device__ __forceinline__ void sj_scatter_body(const SceneSplatInput& in, const SceneJudgeBuffers& j, int slot, const int* __restrict__ bases, const EgoTf* __restrict__ tf,
-                                                mot_track_point* __restrict__ out, long lim, int (*s_cnt)[MOT_SCENE_CLASSES], int (*s_at)[MOT_SCENE_CLASSES]) {
+                                                long lim, int (*s_cnt)[MOT_SCENE_CLASSES], int (*s_at)[MOT_SCENE_CLASSES], const Sink& sink) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int n = scene_count(in, slot);
   const long base = (long)blockIdx.x * kSceneChunk;
@@ -154,7 +162,6 @@ __device__ __forceinline__ void sj_scatter_body(const SceneSplatInput& in, const
   const uint8_t* __restrict__ cls_in = j.cls + (long)slot * in.cap;
   const float4* __restrict__ cloud = in.elevated + (long)slot * in.cap;
   const int* __restrict__ row = j.rows + ((long)slot * j.max_chunks + blockIdx.x) * kSceneJudgeRow;
-  const bool vec_out = (reinterpret_cast<uintptr_t>(out) & 15) == 0;
   int cls[kSceneItems];
   float4 q[kSceneItems];
 #pragma unroll
@@ -182,7 +189,12 @@ __device__ __forceinline__ void sj_scatter_body(const SceneSplatInput& in, const
     if (cls[k] >= MOT_SCENE_CLASSES || !((j.class_mask >> cls[k]) & 1)) continue;
     const long dst = (long)s_at[k * kSjWaves + wave][cls[k]] + rank[k];
     if ((kDrive && dst < 0) || dst >= lim) continue;   // never a store outside the slot's records / the caller's block (live: dst < n while the rows are this call's)
-    sj_store_record(out + dst, vec_out, tf != nullptr, m, q[k], (int)i);
+    sink(dst, sj_record(tf != nullptr, m, q[k], (int)i));
   }
+}
+template <bool kDrive>
+__device__ __forceinline__ void sj_scatter_body(const SceneSplatInput& in, const SceneJudgeBuffers& j, int slot, const int* __restrict__ bases, const EgoTf* __restrict__ tf,
+                                                mot_track_point* __restrict__ out, long lim, int (*s_cnt)[MOT_SCENE_CLASSES], int (*s_at)[MOT_SCENE_CLASSES]) {
+  sj_scatter_body<kDrive>(in, j, slot, bases, tf, lim, s_cnt, s_at, SjRecordStore{out, (reinterpret_cast<uintptr_t>(out) & 15) == 0});
 }
 #endif

@@ -17,6 +17,11 @@
 // body for both builds, written over wave_scan_incl_i32, and tests/primitive_cases.py holds it thread by thread at 128, 256, 512 and 1024 threads.
 #ifndef MOT_WAVE_H_
 #define MOT_WAVE_H_
+#ifndef MOT_HIPEMU
+#include <hip/hip_runtime.h>
+#endif
+
+#include "mot_wave_sync.h"   // MOT_WAVE_SYNC
 
 #ifndef MOT_HIPEMU
 // v' = op(v, v permuted by ctrl); lanes whose source is invalid keep v (bound_ctrl off, old = v)

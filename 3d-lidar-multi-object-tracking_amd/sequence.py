@@ -117,18 +117,9 @@ def _torch_upload(host: np.ndarray):
     return d.data_ptr(), d
 
 
-def play_static_map(ctx, frames, dt_us: float = 1.0e5, t0: float = 1.0e9, classes=("known",), frame: str = "global", min_static_hits: int = 1, trail=(1, 2),
-                    upload=None) -> list:
-    """A recorded drive into its static map on the SEQUENCE path: the drive is cut into pieces of at most `ctx.max_batch` frames, each piece goes through
-    `Context.sequence_products_dev(scene=True)` (one asynchronous call: stateless stages batched, tracker steps chained, every frame into stream 0's scene grid) and is
-    judged right behind its call with `Context.get_sequence_scene_points`. Needs `set_track_links(True)` and `set_scene_grid(...)` on the context.
-
-    EACH PIECE IS JUDGED AGAINST THE GRID SO FAR: the frames of piece p see every frame of pieces 0..p (their own piece with hindsight), not the pieces behind them.
-    A drive that fits one call (`max_batch >= len(frames)`) is judged against the whole drive.
-
-    frames: a sequence of (cloud, v, yaw), clouds (n, 4) float32. upload: host array -> (device pointer, an object that keeps the block alive); default: through torch.
-    Returns one `get_sequence_scene_points` dict per piece (totals, segments, xyz, index, classes) with `first_frame` added; with the defaults `xyz` of the pieces,
-    concatenated, is the drive's static map in the global frame — movers and their trails cut out."""
+def _play_pieces(ctx, frames, dt_us, t0, upload, behind) -> list:
+    """the loop play_static_map and play_static_voxel_map share: the drive in pieces of at most `ctx.max_batch` frames, each through sequence_products_dev(scene=True);
+    behind(n_frames) reads the piece right behind its call (it synchronises: the upload may go) and returns the piece's dict, which gets `first_frame`"""
     upload = upload or _torch_upload
     frames = list(frames)
     stride = ctx.max_points
@@ -145,8 +136,39 @@ def play_static_map(ctx, frames, dt_us: float = 1.0e5, t0: float = 1.0e9, classe
             n.append(len(a))
         ptr, keep = upload(host)
         ctx.sequence_products_dev(ptr, stride * 4, n, [t0 + (k0 + k) * dt_us for k in range(len(piece))], [p[1] for p in piece], [p[2] for p in piece], scene=True)
-        r = ctx.get_sequence_scene_points(len(piece), min_static_hits=min_static_hits, trail=trail, classes=classes, frame=frame)   # (synchronises: `keep` may go)
+        r = behind(len(piece))
         r["first_frame"] = k0
         out.append(r)
         del keep
     return out
+
+
+def play_static_map(ctx, frames, dt_us: float = 1.0e5, t0: float = 1.0e9, classes=("known",), frame: str = "global", min_static_hits: int = 1, trail=(1, 2),
+                    upload=None) -> list:
+    """A recorded drive into its static map on the SEQUENCE path: the drive is cut into pieces of at most `ctx.max_batch` frames, each piece goes through
+    `Context.sequence_products_dev(scene=True)` (one asynchronous call: stateless stages batched, tracker steps chained, every frame into stream 0's scene grid) and is
+    judged right behind its call with `Context.get_sequence_scene_points`. Needs `set_track_links(True)` and `set_scene_grid(...)` on the context.
+
+    EACH PIECE IS JUDGED AGAINST THE GRID SO FAR: the frames of piece p see every frame of pieces 0..p (their own piece with hindsight), not the pieces behind them.
+    A drive that fits one call (`max_batch >= len(frames)`) is judged against the whole drive.
+
+    frames: a sequence of (cloud, v, yaw), clouds (n, 4) float32. upload: host array -> (device pointer, an object that keeps the block alive); default: through torch.
+    Returns one `get_sequence_scene_points` dict per piece (totals, segments, xyz, index, classes) with `first_frame` added; with the defaults `xyz` of the pieces,
+    concatenated, is the drive's static map in the global frame — movers and their trails cut out."""
+    return _play_pieces(ctx, frames, dt_us, t0, upload,
+                        lambda n: ctx.get_sequence_scene_points(n, min_static_hits=min_static_hits, trail=trail, classes=classes, frame=frame))
+
+
+def play_static_voxel_map(ctx, frames, leaf, min_points: int = 1, dt_us: float = 1.0e5, t0: float = 1.0e9, classes=("known",), min_static_hits: int = 1, trail=(1, 2),
+                          upload=None) -> list:
+    """`play_static_map`'s loop with `Context.get_sequence_scene_voxels` behind each piece: the piece's selected records (global frame) thinned on the device to one
+    centroid and one count per occupied voxel of edge `leaf` (a float, or three) of a lattice anchored at the global origin; voxels with fewer than `min_points`
+    records are dropped. Needs `set_track_links(True)` and `set_scene_grid(...)` on the context.
+
+    EACH PIECE IS JUDGED AGAINST THE GRID SO FAR, as in `play_static_map`, AND THINNED ON ITS OWN: a voxel that two pieces see appears in both results (the lattice
+    is the same from piece to piece, so the cells can be matched by the caller). Merging the voxel maps of several pieces is out of scope here; a drive that fits one
+    call (`max_batch >= len(frames)`) gives one map.
+
+    Returns one `get_sequence_scene_voxels` dict per piece (xyz, count, header, totals) with `first_frame` added."""
+    return _play_pieces(ctx, frames, dt_us, t0, upload,
+                        lambda n: ctx.get_sequence_scene_voxels(n, leaf, min_points=min_points, min_static_hits=min_static_hits, trail=trail, classes=classes))

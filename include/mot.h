@@ -874,6 +874,62 @@ int mot_get_sequence_scene_points(mot_ctx* ctx, int frames, const mot_scene_judg
         mot_scene_segment* segments /* [frames][5] */, mot_scene_segment totals[5],
         uint8_t* classes /* may be NULL */, long class_stride);
 
+/* ---------------------------------------------------------------- voxel-thinned static map of a recorded drive (additions within ABI v6)
+ * The run mot_export_sequence_scene_points_dev gives holds a standing wall once per frame that saw it. These calls reduce the same records, on the device, to ONE
+ * RECORD PER OCCUPIED VOXEL: the centroid of the cell's records and their number. Asynchronous, behind the sequence call on the context stream; the call READS the
+ * grid and consumes no step. Nothing is launched, written or allocated unless these calls are used. Every rule below is fp32 exactly as written, no contraction.
+ *
+ * RECORDS. R[0..m) are the records mot_export_sequence_scene_points_dev(frames, params, class_mask, MOT_FRAME_GLOBAL, ...) would write with unlimited capacity, in
+ * that call's order (class ascending, then frame ascending, then input order): its verdicts, its global coordinates and its order, bit for bit (the same device
+ * functions). Records at positions >= record_capacity take no part and are counted in n_beyond.
+ * CELL OF A RECORD. inv_a = 1.0f / leaf_a, computed once on the host; t_a = coord_a * inv_a. The record takes part iff all three coordinates are finite and
+ * -2^20 <= t_x, t_y < 2^20 and -2^11 <= t_z < 2^11, compared as floats; then i_a = (int)floorf(t_a). Every other record below the capacity counts in n_outside. The
+ * lattice is anchored at the global origin: a voxel is the same piece of the world from call to call and from drive to drive.
+ * VOXELS. The distinct cells in ascending (i_z, i_y, i_x); count = the cell's records. A voxel with count < min_points is dropped and counted in n_sparse; the kept
+ * voxels are packed back to back, the first voxel_capacity of them are stored and nothing is written beyond.
+ * CENTROID. A voxel's records in record order r_0 .. r_{n-1}; per axis 64 fp64 accumulators acc[l] = ((r_l + r_{l+64}) + r_{l+128}) + ..., each starting from its
+ * first record; S = ((acc[0] + acc[1]) + acc[2]) + ... + acc[min(n, 64) - 1], added in ascending l; the centroid is (float)(S / (double)n). For n <= 64 this is the
+ * plain left-to-right sum. (The order is fixed so that a wave can sum a long run and the bytes do not depend on how the work was cut.)
+ * HEADER. n_records = n_beyond + n_outside + sum of count over the kept voxels + sum of count over the sparse ones. d_totals (may be NULL): the five {first, count}
+ * of the judge call for this mask (first = -1 outside the mask).
+ * VALIDITY: exactly that of mot_export_sequence_scene_points_dev — only behind the latest MOT_SEQ_SCENE sequence call, frames within that call's, links and grid on,
+ * nothing having taken a slot or changed a grid since.
+ * REFUSALS, each before anything is launched, the caller's blocks untouched: MOT_E_STATE as above; MOT_E_ARG for the judge call's argument errors, null voxel or
+ * d_header, a leaf that is not finite or outside [1e-2, 1e3], min_points outside [1, 2^30], record_capacity outside [0, 2^31 - 1], a negative voxel_capacity, null
+ * d_voxels with voxel_capacity > 0, d_voxels not 16-byte aligned or another block not 4-byte aligned; MOT_E_HIP when the scratch cannot be had — all of its blocks
+ * or none, the next call tries again.
+ * mot_get_sequence_scene_voxels does the same to the host (synchronises): the header, *n_voxels (the true count) and the totals are always delivered;
+ * MOT_E_CAPACITY with nothing copied when voxels is given and voxel_capacity < *n_voxels. The getter's n_stored is what it copied to the caller: n_voxels, or 0
+ * when voxels is NULL or the call answers MOT_E_CAPACITY.
+ *
+ * Scratch: that of mot_export_sequence_scene_points_dev and ONE block grown on demand to record_capacity — 40 bytes per record of capacity (two 8-byte keys and two
+ * 4-byte payloads, which ping-pong in the sort, and the 16-byte record staged at its place) and 1036 bytes per 2048 records for the sort's tables. The launches are
+ * sized by record_capacity as well; the kernels read the true m on the device and leave early. Released with the grid (mot_set_scene_grid(NULL) or another
+ * geometry) and by mot_destroy. The host getter adds, as mot_get_sequence_scene_points does, a 96-byte table block at ITS first call (released with the rest) and
+ * takes a device block of n_voxels x 16 bytes for the duration of a call that copies voxels (allocated and freed inside the call).
+ * Kernels (csrc/scene_voxels_seq.hip, csrc/mot_sort.h): the judge's three count launches; a key kernel on the scatter kernel's geometry; a device-wide stable LSD
+ * radix sort of the 64-bit keys, key = (i_z + 2^11) << 42 | (i_y + 2^20) << 21 | (i_x + 2^20), all ones outside the lattice (7 passes of 8 bits, three launches a
+ * pass); run heads, a scan, the run table; kept runs, a scan, the header; one wave per run writes the voxels. 32 launches whatever `frames` and the data are. No
+ * global atomics, no workgroup waits on another, the output does not depend on scheduling. Cost: profiles/scene_voxels_sequence.md
+ * (tools/time_scene_voxels_sequence.py). */
+typedef struct mot_scene_voxel_header {   /* 32 bytes */
+  int32_t n_records;   /* selected records of the drive: the sum of the mask's class totals (TRUE) */
+  int32_t n_beyond;    /* records at positions >= record_capacity: took no part */
+  int32_t n_outside;   /* records below the capacity with a non-finite coordinate or a cell outside the lattice */
+  int32_t n_voxels;    /* kept voxels (TRUE, whatever voxel_capacity is) */
+  int32_t n_sparse;    /* occupied voxels dropped for fewer than min_points records */
+  int32_t n_stored;    /* min(n_voxels, voxel_capacity) */
+  int32_t reserved[2]; /* 0 */
+} mot_scene_voxel_header;
+int mot_export_sequence_scene_voxels_dev(mot_ctx* ctx, int frames, const mot_scene_judge_params* params, int class_mask,
+        const mot_voxel_params* voxel, long record_capacity,
+        mot_model_voxel* d_voxels, long voxel_capacity,
+        mot_scene_voxel_header* d_header, mot_scene_segment* d_totals /* [5], may be NULL */);
+int mot_get_sequence_scene_voxels(mot_ctx* ctx, int frames, const mot_scene_judge_params* params, int class_mask,
+        const mot_voxel_params* voxel, long record_capacity,
+        mot_model_voxel* voxels /* may be NULL */, long voxel_capacity, long* n_voxels,
+        mot_scene_voxel_header* header, mot_scene_segment totals[5] /* may be NULL */);
+
 /* on != 0: the fused entry points send their launch sequence (13 kernels with the tracker) as ONE hipGraph launch, captured once per launch geometry
  * (batch, chunks of the largest frame, tracker on / off, outputs); what changes per call without changing the geometry travels in the
  * device-resident argument block. For contexts somebody waits on frame by frame (one or a few streams): the host's part of a frame
