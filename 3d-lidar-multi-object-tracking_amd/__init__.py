@@ -107,6 +107,10 @@ assert SCENE_SEGMENT_DTYPE.itemsize == 8
 # struct mot_scene_voxel_header of mot_export_sequence_scene_voxels_dev / mot_get_sequence_scene_voxels (voxel-thinned static map of a recorded drive)
 SCENE_VOXEL_HEADER_DTYPE = np.dtype([("n_records", "i4"), ("n_beyond", "i4"), ("n_outside", "i4"), ("n_voxels", "i4"), ("n_sparse", "i4"), ("n_stored", "i4"), ("reserved", "i4", 2)])
 assert SCENE_VOXEL_HEADER_DTYPE.itemsize == 32
+# struct mot_voxel_merge_header / mot_voxel_map_src of mot_merge_voxel_maps_dev / mot_merge_voxel_maps (voxel maps merged into one)
+VOXEL_MERGE_MAX_MAPS = 16
+VOXEL_MERGE_HEADER_DTYPE = np.dtype([("n_inputs", "i4"), ("n_outside", "i4"), ("n_voxels", "i4"), ("n_sparse", "i4"), ("n_stored", "i4"), ("n_saturated", "i4"), ("reserved", "i4", 2)])
+assert VOXEL_MERGE_HEADER_DTYPE.itemsize == 32
 
 
 class MotSceneJudgeParams(C.Structure):
@@ -139,6 +143,14 @@ def voxel_params(leaf, min_points: int = 1) -> MotVoxelParams:
     return MotVoxelParams(float(lx), float(ly), float(lz), int(min_points))
 
 
+class MotVoxelMapSrc(C.Structure):
+    """struct mot_voxel_map_src"""
+    _fields_ = [("voxels", C.c_void_p), ("count", C.c_void_p), ("capacity", C.c_long)]
+
+
+assert C.sizeof(MotVoxelMapSrc) == 24
+
+
 class MotAccumView(C.Structure):
     """mirror of struct mot_accum_view (include/mot.h)"""
     _fields_ = [("d_rows", C.c_void_p), ("d_points", C.c_void_p), ("d_obs", C.c_void_p), ("tracks_per_slot", C.c_int32), ("points_per_track", C.c_int32),
@@ -167,7 +179,7 @@ EXPORTS = (
     "mot_export_track_models_dev", "mot_get_track_models", "mot_export_track_model_voxels_dev", "mot_get_track_model_voxels",
     "mot_set_scene_grid", "mot_accumulate_scene", "mot_export_scene_grid_dev", "mot_get_scene_grid", "mot_sequence_products_dev",
     "mot_export_scene_points_dev", "mot_get_scene_points", "mot_export_sequence_scene_points_dev", "mot_get_sequence_scene_points",
-    "mot_export_sequence_scene_voxels_dev", "mot_get_sequence_scene_voxels",
+    "mot_export_sequence_scene_voxels_dev", "mot_get_sequence_scene_voxels", "mot_merge_voxel_maps_dev", "mot_merge_voxel_maps",
     "mot_gather_unique_id", "mot_gather_create", "mot_gather_contribute", "mot_gather_result", "mot_gather_synchronize", "mot_gather_destroy", "mot_gather_last_error",
 )
 ABI_VERSION = 6
@@ -547,6 +559,34 @@ class Context:
         self._ck(self.lib.mot_get_sequence_scene_voxels(self._h, F, C.byref(p), mask, C.byref(v), cap, _vp(vox), C.c_long(bound), C.byref(n), _vp(hdr), _vp(tot)))
         vox = vox[: n.value]
         return dict(xyz=vox["xyz"].copy(), count=vox["count"].copy(), header=hdr[0].copy(), totals=tot)
+
+    def merge_voxel_maps_dev(self, maps, leaf, d_out_ptr: int, out_capacity: int, d_header_ptr: int, min_points: int = 1):
+        """up to 16 voxel maps of the global lattice merged into one on the device (mot_merge_voxel_maps_dev). maps: (d_voxels_ptr, d_count_ptr or 0, capacity)
+        each — device blocks of MODEL_VOXEL_DTYPE as every voxel export writes them, the count an int32 ON THE DEVICE (e.g. the address of n_stored in the header
+        an earlier export (header pointer + 20) or an earlier merge (+ 16) wrote; 0: the capacity is the count). -> caller's device blocks: the voxels of the distinct cells of edge
+        `leaf` in ascending (i_z, i_y, i_x), counts added, centroids weighted by count, cells whose summed count is below min_points dropped; the 32-byte header
+        (VOXEL_MERGE_HEADER_DTYPE). Reads nothing but its arguments; asynchronous"""
+        arr = (MotVoxelMapSrc * max(len(maps), 1))(*[MotVoxelMapSrc(int(p) or None, int(n) or None, int(cap)) for p, n, cap in maps])
+        v = voxel_params(leaf, min_points)
+        self._ck(self.lib.mot_merge_voxel_maps_dev(self._h, arr, len(maps), C.byref(v), C.c_void_p(d_out_ptr or None), C.c_long(out_capacity), C.c_void_p(d_header_ptr or None)))
+
+    def merge_voxel_maps(self, maps, leaf, min_points: int = 1) -> dict:
+        """the same from host arrays (mot_merge_voxel_maps; synchronises). maps: dicts with xyz [n, 3] and count [n] (what the voxel getters return), or
+        MODEL_VOXEL_DTYPE arrays. -> xyz [n, 3], count [n], header (a VOXEL_MERGE_HEADER_DTYPE record)"""
+        blocks = []
+        for mp in maps:
+            if isinstance(mp, dict):
+                b = np.zeros(len(mp["count"]), MODEL_VOXEL_DTYPE); b["xyz"] = np.asarray(mp["xyz"], np.float32).reshape(-1, 3); b["count"] = mp["count"]
+            else:
+                b = np.ascontiguousarray(mp, MODEL_VOXEL_DTYPE)
+            blocks.append(b)
+        arr = (MotVoxelMapSrc * max(len(blocks), 1))(*[MotVoxelMapSrc(b.ctypes.data if len(b) else None, None, len(b)) for b in blocks])
+        v = voxel_params(leaf, min_points)
+        bound = sum(len(b) for b in blocks)   # a voxel holds an input or more
+        out = np.zeros(max(bound, 1), MODEL_VOXEL_DTYPE); hdr = np.zeros(1, VOXEL_MERGE_HEADER_DTYPE); n = C.c_long(0)
+        self._ck(self.lib.mot_merge_voxel_maps(self._h, arr, len(blocks), C.byref(v), _vp(out), C.c_long(bound), C.byref(n), _vp(hdr)))
+        out = out[: n.value]
+        return dict(xyz=out["xyz"].copy(), count=out["count"].copy(), header=hdr[0].copy())
 
     def get_scene_grid(self, slot: int = 0, cells: bool = True) -> dict:
         """one slot's grid on the host (mot_get_scene_grid): header (a SCENE_HEADER_DTYPE record) and cells [size, size] indexed (v, u) (SCENE_CELL_DTYPE;

@@ -1,5 +1,5 @@
 // mot_api_scene.hip — host side of the C-ABI (include/mot.h), the rolling static-scene grid: the setter and what it owns, the per-slot step counters, the state
-// checks of mot_accumulate_scene, the two readers, the frame's points and a recorded drive's points judged against the grid, the drive's static map thinned to voxels. Kernels: scene_grid.hip, scene_grid_seq.hip, scene_judge.hip, scene_judge_seq.hip, scene_voxels_seq.hip. Context and helpers: mot_host.h.
+// checks of mot_accumulate_scene, the two readers, the frame's points and a recorded drive's points judged against the grid, the drive's static map thinned to voxels, voxel maps merged into one. Kernels: scene_grid.hip, scene_grid_seq.hip, scene_judge.hip, scene_judge_seq.hip, scene_voxels_seq.hip, voxel_merge.hip. Context and helpers: mot_host.h.
 #include "mot_host.h"
 
 // The setter owns the feature's memory: cells, headers, previous origins, the argument block and its ring of page-locked staging blocks are allocated together and
@@ -536,5 +536,155 @@ extern "C" int mot_get_sequence_scene_voxels(mot_ctx* c, int frames, const mot_s
     MOT_TRY(release(c, &d_vox));
     MOT_HIP_AS(c, "mot_get_sequence_scene_voxels: the voxels", e != hipSuccess ? e : e2);
   }
+  return MOT_OK;
+}
+
+// ---------------------------------------------------------------------------------------- voxel maps merged into one (voxel_merge.hip)
+// The calls read nothing but their arguments: no state check, no slot, no step counter, no grid. ONE block of the feature's own, laid out by
+// mot_voxel_merge_scratch_bytes for the largest sum of capacities asked so far and released by mot_destroy alone (it does not go with the grid: the calls work
+// without one). Growing it drains the stream first (nothing may still read the old block).
+static bool blocks_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+  return a && b && a_bytes && b_bytes && pa < pb + b_bytes && pb < pa + a_bytes;
+}
+// what the device call and the host call refuse alike; *total: the sum of the capacities
+static int check_merge_args(mot_ctx* c, const char* who, const mot_voxel_map_src* maps, int n_maps, const mot_voxel_params* voxel, const void* out, long out_capacity, long* total) {
+  if (!maps) return fail(c, MOT_E_ARG, who, ": null maps");
+  if (n_maps < 1 || n_maps > MOT_VOXEL_MERGE_MAX_MAPS) return fail(c, MOT_E_ARG, who, ": n_maps must lie in [1, 16]");
+  MOT_TRY(check_voxel_args(c, who, voxel, 0, out_capacity));
+  long sum = 0;
+  for (int k = 0; k < n_maps; k++) {
+    const long cap = maps[k].capacity;
+    if (cap < 0 || cap > 2147483647L) return fail(c, MOT_E_ARG, who, ": a map's capacity must lie in [0, 2^31 - 1]");
+    sum += cap;
+    if (sum > 2147483647L) return fail(c, MOT_E_ARG, who, ": the capacities add up to more than 2^31 - 1 (positions are int32)");
+    if (!maps[k].voxels && cap > 0) return fail(c, MOT_E_ARG, who, ": null voxels with a capacity");
+  }
+  if (!out && out_capacity > 0) return fail(c, MOT_E_ARG, who, ": null output block with a capacity");
+  *total = sum;
+  return MOT_OK;
+}
+static int ensure_merge_scratch(mot_ctx* c, long total) {
+  if (c->d_vm_scratch && c->vm_cap >= total) return MOT_OK;
+  if (c->d_vm_scratch) {
+    MOT_HIP(c, hipStreamSynchronize(c->stream));
+    MOT_TRY(release(c, &c->d_vm_scratch));
+  }
+  c->vm_cap = -1;
+  MOT_TRY(dev_alloc(c, &c->d_vm_scratch, mot_voxel_merge_scratch_bytes(total)));
+  c->vm_cap = total;
+  return MOT_OK;
+}
+static SceneVoxelBuffers merge_buffers(const mot_ctx* c, long total) {
+  SceneVoxelBuffers v;
+  (void)mot_voxel_merge_scratch_bytes(c->vm_cap, &v, c->d_vm_scratch);
+  v.cap = (int)total;
+  v.tiles = (int)((total + 2047) / 2048); if (v.tiles < 1) v.tiles = 1;
+  return v;
+}
+static SceneVoxelArgs merge_args(const mot_voxel_params* vp) { return {1.0f / vp->leaf_x, 1.0f / vp->leaf_y, 1.0f / vp->leaf_z, vp->min_points}; }
+
+extern "C" int mot_merge_voxel_maps_dev(mot_ctx* c, const mot_voxel_map_src* maps, int n_maps, const mot_voxel_params* voxel, mot_model_voxel* d_out, long out_capacity,
+                                        mot_voxel_merge_header* d_header) {
+  if (!c) return MOT_E_ARG;
+  MOT_GUARD(c);
+  const char* who = "mot_merge_voxel_maps_dev";
+  long total = 0;
+  MOT_TRY(check_merge_args(c, who, maps, n_maps, voxel, d_out, out_capacity, &total));
+  if (!d_header) return fail(c, MOT_E_ARG, who, ": null header");
+  if (((size_t)d_out & 15) || ((size_t)d_header & 3)) return fail(c, MOT_E_ARG, who, ": the output block off 16 bytes or the header off 4 bytes");
+  const size_t out_bytes = (size_t)(out_capacity > 2147483647L ? 2147483647L : out_capacity) * sizeof(mot_model_voxel);
+  VoxelMergeMaps m = {};
+  for (int k = 0; k < n_maps; k++) {
+    const size_t in_bytes = (size_t)maps[k].capacity * sizeof(mot_model_voxel);
+    if (((size_t)maps[k].voxels & 15) || ((size_t)maps[k].count & 3)) return fail(c, MOT_E_ARG, who, ": an input block off 16 bytes or a count off 4 bytes");
+    if (blocks_overlap(d_out, out_bytes, maps[k].voxels, in_bytes) || blocks_overlap(d_out, out_bytes, maps[k].count, 4) ||
+        blocks_overlap(d_header, sizeof(mot_voxel_merge_header), maps[k].voxels, in_bytes) || blocks_overlap(d_header, sizeof(mot_voxel_merge_header), maps[k].count, 4))
+      return fail(c, MOT_E_ARG, who, ": the output block or the header overlaps an input block or a count");
+    m.vox[k] = maps[k].voxels; m.count[k] = maps[k].count; m.cap[k] = (int)maps[k].capacity;
+  }
+  m.n_maps = n_maps; m.short_max = c->vm_short_max;
+  MOT_TRY(ensure_merge_scratch(c, total));
+  const SceneVoxelBuffers v = merge_buffers(c, total);
+  mot_launch_voxel_merge_count(m, v, merge_args(voxel), out_capacity, d_header, c->stream);
+  mot_launch_voxel_merge_write(m, v, voxel->min_points, d_out, out_capacity, c->stream);
+  MOT_HIP(c, hipGetLastError());
+  return MOT_OK;
+}
+
+// the host call's device blocks live for the duration of the call: whatever way it ends, the stream is drained and they go back
+struct MergeCallBlocks {
+  mot_ctx* c; char* stage = nullptr; mot_model_voxel* vox = nullptr;
+  explicit MergeCallBlocks(mot_ctx* ctx) : c(ctx) {}
+  ~MergeCallBlocks() {
+    if (!stage && !vox) return;
+    const std::string why = c->err;
+    (void)hipStreamSynchronize(c->stream); (void)release(c, &stage); (void)release(c, &vox);
+    c->err = why;
+  }
+};
+extern "C" int mot_merge_voxel_maps(mot_ctx* c, const mot_voxel_map_src* maps, int n_maps, const mot_voxel_params* voxel, mot_model_voxel* out, long out_capacity, long* n_voxels,
+                                    mot_voxel_merge_header* header) {
+  if (!c) return MOT_E_ARG;
+  MOT_GUARD(c);
+  const char* who = "mot_merge_voxel_maps";
+  long total = 0;
+  MOT_TRY(check_merge_args(c, who, maps, n_maps, voxel, out, out_capacity, &total));
+  if (!n_voxels || !header) return fail(c, MOT_E_ARG, who, ": null count or header");
+  long cnt[MOT_VOXEL_MERGE_MAX_MAPS];
+  total = 0;
+  for (int k = 0; k < n_maps; k++) {   // the counts are the host's: clamped here, and only those voxels travel
+    const long v = maps[k].count ? (long)*maps[k].count : maps[k].capacity;
+    cnt[k] = v < 0 ? 0 : (v > maps[k].capacity ? maps[k].capacity : v);
+    total += cnt[k];
+  }
+  // the inputs back to back, then the header: one block; the scratch behind it — all of the call's blocks or none
+  const bool had_scratch = c->d_vm_scratch && c->vm_cap >= total;
+  MergeCallBlocks blk(c);
+  const size_t in_bytes = (size_t)(total < 1 ? 1 : total) * sizeof(mot_model_voxel);
+  MOT_TRY(dev_alloc(c, &blk.stage, in_bytes + sizeof(mot_voxel_merge_header)));
+  int rc = ensure_merge_scratch(c, total);
+  if (rc) return rc;
+  mot_voxel_merge_header* d_hdr = reinterpret_cast<mot_voxel_merge_header*>(blk.stage + in_bytes);
+  VoxelMergeMaps m = {};
+  long at = 0;
+  for (int k = 0; k < n_maps; k++) {
+    m.vox[k] = reinterpret_cast<const mot_model_voxel*>(blk.stage) + at; m.count[k] = nullptr; m.cap[k] = (int)cnt[k];
+    if (cnt[k] > 0) MOT_HIP(c, hipMemcpyAsync(blk.stage + (size_t)at * sizeof(mot_model_voxel), maps[k].voxels, (size_t)cnt[k] * sizeof(mot_model_voxel), hipMemcpyHostToDevice, c->stream));
+    at += cnt[k];
+  }
+  m.n_maps = n_maps; m.short_max = c->vm_short_max;
+  const SceneVoxelBuffers v = merge_buffers(c, total);
+  // the counts first (they are always delivered); what fits the caller's buffer is decided here, and the voxels are written into a block of their own size
+  mot_launch_voxel_merge_count(m, v, merge_args(voxel), out_capacity, d_hdr, c->stream);
+  MOT_HIP(c, hipGetLastError());
+  char* pin;
+  MOT_TRY(pinned_scratch(c, sizeof(mot_voxel_merge_header), &pin));
+  MOT_HIP(c, hipMemcpyAsync(pin, d_hdr, sizeof(mot_voxel_merge_header), hipMemcpyDeviceToHost, c->stream));
+  MOT_HIP(c, hipStreamSynchronize(c->stream));
+  const mot_voxel_merge_header* h = reinterpret_cast<const mot_voxel_merge_header*>(pin);
+  const long nv = h->n_voxels;
+  if (nv < 0 || nv > total || h->n_inputs != total) return fail(c, MOT_E_STATE, who, ": inconsistent counts");
+  memcpy(header, h, sizeof(mot_voxel_merge_header));
+  header->n_stored = (out && nv <= out_capacity) ? (int32_t)nv : 0;   // what this call copies to the caller: all of the voxels or none
+  *n_voxels = nv;
+  if (out && nv > out_capacity) return fail(c, MOT_E_CAPACITY, "more voxels than the caller's buffer holds");
+  if (out && nv > 0) {
+    rc = dev_alloc(c, &blk.vox, (size_t)nv * sizeof(mot_model_voxel));
+    if (rc) {
+      if (!had_scratch) { const std::string why = c->err; (void)release(c, &c->d_vm_scratch); c->vm_cap = -1; c->err = why; }
+      return rc;
+    }
+    mot_launch_voxel_merge_write(m, v, voxel->min_points, blk.vox, nv, c->stream);
+    MOT_HIP(c, hipGetLastError());
+    MOT_HIP(c, hipMemcpyAsync(out, blk.vox, (size_t)nv * sizeof(mot_model_voxel), hipMemcpyDeviceToHost, c->stream));
+    MOT_HIP(c, hipStreamSynchronize(c->stream));
+  }
+  return MOT_OK;
+}
+
+extern "C" int mot_debug_voxel_merge_cut(mot_ctx* c, int short_max) {
+  if (!c || short_max < 0 || short_max > 64) return MOT_E_ARG;
+  c->vm_short_max = short_max;
   return MOT_OK;
 }

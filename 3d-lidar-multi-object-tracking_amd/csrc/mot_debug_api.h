@@ -24,6 +24,9 @@ int mot_debug_skip_kernels(mot_ctx* ctx, int mask);
 int mot_debug_tf_matrix(double x, double y, double yaw, float* m12);
 /* the matrix of the way back: global -> sensor, what the MOT_FRAME_SENSOR exports apply to the track records (mot_sensor_pose's sensor_from_global) */
 int mot_debug_tf_matrix_inv(double x, double y, double yaw, float* m12);
+/* MEASUREMENT ONLY: the cut of the voxel merge's reduce kernel (csrc/voxel_merge.hip) — cells of at most short_max inputs are summed by one thread, longer ones by
+ * a wave. [0, 64], default 64; 0: every cell by a wave. The output bytes do not depend on it (tools/time_voxel_merge.py times both) */
+int mot_debug_voxel_merge_cut(mot_ctx* ctx, int short_max);
 #ifdef __cplusplus
 }
 #endif

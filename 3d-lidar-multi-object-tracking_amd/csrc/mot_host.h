@@ -303,6 +303,10 @@ struct mot_ctx {
   char* d_sv_scratch = nullptr;            // mot_scene_voxel_scratch_bytes(sv_cap, batch): keys, payloads, staged records, the sort's table, the plan, the judge's two tables
   long sv_cap = -1;                        // the record capacity the block was laid out for (grown on demand; -1: none)
   char* d_sv_stage = nullptr;              // the getter: the header and [5] totals before they go to the host (allocated at ITS first call)
+  // mot_merge_voxel_maps_dev / mot_merge_voxel_maps (voxel_merge.hip): ONE block of their own, allocated at the first call, kept until mot_destroy (no grid needed)
+  char* d_vm_scratch = nullptr;            // mot_voxel_merge_scratch_bytes(vm_cap): keys, payloads, the sort's table, the per-tile counts, the plan
+  long vm_cap = -1;                        // the sum of capacities the block was laid out for (grown on demand; -1: none)
+  int vm_short_max = 64;                   // runs of at most so many inputs are summed by one thread (mot_debug_voxel_merge_cut: measurement; the bytes do not depend on it)
   std::vector<EgoTf> link_tf;          // [batch] the matrix every slot's boxes took in its last fused call with the tracker, kept while links are on (host side)
   Vec2d* d_cp = nullptr;
   TrackItem* d_items = nullptr;

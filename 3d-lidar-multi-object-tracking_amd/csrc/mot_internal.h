@@ -555,7 +555,7 @@ struct SceneVoxelBuffers {
   float4* staged;              // [cap] the records at their record position
   int* table;                  // [256][tiles] the sort's digit table
   int* totals;                 // [256]
-  int* part;                   // [3][tiles] per tile: run heads, records outside the lattice, kept runs
+  int* part;                   // [3][tiles] per tile: run heads, records outside the lattice, kept runs (the voxel merge adds a fourth row: saturated runs)
   int* plan;                   // [kSceneVoxelPlan]
   const mot_scene_segment* tab;// [frames][5] segments, then [5] totals: what the count launches wrote
   int cap, tiles;              // tiles = ceil(cap / 2048), at least 1
@@ -581,6 +581,39 @@ inline size_t mot_scene_voxel_scratch_bytes(long cap, int batch, SceneVoxelBuffe
 void mot_launch_scene_voxels_seq_count(const SceneSplatInput& in, const SceneJudgeBuffers& j, const int* bases, int frames, int max_n, const EgoTf* tf, const SceneVoxelBuffers& v,
                                        const SceneVoxelArgs& a, long voxel_capacity, mot_scene_voxel_header* header, mot_scene_segment* totals, hipStream_t stream);
 void mot_launch_scene_voxels_seq_write(const SceneVoxelBuffers& v, mot_model_voxel* voxels, long voxel_capacity, hipStream_t stream);
+
+// Voxel maps merged into one (voxel_merge.hip, mot_merge_voxel_maps_dev): the maps' voxels, read in place, are keyed by the cell of their centroid (sv_key,
+// mot_voxel_runs.h), sorted (mot_sort.h), cut into runs and reduced to one record per kept cell. The scratch is a SceneVoxelBuffers without staged records and
+// without the judge's tables, sized by `cap` = the sum of the maps' capacities (at least 1 of room): see mot_voxel_merge_scratch_bytes.
+constexpr int kVoxelMergeMaps = 16;
+constexpr int kVmPrefix = 8;               // plan[kVmPrefix + k]: the inputs of the maps before k (k = 0 .. 16); the ints below are those of the drive voxel call
+constexpr int kVoxelMergePlan = 32;        // ints
+struct VoxelMergeMaps {
+  const mot_model_voxel* vox[kVoxelMergeMaps];   // device blocks, 16-byte aligned
+  const int* count[kVoxelMergeMaps];             // on the device; null: the capacity is the count
+  int cap[kVoxelMergeMaps];
+  int n_maps;
+  int short_max;                                 // runs of at most so many inputs are summed by one thread, the longer ones by a wave; [0, 64]: the bytes do not depend on it
+};
+inline size_t mot_voxel_merge_scratch_bytes(long cap, SceneVoxelBuffers* at = nullptr, char* base = nullptr) {
+  const size_t n = (size_t)((cap < 1 ? 1 : cap) + 3) & ~(size_t)3;   // (every block starts 16-byte aligned)
+  const size_t tiles = (n + 2047) / 2048;
+  size_t o = 0;
+  auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 15) & ~(size_t)15; return at; };
+  const size_t k0 = take(8 * n), k1 = take(8 * n), v0 = take(4 * n), v1 = take(4 * n);
+  const size_t tb = take(4 * 256 * tiles), tt = take(4 * 256), pt = take(4 * 4 * tiles), pl = take(4 * kVoxelMergePlan);
+  if (at && base) {
+    at->key[0] = reinterpret_cast<unsigned long long*>(base + k0); at->key[1] = reinterpret_cast<unsigned long long*>(base + k1); at->staged = nullptr;
+    at->val[0] = reinterpret_cast<unsigned*>(base + v0); at->val[1] = reinterpret_cast<unsigned*>(base + v1); at->table = reinterpret_cast<int*>(base + tb);
+    at->totals = reinterpret_cast<int*>(base + tt); at->part = reinterpret_cast<int*>(base + pt); at->plan = reinterpret_cast<int*>(base + pl);
+    at->tab = nullptr;
+  }
+  return o;
+}
+// count: keys, the sort, runs, the runs' summed counts, kept voxels and the header; write (behind count on the same stream, the same maps and buffers; nothing without
+// room for voxels): the kept voxels. part is [4][tiles] here: run heads, inputs outside the lattice, kept runs, saturated runs
+void mot_launch_voxel_merge_count(const VoxelMergeMaps& m, const SceneVoxelBuffers& v, const SceneVoxelArgs& a, long out_capacity, mot_voxel_merge_header* header, hipStream_t stream);
+void mot_launch_voxel_merge_write(const VoxelMergeMaps& m, const SceneVoxelBuffers& v, int min_points, mot_model_voxel* out, long out_capacity, hipStream_t stream);
 
 #include "mot_wave_sync.h"   // MOT_WAVE_SYNC (shared with mot_wave.h)
 

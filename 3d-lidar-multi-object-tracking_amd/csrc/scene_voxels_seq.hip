@@ -26,25 +26,11 @@
 // capacity beyond 2^31 - 1).
 // Resources (tools/kernel_resources.py): profiles/scene_voxels_sequence.md.
 #include "mot_scene_judge.h"
-#include "mot_sort.h"
+#include "mot_voxel_runs.h"   // sv_key (THE cell rule), the plan's ints, sv_heads_body: shared with voxel_merge.hip
 
 static_assert(sizeof(mot_scene_voxel_header) == 32 && sizeof(mot_model_voxel) == 16, "include/mot.h documents the sizes");
 static_assert(kSortTile == 2048, "SceneVoxelBuffers::tiles and mot_scene_voxel_scratch_bytes count tiles of 2048");
-constexpr unsigned long long kSvOutside = ~0ull;
-constexpr int kSvSorted = ((kSceneVoxelKeyBits + kSortDigitBits - 1) / kSortDigitBits) & 1;   // the buffer mot_sort_launch leaves the result in
 constexpr int kSvWriteBlocks = 16384;   // workgroups of X6 at the most (four runs a round each)
-enum { kSvRecords = 0, kSvPlay = 1, kSvRuns = 2, kSvOutsideN = 3, kSvVoxels = 4 };   // the plan's ints
-
-// the cell of a record (include/mot.h, CELL OF A RECORD): the all-ones key when it takes no part
-__device__ __forceinline__ unsigned long long sv_key(const float4& q, const SceneVoxelArgs& a) {
-  const float lim = 3.4028234663852886e38f;
-  if (!(fabsf(q.x) <= lim && fabsf(q.y) <= lim && fabsf(q.z) <= lim)) return kSvOutside;   // (NaN fails the compare)
-  const float tx = q.x * a.inv_x, ty = q.y * a.inv_y, tz = q.z * a.inv_z;
-  if (!(tx >= -1048576.f && tx < 1048576.f && ty >= -1048576.f && ty < 1048576.f && tz >= -2048.f && tz < 2048.f)) return kSvOutside;
-  const int ix = (int)floorf(tx), iy = (int)floorf(ty), iz = (int)floorf(tz);
-  return ((unsigned long long)(unsigned)(iz + 2048) << 42) | ((unsigned long long)(unsigned)(iy + 1048576) << 21) | (unsigned long long)(unsigned)(ix + 1048576);
-}
-__device__ __forceinline__ int sv_play(const SceneVoxelBuffers& v) { return sort_count(v.plan + kSvPlay, v.cap); }
 
 // ------------------------------------------------------------------------------------------ X1
 struct SvKeySink {
@@ -69,45 +55,7 @@ scene_voxels_seq_key_kernel(SceneSplatInput in, SceneJudgeBuffers j, const int* 
 }
 
 // ------------------------------------------------------------------------------------------ X2, X4
-// thread t owns sorted positions base + 8 t .. base + 8 t + 7 of the tile: bit q of the result = position q is a run head; *outs: its all-ones keys
-__device__ __forceinline__ unsigned sv_heads(const unsigned long long* __restrict__ key, long base, int n, int tid, int* outs) {
-  const long p0 = base + (long)tid * kSortItems;
-  unsigned heads = 0;
-  *outs = 0;
-  unsigned long long prev = (p0 > 0 && p0 < n) ? key[p0 - 1] : 0;
-#pragma unroll
-  for (int q = 0; q < kSortItems; q++) {
-    const long p = p0 + q;
-    if (p >= n) break;
-    const unsigned long long k = key[p];
-    if (k == kSvOutside) ++*outs;
-    else if (p == 0 || k != prev) heads |= 1u << q;
-    prev = k;
-  }
-  return heads;
-}
-template <bool kWrite>
-__device__ __forceinline__ void sv_heads_body(const SceneVoxelBuffers& v, int* s_part) {
-  const int tid = threadIdx.x, tile = blockIdx.x;
-  const int n = sv_play(v);
-  const long base = (long)tile * kSortTile;
-  if (base >= n || tile >= v.tiles) return;   // (uniform over the workgroup)
-  int outs;
-  const unsigned heads = sv_heads(v.key[kSvSorted], base, n, tid, &outs);
-  const int cnt[2] = {(int)__popc(heads), outs};
-  int before[2], all[2];
-  block_scan_excl_i32<kSortWaves, 2>(cnt, s_part, before, all);
-  if (!kWrite) {
-    if (tid == 0) { v.part[tile] = all[0]; v.part[v.tiles + tile] = all[1]; }
-    return;
-  }
-  int* __restrict__ start = reinterpret_cast<int*>(v.key[kSvSorted ^ 1]);   // the run table: [cap] starts, then [cap] voxel places
-  int r = v.part[tile] + before[0];   // (X3 turned the tile's count into the runs of earlier tiles)
-  for (unsigned m = heads; m; m &= m - 1) {
-    if (r >= 0 && r < n) start[r] = (int)(base + (long)tid * kSortItems + (__ffs(m) - 1));
-    r++;
-  }
-}
+// sv_heads_body (mot_voxel_runs.h): the tile's run heads and all-ones keys, counted (X2) or ranked into the run table (X4)
 __global__ void MOT_SORT_BOUNDS(kSortBlock) scene_voxels_seq_heads_kernel(SceneVoxelBuffers v) {
   __shared__ int s_part[kSortWaves * 2];
   sv_heads_body<false>(v, s_part);

@@ -166,9 +166,33 @@ def play_static_voxel_map(ctx, frames, leaf, min_points: int = 1, dt_us: float =
     records are dropped. Needs `set_track_links(True)` and `set_scene_grid(...)` on the context.
 
     EACH PIECE IS JUDGED AGAINST THE GRID SO FAR, as in `play_static_map`, AND THINNED ON ITS OWN: a voxel that two pieces see appears in both results (the lattice
-    is the same from piece to piece, so the cells can be matched by the caller). Merging the voxel maps of several pieces is out of scope here; a drive that fits one
+    is the same from piece to piece, so the cells can be matched). `play_merged_voxel_map` merges the pieces' maps into one on the device; a drive that fits one
     call (`max_batch >= len(frames)`) gives one map.
 
     Returns one `get_sequence_scene_voxels` dict per piece (xyz, count, header, totals) with `first_frame` added."""
     return _play_pieces(ctx, frames, dt_us, t0, upload,
                         lambda n: ctx.get_sequence_scene_voxels(n, leaf, min_points=min_points, min_static_hits=min_static_hits, trail=trail, classes=classes))
+
+
+def play_merged_voxel_map(ctx, frames, leaf, min_points: int = 1, dt_us: float = 1.0e5, t0: float = 1.0e9, classes=("known",), min_static_hits: int = 1, trail=(1, 2),
+                          upload=None):
+    """`play_static_voxel_map`'s loop with every piece thinned at `min_points=1` and the pieces' voxel maps merged into ONE map (`Context.merge_voxel_maps`, on the
+    device): a voxel that several pieces see appears once, its count the sum of theirs, its centroid theirs weighted by count; `min_points` is applied by the merge,
+    to the summed count. Needs `set_track_links(True)` and `set_scene_grid(...)` on the context. Up to 16 maps go into one merge; a drive of more pieces is merged in
+    rounds (the map so far and the next 15 pieces).
+
+    EACH PIECE IS JUDGED AGAINST THE GRID SO FAR, as in `play_static_map`: a drive longer than the grid's window keeps its start this way.
+
+    Returns (one dict: xyz, count, header of the last merge; the list of the pieces' headers with `first_frame`)."""
+    pieces = play_static_voxel_map(ctx, frames, leaf, 1, dt_us, t0, classes, min_static_hits, trail, upload)
+    heads = [dict(header=p["header"], totals=p["totals"], first_frame=p["first_frame"]) for p in pieces]
+    if not pieces:
+        return ctx.merge_voxel_maps([dict(xyz=np.zeros((0, 3), np.float32), count=np.zeros(0, np.int32))], leaf, min_points), heads
+    # rounds of up to 16 maps; min_points only in the last one (a cell sparse so far may still fill up)
+    acc, rest = None, list(pieces)
+    while True:
+        take = rest[: 16 - (acc is not None)]
+        rest = rest[len(take):]
+        acc = ctx.merge_voxel_maps(([acc] if acc is not None else []) + take, leaf, 1 if rest else min_points)
+        if not rest:
+            return acc, heads

@@ -930,6 +930,65 @@ int mot_get_sequence_scene_voxels(mot_ctx* ctx, int frames, const mot_scene_judg
         mot_model_voxel* voxels /* may be NULL */, long voxel_capacity, long* n_voxels,
         mot_scene_voxel_header* header, mot_scene_segment totals[5] /* may be NULL */);
 
+/* ---------------------------------------------------------------- voxel maps merged into one (additions within ABI v6)
+ * The voxel lattice is anchored at the global origin: the maps of a drive's pieces, of a drive longer than the scene grid's window, or of two passes over one
+ * street speak of the same cells. These calls merge up to 16 such maps — blocks of mot_model_voxel, as every voxel export of the library writes them — into ONE map
+ * of the same record format and the same order, counts added and centroids weighted by count, on the device. Asynchronous on the context stream; the host never
+ * reads the data; deterministic byte for byte. Nothing is launched or allocated unless these calls are used. Every rule below is fp32 or fp64 exactly as written,
+ * no contraction.
+ *
+ * INPUTS. I[0..n) is the concatenation of the maps in argument order; map k contributes its first min(max(*count_k, 0), capacity_k) voxels, in position order.
+ * count_k is an int32 ON THE DEVICE, read there (NULL: capacity_k is the count): it may point at &d_header->n_stored of an earlier
+ * mot_export_sequence_scene_voxels_dev or of an earlier merge, so that an export -> merge -> export -> merge chain needs no synchronisation. Voxels beyond the
+ * clamped count are never read.
+ * CELL OF AN INPUT. The CELL OF A RECORD rule of the drive voxel call (above), applied to the input's centroid with THIS call's leaf — the same device function.
+ * An input with count <= 0, a non-finite centroid or a cell outside the lattice takes no part and counts in n_outside.
+ * LEAF. It need not be the one the inputs were made with: merging at a coarser leaf is re-thinning. The merge is defined by the centroids' cells, whatever they are.
+ * VOXELS. The distinct cells in ascending (i_z, i_y, i_x). A cell's inputs are taken in concatenation order (map ascending, then position). W = the int64 sum of
+ * the cell's counts; a cell with W < min_points is dropped and counted in n_sparse; a kept voxel's count is min(W, 2^31 - 1), and it counts in n_saturated when W
+ * is larger. The kept voxels are packed back to back, the first out_capacity of them are stored and nothing is written beyond.
+ * CENTROID. The order of the drive voxel call's CENTROID rule: a cell's inputs r_0 .. r_{m-1}, per axis 64 fp64 accumulators acc[l] = ((t_l + t_{l+64}) + ...), each
+ * starting from its own first term, S = ((acc[0] + acc[1]) + ...) + acc[min(m, 64) - 1] in ascending l; the term of input r is t_r = (double)c_r * (double)count_r,
+ * one fp64 multiply; the centroid is (float)(S / (double)W), W the TRUE sum. For m <= 64 this is the plain left-to-right sum.
+ * HEADER. n_inputs = n_outside + sum of the inputs of the kept cells + those of the sparse cells.
+ * STATE. The calls read nothing but their arguments: they work with the grid and the links on or off and on any slot state, touch no slot, no step counter and no
+ * grid, and leave the validity of the sequence exports alone.
+ * REFUSALS, each before anything is launched, the caller's blocks untouched: MOT_E_ARG for a null context, maps, voxel or header; n_maps outside [1, 16]; a leaf or
+ * min_points outside the domain of the drive voxel call; a negative capacity; a sum of capacities above 2^31 - 1; null voxels with capacity > 0; null d_out with
+ * out_capacity > 0; d_out or an input not 16-byte aligned; a count or header pointer off 4 bytes; d_out or d_header overlapping any input block or count word
+ * (inputs may overlap each other). MOT_E_HIP when the scratch cannot be had — all of its blocks or none, the next call tries again.
+ * mot_merge_voxel_maps takes host blocks (and host counts, clamped on the host), synchronises and stages inputs and output through device blocks that live for the
+ * duration of the call: *n_voxels and the header are always delivered; MOT_E_CAPACITY with nothing copied when out is given and out_capacity < *n_voxels; its
+ * n_stored is what it copied (n_voxels, or 0). Host blocks need 4-byte alignment only, and may overlap.
+ *
+ * Scratch: ONE block of the merge's own on the context, grown on demand to the sum of the capacities — 24 bytes per input of capacity (two 8-byte keys and two
+ * 4-byte payloads, which ping-pong in the sort; the buffers the sort leaves free hold the run table) and 1040 bytes per 2048 inputs for the sort's tables and the
+ * per-tile counts. The inputs are read in place, not staged. Released by mot_destroy.
+ * Kernels (csrc/voxel_merge.hip, csrc/mot_sort.h, csrc/mot_voxel_runs.h): a key kernel over the concatenation (every workgroup repeats the prefix over the <= 16
+ * counts); the radix sort of the drive voxel call over the same 56 key bits; run heads, a scan, the run table; the runs' summed counts; kept runs, a scan, the
+ * header; the voxels — a run of at most 64 inputs by one thread, a longer one by a wave. 30 launches whatever the data and n_maps are (29 without an output block).
+ * No global atomics, no workgroup waits on another, the output does not depend on scheduling. Cost: profiles/voxel_merge.md (tools/time_voxel_merge.py). */
+enum { MOT_VOXEL_MERGE_MAX_MAPS = 16 };
+typedef struct mot_voxel_map_src {      /* 24 bytes */
+  const mot_model_voxel* voxels;        /* _dev call: device block, 16-byte aligned; host call: host block */
+  const int32_t* count;                 /* _dev call: an int32 ON THE DEVICE, read there and clamped to [0, capacity]; NULL: capacity is the count.
+                                           Host call: a host int32 or NULL */
+  long capacity;                        /* [0, 2^31 - 1]; voxels may be NULL when 0 */
+} mot_voxel_map_src;
+typedef struct mot_voxel_merge_header { /* 32 bytes */
+  int32_t n_inputs;     /* sum of the clamped counts */
+  int32_t n_outside;    /* inputs that took no part: count <= 0, a non-finite centroid, or a cell outside the lattice */
+  int32_t n_voxels;     /* kept voxels (TRUE, whatever out_capacity is) */
+  int32_t n_sparse;     /* occupied cells dropped: summed count < min_points */
+  int32_t n_stored;     /* min(n_voxels, out_capacity) */
+  int32_t n_saturated;  /* kept voxels whose summed count exceeds 2^31 - 1 (stored as 2^31 - 1) */
+  int32_t reserved[2];  /* 0 */
+} mot_voxel_merge_header;
+int mot_merge_voxel_maps_dev(mot_ctx* ctx, const mot_voxel_map_src* maps /* HOST array */, int n_maps, const mot_voxel_params* voxel,
+        mot_model_voxel* d_out, long out_capacity, mot_voxel_merge_header* d_header);
+int mot_merge_voxel_maps(mot_ctx* ctx, const mot_voxel_map_src* maps /* host array, host blocks */, int n_maps, const mot_voxel_params* voxel,
+        mot_model_voxel* out /* may be NULL */, long out_capacity, long* n_voxels, mot_voxel_merge_header* header);
+
 /* on != 0: the fused entry points send their launch sequence (13 kernels with the tracker) as ONE hipGraph launch, captured once per launch geometry
  * (batch, chunks of the largest frame, tracker on / off, outputs); what changes per call without changing the geometry travels in the
  * device-resident argument block. For contexts somebody waits on frame by frame (one or a few streams): the host's part of a frame
