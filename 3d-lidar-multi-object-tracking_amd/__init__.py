@@ -149,6 +149,39 @@ class MotVoxelMapSrc(C.Structure):
 
 
 assert C.sizeof(MotVoxelMapSrc) == 24
+# the classes of mot_export_map_points_dev / mot_get_map_points (a frame's points judged against a voxel index); the segments are SCENE_SEGMENT_DTYPE
+MAP_OUTSIDE, MAP_MOVING, MAP_SPARSE, MAP_ABSENT, MAP_PRESENT, MAP_CLASSES = 0, 1, 2, 3, 4, 5
+MAP_CLASS_NAMES = ("outside", "moving", "sparse", "absent", "present")
+
+
+class MotVoxelIndex(C.Structure):
+    """struct mot_voxel_index: a HOST struct of device pointers (mot_index_voxel_maps_dev fills the leaf in)"""
+    _fields_ = [("keys", C.c_void_p), ("counts", C.c_void_p), ("header", C.c_void_p), ("capacity", C.c_long), ("leaf_x", C.c_float), ("leaf_y", C.c_float), ("leaf_z", C.c_float),
+                ("reserved", C.c_int32)]
+
+
+class MotMapJudgeParams(C.Structure):
+    """struct mot_map_judge_params"""
+    _fields_ = [("min_count", C.c_int32), ("reach", C.c_int32)]
+
+
+assert C.sizeof(MotVoxelIndex) == 48 and C.sizeof(MotMapJudgeParams) == 8
+
+
+def voxel_index(d_keys_ptr: int, d_counts_ptr: int, d_header_ptr: int, capacity: int, leaf=None) -> MotVoxelIndex:
+    """the descriptor of an index in the caller's device blocks: [capacity] uint64 keys (8-byte aligned), [capacity] int32 counts, a 32-byte header
+    (VOXEL_MERGE_HEADER_DTYPE). leaf: only for an index that index_voxel_maps_dev wrote earlier through another descriptor"""
+    lx, ly, lz = (0.0, 0.0, 0.0) if leaf is None else ((leaf, leaf, leaf) if np.isscalar(leaf) else leaf)
+    return MotVoxelIndex(int(d_keys_ptr) or None, int(d_counts_ptr) or None, int(d_header_ptr) or None, int(capacity), float(lx), float(ly), float(lz), 0)
+
+
+def _map_mask(classes) -> int:
+    """None: all five; an int: the bit mask itself; else an iterable of class numbers or names"""
+    if classes is None:
+        return (1 << MAP_CLASSES) - 1
+    if isinstance(classes, (int, np.integer)):
+        return int(classes)
+    return sum({1 << (MAP_CLASS_NAMES.index(k) if isinstance(k, str) else int(k)) for k in classes})
 
 
 class MotAccumView(C.Structure):
@@ -180,6 +213,7 @@ EXPORTS = (
     "mot_set_scene_grid", "mot_accumulate_scene", "mot_export_scene_grid_dev", "mot_get_scene_grid", "mot_sequence_products_dev",
     "mot_export_scene_points_dev", "mot_get_scene_points", "mot_export_sequence_scene_points_dev", "mot_get_sequence_scene_points",
     "mot_export_sequence_scene_voxels_dev", "mot_get_sequence_scene_voxels", "mot_merge_voxel_maps_dev", "mot_merge_voxel_maps",
+    "mot_index_voxel_maps_dev", "mot_export_map_points_dev", "mot_get_map_points",
     "mot_gather_unique_id", "mot_gather_create", "mot_gather_contribute", "mot_gather_result", "mot_gather_synchronize", "mot_gather_destroy", "mot_gather_last_error",
 )
 ABI_VERSION = 6
@@ -587,6 +621,38 @@ class Context:
         self._ck(self.lib.mot_merge_voxel_maps(self._h, arr, len(blocks), C.byref(v), _vp(out), C.c_long(bound), C.byref(n), _vp(hdr)))
         out = out[: n.value]
         return dict(xyz=out["xyz"].copy(), count=out["count"].copy(), header=hdr[0].copy())
+
+    def index_voxel_maps_dev(self, maps, leaf, index: MotVoxelIndex, min_points: int = 1) -> MotVoxelIndex:
+        """up to 16 voxel maps of the global lattice indexed on the device (mot_index_voxel_maps_dev): the merge without the centroid. maps: as for
+        merge_voxel_maps_dev, the counts read on the device. -> the caller's device blocks named by `index` (voxel_index()): the kept cells' 64-bit keys, strictly
+        ascending, their summed counts (saturated at 2^31 - 1) and the merge's header, whose n_stored is the index's length; the descriptor's leaf is filled in and
+        the descriptor returned: what export_map_points_dev / get_map_points take. Asynchronous"""
+        arr = (MotVoxelMapSrc * max(len(maps), 1))(*[MotVoxelMapSrc(int(p) or None, int(n) or None, int(cap)) for p, n, cap in maps])
+        v = voxel_params(leaf, min_points)
+        self._ck(self.lib.mot_index_voxel_maps_dev(self._h, arr, len(maps), C.byref(v), C.byref(index)))
+        return index
+
+    def export_map_points_dev(self, batch: int, index: MotVoxelIndex, d_points_ptr: int, point_stride: int, d_segments_ptr: int, d_classes_ptr: int = 0, class_stride: int = 0,
+                              min_count: int = 1, reach: int = 0, classes=None, frame=MOT_FRAME_GLOBAL):
+        """the elevated points of slots 0..batch-1 judged against a voxel index and partitioned by class (mot_export_map_points_dev) -> caller's device blocks, in
+        the shape of export_scene_points_dev: 16-byte records d_points[b * point_stride + i] (the classes of `classes`, ascending, each in input order), 8-byte
+        segments d_segments[b * 5 + k] = {first, count} (SCENE_SEGMENT_DTYPE; classes MAP_OUTSIDE .. MAP_PRESENT) and, if given, one class byte per elevated point.
+        MAP_ABSENT: the map of the earlier pass has nothing there. reach 1: the 27 cells round the point's. Needs links, not the scene grid; asynchronous"""
+        p = MotMapJudgeParams(int(min_count), int(reach))
+        self._ck(self.lib.mot_export_map_points_dev(self._h, int(batch), C.byref(index), C.byref(p), _map_mask(classes), _frame(frame), C.c_void_p(d_points_ptr or None),
+                                                    C.c_long(point_stride), C.c_void_p(d_segments_ptr or None), C.c_void_p(d_classes_ptr or None), C.c_long(class_stride)))
+
+    def get_map_points(self, slot: int, index: MotVoxelIndex, min_count: int = 1, reach: int = 0, classes=None, frame=MOT_FRAME_GLOBAL) -> dict:
+        """one slot's elevated points judged against a voxel index in DEVICE blocks (mot_get_map_points; synchronises): segments [5] (SCENE_SEGMENT_DTYPE: first,
+        count per class MAP_OUTSIDE .. MAP_PRESENT; first = -1 for a class outside `classes`), xyz [n, 3] and index [n] of the selected classes back to back,
+        classes [n_elevated] (uint8, input order)"""
+        p = MotMapJudgeParams(int(min_count), int(reach))
+        cap = self.max_points
+        pts = np.zeros(max(cap, 1), TRACK_POINT_DTYPE); seg = np.zeros(MAP_CLASSES, SCENE_SEGMENT_DTYPE); cls = np.zeros(max(cap, 1), np.uint8); npts, ne = C.c_int(0), C.c_int(0)
+        self._ck(self.lib.mot_get_map_points(self._h, int(slot), C.byref(index), C.byref(p), _map_mask(classes), _frame(frame), _vp(pts), cap, C.byref(npts), _vp(seg), _vp(cls), cap,
+                                             C.byref(ne)))
+        pts = pts[: npts.value]
+        return dict(segments=seg, xyz=pts["xyz"].copy(), index=pts["index"].copy(), classes=cls[: ne.value].copy())
 
     def get_scene_grid(self, slot: int = 0, cells: bool = True) -> dict:
         """one slot's grid on the host (mot_get_scene_grid): header (a SCENE_HEADER_DTYPE record) and cells [size, size] indexed (v, u) (SCENE_CELL_DTYPE;

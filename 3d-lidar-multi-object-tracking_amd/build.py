@@ -14,10 +14,10 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmot_hip.so")
-SOURCES = ["ground.hip", "cluster.hip", "box.hip", "regroup.hip", "side.hip", "track.hip", "link.hip", "track_points.hip", "track_accum.hip", "track_accum_seq.hip", "track_models.hip", "track_voxels.hip", "scene_grid.hip", "scene_grid_seq.hip", "scene_judge.hip", "scene_judge_seq.hip", "scene_voxels_seq.hip", "voxel_merge.hip", "mot_api.hip", "mot_api_stages.hip", "mot_api_tracks.hip", "mot_api_scene.hip", "mot_gather.hip"]
+SOURCES = ["ground.hip", "cluster.hip", "box.hip", "regroup.hip", "side.hip", "track.hip", "link.hip", "track_points.hip", "track_accum.hip", "track_accum_seq.hip", "track_models.hip", "track_voxels.hip", "scene_grid.hip", "scene_grid_seq.hip", "scene_judge.hip", "scene_judge_seq.hip", "scene_voxels_seq.hip", "voxel_merge.hip", "map_judge.hip", "mot_api.hip", "mot_api_stages.hip", "mot_api_tracks.hip", "mot_api_scene.hip", "mot_gather.hip"]
 # host-only translation units: no __global__ function (tools/kernel_resources.py skips them, the emulator build leaves their libm calls unperturbed)
 HOST_SOURCES = ["mot_api.hip", "mot_api_stages.hip", "mot_api_tracks.hip", "mot_api_scene.hip", "mot_gather.hip"]
-HEADERS = ["mot_internal.h", "mot_host.h", "mot_math.h", "mot_wave.h", "mot_wave_sync.h", "mot_debug.h", "mot_debug_api.h", "mot_track_prep.h", "mot_track_place.h", "mot_track_model.h", "mot_scene_splat.h", "mot_scene_judge.h", "mot_sort.h", "mot_voxel_runs.h", os.path.join("..", "..", "include", "mot.h")]
+HEADERS = ["mot_internal.h", "mot_host.h", "mot_math.h", "mot_wave.h", "mot_wave_sync.h", "mot_debug.h", "mot_debug_api.h", "mot_track_prep.h", "mot_track_place.h", "mot_track_model.h", "mot_scene_splat.h", "mot_scene_judge.h", "mot_sort.h", "mot_voxel_runs.h", "mot_voxel_cell.h", os.path.join("..", "..", "include", "mot.h")]
 
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",

@@ -1,5 +1,5 @@
 // mot_api_scene.hip — host side of the C-ABI (include/mot.h), the rolling static-scene grid: the setter and what it owns, the per-slot step counters, the state
-// checks of mot_accumulate_scene, the two readers, the frame's points and a recorded drive's points judged against the grid, the drive's static map thinned to voxels, voxel maps merged into one. Kernels: scene_grid.hip, scene_grid_seq.hip, scene_judge.hip, scene_judge_seq.hip, scene_voxels_seq.hip, voxel_merge.hip. Context and helpers: mot_host.h.
+// checks of mot_accumulate_scene, the two readers, the frame's points and a recorded drive's points judged against the grid, the drive's static map thinned to voxels, voxel maps merged into one, voxel maps indexed and the frame's points judged against the index (its own scratch: no grid needed). Kernels: scene_grid.hip, scene_grid_seq.hip, scene_judge.hip, scene_judge_seq.hip, scene_voxels_seq.hip, voxel_merge.hip, map_judge.hip. Context and helpers: mot_host.h.
 #include "mot_host.h"
 
 // The setter owns the feature's memory: cells, headers, previous origins, the argument block and its ring of page-locked staging blocks are allocated together and
@@ -680,6 +680,170 @@ extern "C" int mot_merge_voxel_maps(mot_ctx* c, const mot_voxel_map_src* maps, i
     MOT_HIP(c, hipMemcpyAsync(out, blk.vox, (size_t)nv * sizeof(mot_model_voxel), hipMemcpyDeviceToHost, c->stream));
     MOT_HIP(c, hipStreamSynchronize(c->stream));
   }
+  return MOT_OK;
+}
+
+// ---------------------------------------------------------------------------------------- voxel maps indexed (voxel_merge.hip: the merge's count launches, one write launch)
+// The merge's argument checks, scratch block and launches; the descriptor's three blocks are read in place of d_out and d_header.
+struct IndexBlock { const void* p; size_t bytes; };
+static void index_blocks(const mot_voxel_index* x, IndexBlock (&blk)[3]) {
+  const size_t cap = (size_t)(x->capacity < 0 ? 0 : x->capacity);
+  blk[0] = {x->keys, cap * sizeof(uint64_t)}; blk[1] = {x->counts, cap * sizeof(int32_t)}; blk[2] = {x->header, sizeof(mot_voxel_merge_header)};
+}
+// what the index call and the judge refuse alike of a descriptor's blocks
+static int check_index_blocks(mot_ctx* c, const char* who, const mot_voxel_index* x) {
+  if (!x) return fail(c, MOT_E_ARG, who, ": null index");
+  if (!x->header) return fail(c, MOT_E_ARG, who, ": null index header");
+  if (x->capacity < 0 || x->capacity > 2147483647L) return fail(c, MOT_E_ARG, who, ": the index capacity must lie in [0, 2^31 - 1]");
+  if ((!x->keys || !x->counts) && x->capacity > 0) return fail(c, MOT_E_ARG, who, ": null index keys or counts with a capacity");
+  if (((size_t)x->keys & 7) || (((size_t)x->counts | (size_t)x->header) & 3)) return fail(c, MOT_E_ARG, who, ": index keys off 8 bytes, or counts or header off 4 bytes");
+  return MOT_OK;
+}
+
+extern "C" int mot_index_voxel_maps_dev(mot_ctx* c, const mot_voxel_map_src* maps, int n_maps, const mot_voxel_params* voxel, mot_voxel_index* index) {
+  if (!c) return MOT_E_ARG;
+  MOT_GUARD(c);
+  const char* who = "mot_index_voxel_maps_dev";
+  MOT_TRY(check_index_blocks(c, who, index));
+  long total = 0;
+  MOT_TRY(check_merge_args(c, who, maps, n_maps, voxel, index->keys, index->capacity, &total));
+  IndexBlock blk[3];
+  index_blocks(index, blk);
+  for (int a = 0; a < 3; a++)
+    for (int b = a + 1; b < 3; b++)
+      if (blocks_overlap(blk[a].p, blk[a].bytes, blk[b].p, blk[b].bytes)) return fail(c, MOT_E_ARG, who, ": the index's keys, counts and header overlap each other");
+  VoxelMergeMaps m = {};
+  for (int k = 0; k < n_maps; k++) {
+    const size_t in_bytes = (size_t)maps[k].capacity * sizeof(mot_model_voxel);
+    if (((size_t)maps[k].voxels & 15) || ((size_t)maps[k].count & 3)) return fail(c, MOT_E_ARG, who, ": an input block off 16 bytes or a count off 4 bytes");
+    for (const IndexBlock& o : blk)
+      if (blocks_overlap(o.p, o.bytes, maps[k].voxels, in_bytes) || blocks_overlap(o.p, o.bytes, maps[k].count, 4))
+        return fail(c, MOT_E_ARG, who, ": an index block overlaps an input block or a count");
+    m.vox[k] = maps[k].voxels; m.count[k] = maps[k].count; m.cap[k] = (int)maps[k].capacity;
+  }
+  m.n_maps = n_maps; m.short_max = c->vm_short_max;
+  MOT_TRY(ensure_merge_scratch(c, total));
+  const SceneVoxelBuffers v = merge_buffers(c, total);
+  mot_launch_voxel_merge_count(m, v, merge_args(voxel), index->capacity, index->header, c->stream);
+  mot_launch_voxel_merge_index(m, v, reinterpret_cast<unsigned long long*>(index->keys), index->counts, index->capacity, c->stream);
+  MOT_HIP(c, hipGetLastError());
+  index->leaf_x = voxel->leaf_x; index->leaf_y = voxel->leaf_y; index->leaf_z = voxel->leaf_z; index->reserved = 0;
+  return MOT_OK;
+}
+
+// ---------------------------------------------------------------------------------------- a frame's points judged against a voxel index (map_judge.hip)
+// The validity of check_point_tracks, sequence slots refused; the grid is neither required nor read. The scratch and the ring are the calls' own (the scene judge's
+// go with the grid): taken at the first call, all or none, released by mot_destroy alone.
+static int check_map_judge_args(mot_ctx* c, const char* who, const mot_voxel_index* x, const mot_map_judge_params* p, int class_mask, int frame) {
+  MOT_TRY(check_index_blocks(c, who, x));
+  if (!p) return fail(c, MOT_E_ARG, who, ": null params");
+  const float leaf[3] = {x->leaf_x, x->leaf_y, x->leaf_z};
+  for (float l : leaf)
+    if (!(l >= 1e-2f && l <= 1e3f)) return fail(c, MOT_E_ARG, who, ": every leaf of the index must be finite and in [1e-2, 1e3] metres (mot_index_voxel_maps_dev writes it)");
+  if (p->min_count < 1) return fail(c, MOT_E_ARG, who, ": min_count must lie in [1, 2^31 - 1]");
+  if (p->reach != 0 && p->reach != 1) return fail(c, MOT_E_ARG, who, ": reach must be 0 or 1");
+  if (class_mask & ~((1 << MOT_MAP_CLASSES) - 1)) return fail(c, MOT_E_ARG, who, ": unknown class bits");
+  if (frame != MOT_FRAME_GLOBAL && frame != MOT_FRAME_SENSOR) return fail(c, MOT_E_ARG, who, ": frame must be MOT_FRAME_GLOBAL or MOT_FRAME_SENSOR");
+  return MOT_OK;
+}
+static int check_map_judge_slot(mot_ctx* c, int b, const char* who) {
+  MOT_TRY(check_point_tracks(c, b, who));
+  if (c->res.sequence_frame(b)) return fail(c, MOT_E_STATE, who, ": the slots hold the frames of ONE stream (mot_sequence_dev)");
+  return MOT_OK;
+}
+static int ensure_map_judge(mot_ctx* c, bool host_stage) {
+  c->mj_chunks = (c->cap + kSceneChunk - 1) / kSceneChunk;
+  if (!c->d_mj_cls || !c->d_mj_rows || !c->d_mj_args || !c->mj_ring.base) {
+    int rc = dev_alloc(c, &c->d_mj_cls, (size_t)c->batch * c->cap);
+    if (!rc) rc = dev_alloc(c, &c->d_mj_rows, (size_t)c->batch * c->mj_chunks * kSceneJudgeRow * sizeof(int));
+    if (!rc) rc = dev_alloc(c, &c->d_mj_args, (size_t)c->batch * sizeof(EgoTf));
+    if (!rc) rc = c->mj_ring.create(c, (size_t)c->batch * sizeof(EgoTf));   // (skips what exists; the ring's events stay in the registry, as those of every ring do)
+    if (rc) {
+      const std::string why = c->err;
+      (void)release(c, &c->d_mj_cls); (void)release(c, &c->d_mj_rows); (void)release(c, &c->d_mj_args); (void)release(c, &c->mj_ring.base);
+      c->err = why;
+      return rc;
+    }
+  }
+  // [cap records][5 segments, padded to 48 bytes][cap class bytes]
+  if (host_stage) MOT_TRY(dev_alloc(c, &c->d_mj_stage, (size_t)c->cap * sizeof(mot_track_point) + 48 + (size_t)c->cap));
+  return MOT_OK;
+}
+static int launch_map_judge(mot_ctx* c, int first, int n, const mot_voxel_index* x, const mot_map_judge_params* p, int class_mask, int frame, mot_track_point* d_points,
+                            long point_stride, mot_scene_segment* d_segments, uint8_t* d_classes, long class_stride) {
+  const EgoTf* d_tf;   // the matrices the slots' boxes took (the cell test needs them in either frame)
+  MOT_TRY(send_link_tf(c, &c->mj_ring, c->d_mj_args, first, n, nullptr, &d_tf));
+  SceneSplatInput in = scene_input(c, true);
+  SceneJudgeBuffers j = {};
+  j.cls = c->d_mj_cls; j.rows = c->d_mj_rows; j.max_chunks = c->mj_chunks; j.class_mask = class_mask;
+  MapJudgeIndex ix;
+  ix.keys = reinterpret_cast<const unsigned long long*>(x->keys); ix.counts = x->counts; ix.n_stored = &x->header->n_stored; ix.capacity = (int)x->capacity;
+  ix.a = {1.0f / x->leaf_x, 1.0f / x->leaf_y, 1.0f / x->leaf_z, 1};
+  ix.min_count = p->min_count; ix.reach = p->reach;
+  for_layout_runs(c, first, n, [&](int k0, int k1, int packed) {
+    in.elevated_packed = packed;
+    mot_launch_map_judge(in, j, ix, first + k0, k1 - k0, c->max_points, d_tf + k0, frame == MOT_FRAME_GLOBAL, d_points ? d_points + (long)k0 * point_stride : nullptr, point_stride,
+                         d_segments + (long)k0 * MOT_MAP_CLASSES, d_classes ? d_classes + (long)k0 * class_stride : nullptr, class_stride, c->stream);
+  });
+  MOT_HIP(c, hipGetLastError());
+  return MOT_OK;
+}
+
+extern "C" int mot_export_map_points_dev(mot_ctx* c, int batch, const mot_voxel_index* index, const mot_map_judge_params* p, int class_mask, int frame, mot_track_point* d_points,
+                                         long point_stride, mot_scene_segment* d_segments, uint8_t* d_classes, long class_stride) {
+  if (!c) return MOT_E_ARG;
+  MOT_GUARD(c);
+  const char* who = "mot_export_map_points_dev";
+  MOT_TRY(check_map_judge_args(c, who, index, p, class_mask, frame));
+  if (!d_segments || batch < 1 || batch > c->batch || point_stride < 0 || class_stride < 0 || (!d_points && (point_stride > 0 || class_mask)) ||
+      (((size_t)d_points | (size_t)d_segments) & 3))
+    return fail(c, MOT_E_ARG, who, ": bad argument (null segments, batch out of range, a negative stride, null points with a stride or a mask, a block off 4 bytes)");
+  IndexBlock blk[3];
+  index_blocks(index, blk);
+  const IndexBlock out[3] = {{d_points, (size_t)batch * (size_t)point_stride * sizeof(mot_track_point)}, {d_segments, (size_t)batch * MOT_MAP_CLASSES * sizeof(mot_scene_segment)},
+                             {d_classes, (size_t)batch * (size_t)class_stride}};
+  for (const IndexBlock& o : out)
+    for (const IndexBlock& i : blk)
+      if (blocks_overlap(o.p, o.bytes, i.p, i.bytes)) return fail(c, MOT_E_ARG, who, ": an output block overlaps a block of the index");
+  for (int b = 0; b < batch; b++) MOT_TRY(check_map_judge_slot(c, b, who));   // every slot before anything is launched
+  MOT_TRY(ensure_map_judge(c, false));
+  return launch_map_judge(c, 0, batch, index, p, class_mask, frame, d_points, point_stride, d_segments, d_classes, class_stride);
+}
+
+extern "C" int mot_get_map_points(mot_ctx* c, int slot, const mot_voxel_index* index, const mot_map_judge_params* p, int class_mask, int frame, mot_track_point* points,
+                                  int point_capacity, int* n_points, mot_scene_segment segments[5], uint8_t* classes, int class_capacity, int* n_elevated) {
+  if (!c) return MOT_E_ARG;
+  MOT_GUARD(c);
+  const char* who = "mot_get_map_points";
+  MOT_TRY(check_map_judge_args(c, who, index, p, class_mask, frame));
+  if (slot < 0 || slot >= c->batch || point_capacity < 0 || class_capacity < 0 || !n_points || !n_elevated || !segments)
+    return fail(c, MOT_E_ARG, who, ": slot or a capacity out of range, or a null count or segment table");
+  MOT_TRY(check_map_judge_slot(c, slot, who));
+  MOT_TRY(ensure_map_judge(c, true));
+  // the slot alone into the staging block, with the block's own capacities; what fits the caller's buffers is decided here
+  mot_track_point* d_pts = reinterpret_cast<mot_track_point*>(c->d_mj_stage);
+  mot_scene_segment* d_seg = reinterpret_cast<mot_scene_segment*>(c->d_mj_stage + (size_t)c->cap * sizeof(mot_track_point));
+  uint8_t* d_cls = reinterpret_cast<uint8_t*>(c->d_mj_stage + (size_t)c->cap * sizeof(mot_track_point) + 48);
+  MOT_TRY(launch_map_judge(c, slot, 1, index, p, class_mask, frame, d_pts, c->cap, d_seg, classes ? d_cls : nullptr, c->cap));
+  char* pin;
+  MOT_TRY(pinned_scratch(c, 48, &pin));
+  MOT_HIP(c, hipMemcpyAsync(pin, d_seg, MOT_MAP_CLASSES * sizeof(mot_scene_segment), hipMemcpyDeviceToHost, c->stream));
+  MOT_HIP(c, hipStreamSynchronize(c->stream));
+  const mot_scene_segment* h = reinterpret_cast<const mot_scene_segment*>(pin);
+  long ne = 0, np = 0;
+  for (int k = 0; k < MOT_MAP_CLASSES; k++) {
+    if (h[k].count < 0 || h[k].count > c->cap) return fail(c, MOT_E_STATE, who, ": inconsistent counts");
+    ne += h[k].count;
+    if ((class_mask >> k) & 1) np += h[k].count;
+  }
+  if (ne > c->cap) return fail(c, MOT_E_STATE, who, ": inconsistent counts");
+  memcpy(segments, h, MOT_MAP_CLASSES * sizeof(mot_scene_segment));
+  *n_points = (int)np; *n_elevated = (int)ne;
+  if (points && np > point_capacity) return fail(c, MOT_E_CAPACITY, "more selected points than the caller's point buffer holds");
+  if (classes && ne > class_capacity) return fail(c, MOT_E_CAPACITY, "more elevated points than the caller's class buffer holds");
+  if (points && np > 0) MOT_HIP(c, hipMemcpyAsync(points, d_pts, (size_t)np * sizeof(mot_track_point), hipMemcpyDeviceToHost, c->stream));
+  if (classes && ne > 0) MOT_HIP(c, hipMemcpyAsync(classes, d_cls, (size_t)ne, hipMemcpyDeviceToHost, c->stream));
+  MOT_HIP(c, hipStreamSynchronize(c->stream));
   return MOT_OK;
 }
 

@@ -307,6 +307,14 @@ struct mot_ctx {
   char* d_vm_scratch = nullptr;            // mot_voxel_merge_scratch_bytes(vm_cap): keys, payloads, the sort's table, the per-tile counts, the plan
   long vm_cap = -1;                        // the sum of capacities the block was laid out for (grown on demand; -1: none)
   int vm_short_max = 64;                   // runs of at most so many inputs are summed by one thread (mot_debug_voxel_merge_cut: measurement; the bytes do not depend on it)
+  // mot_export_map_points_dev / mot_get_map_points (map_judge.hip): blocks of their own — the calls work with the grid off, so nothing here is the grid's.
+  // Allocated at the first call, the three blocks and the ring or none; kept until mot_destroy
+  uint8_t* d_mj_cls = nullptr;             // [batch][cap] class of every elevated point
+  int* d_mj_rows = nullptr;                // [batch][mj_chunks][10] per chunk the points per class and where its records go
+  int mj_chunks = 0;                       // max_points / kSceneChunk rounded up
+  char* d_mj_args = nullptr;               // [batch] sensor -> global matrices
+  PinnedRing mj_ring;                      // blocks of `batch` matrices
+  char* d_mj_stage = nullptr;              // mot_get_map_points: one slot's records, segments and classes before they go to the host (allocated at ITS first call)
   std::vector<EgoTf> link_tf;          // [batch] the matrix every slot's boxes took in its last fused call with the tracker, kept while links are on (host side)
   Vec2d* d_cp = nullptr;
   TrackItem* d_items = nullptr;

@@ -615,6 +615,25 @@ inline size_t mot_voxel_merge_scratch_bytes(long cap, SceneVoxelBuffers* at = nu
 void mot_launch_voxel_merge_count(const VoxelMergeMaps& m, const SceneVoxelBuffers& v, const SceneVoxelArgs& a, long out_capacity, mot_voxel_merge_header* header, hipStream_t stream);
 void mot_launch_voxel_merge_write(const VoxelMergeMaps& m, const SceneVoxelBuffers& v, int min_points, mot_model_voxel* out, long out_capacity, hipStream_t stream);
 
+// the same count pipeline, then — with room in the index — ONE write launch: per kept run below the capacity the run's key itself (the sorted key at the run's
+// start) and its saturated summed count (mot_index_voxel_maps_dev). Behind mot_launch_voxel_merge_count on the same stream, the same maps and buffers
+void mot_launch_voxel_merge_index(const VoxelMergeMaps& m, const SceneVoxelBuffers& v, unsigned long long* keys, int* counts, long capacity, hipStream_t stream);
+
+// A frame's points judged against a voxel index (map_judge.hip, mot_export_map_points_dev): READS the index mot_index_voxel_maps_dev wrote — `capacity` ascending
+// keys and their counts, the length in play an int32 ON THE DEVICE, clamped there. The chunk rows and the class bytes are a SceneJudgeBuffers of the feature's own
+// (its three grid thresholds unused): the scan and the scatter are the scene judge's bodies (mot_scene_judge.h).
+struct MapJudgeIndex {
+  const unsigned long long* keys;   // [capacity], strictly ascending below n
+  const int* counts;                // [capacity]
+  const int* n_stored;              // on the device: the index's length, clamped to [0, capacity] by every reader
+  int capacity;
+  SceneVoxelArgs a;                 // 1.0f / leaf of the index, computed once on the host (min_points unused)
+  int min_count, reach;             // a cell counts from min_count on; reach 0: the point's own cell, 1: its 27 neighbours
+};
+// slots first .. first + batch - 1 into block k = 0 .. batch - 1 of the caller's buffers: classify, scan and — with a mask and room for records — scatter
+void mot_launch_map_judge(const SceneSplatInput& in, const SceneJudgeBuffers& j, const MapJudgeIndex& x, int first, int batch, int max_n, const EgoTf* tf, int global,
+                          mot_track_point* points, long point_stride, mot_scene_segment* segments, uint8_t* classes, long class_stride, hipStream_t stream);
+
 #include "mot_wave_sync.h"   // MOT_WAVE_SYNC (shared with mot_wave.h)
 
 void mot_launch_ground(const MotDevParams& p, const GroundBuffers& g, int batch, int max_n, hipStream_t stream);

@@ -74,6 +74,37 @@ __device__ __forceinline__ void sj_scan_chunks(int* __restrict__ rows, int chunk
   }
 }
 
+// THE per-slot scan body (scene_judge_scan_kernel, map_judge_scan_kernel; ONE workgroup per slot): the chunks of slot b scanned per class, the mask applied, the
+// slot's segment table `seg` ([5] of the caller's), and the segment starts added to every chunk's places
+__device__ __forceinline__ void sj_scan_body(const SceneSplatInput& in, const SceneJudgeBuffers& j, int b, mot_scene_segment* __restrict__ seg, int* s_part, int* s_total) {
+  const int tid = threadIdx.x;
+  const int chunks = sj_chunks(in, j, b);
+  int* __restrict__ rows = j.rows + (long)b * j.max_chunks * kSceneJudgeRow;
+  sj_scan_chunks(rows, chunks, s_part, s_total, tid);
+  __syncthreads();
+  int first_of[MOT_SCENE_CLASSES];
+  int run = 0;
+#pragma unroll
+  for (int c = 0; c < MOT_SCENE_CLASSES; c++) {
+    const bool picked = (j.class_mask >> c) & 1;
+    first_of[c] = picked ? run : -1;
+    if (picked) run += s_total[c];
+  }
+  if (tid < MOT_SCENE_CLASSES) {
+    int* o = reinterpret_cast<int*>(seg + tid);
+    int first = -1;
+#pragma unroll
+    for (int c = 0; c < MOT_SCENE_CLASSES; c++) first = tid == c ? first_of[c] : first;
+    o[0] = first; o[1] = s_total[tid];
+  }
+  // every thread adds the segment starts to the places it wrote itself (chunk ch is thread ch % 256's)
+  for (int ch = tid; ch < chunks; ch += kSceneBlock) {
+#pragma unroll
+    for (int c = 0; c < MOT_SCENE_CLASSES; c++)
+      if (first_of[c] > 0) rows[(long)ch * kSceneJudgeRow + MOT_SCENE_CLASSES + c] += first_of[c];
+  }
+}
+
 // the in-chunk ranking, a wave's share: the lane's rank among the points of its class inside the 64-point tile, and the tile's five counts into the LDS table
 __device__ __forceinline__ int sj_rank(int cls, int tile, int lane, unsigned long long below, int (*s_cnt)[MOT_SCENE_CLASSES]) {
   const unsigned long long a0 = __ballot(cls & 1), a1 = __ballot(cls & 2), a2 = __ballot(cls & 4);

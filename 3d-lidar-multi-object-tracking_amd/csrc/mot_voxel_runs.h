@@ -1,5 +1,5 @@
 // mot_voxel_runs.h — what the two users of the global voxel lattice share on the device (HIP, wave64; product code): scene_voxels_seq.hip (a drive's records thinned
-// to voxels) and voxel_merge.hip (voxel maps merged into one). THE cell rule (sv_key: include/mot.h, CELL OF A RECORD — one device function, so that a voxel is the
+// to voxels) and voxel_merge.hip (voxel maps merged into one). THE cell rule (sv_key of mot_voxel_cell.h: include/mot.h, CELL OF A RECORD — one device function, so that a voxel is the
 // same piece of the world whichever call made it), the ints of the plan, and the run heads of a sorted key array, counted per tile and turned into the run table.
 // Both users lay their scratch out as a SceneVoxelBuffers (mot_internal.h): key[kSvSorted] holds the sorted keys, the other key buffer the run table ([cap] starts,
 // then [cap] voxel places), part[0] / part[1] the tiles' run heads and all-ones keys, plan[kSvPlay] the elements in play. The kernels stay with their users.
@@ -7,20 +7,11 @@
 #define MOT_VOXEL_RUNS_H_
 #include "mot_internal.h"
 #include "mot_sort.h"
+#include "mot_voxel_cell.h"   // sv_key, kSvOutside: THE cell rule (shared with the map's reader, map_judge.hip)
 
-constexpr unsigned long long kSvOutside = ~0ull;
 constexpr int kSvSorted = ((kSceneVoxelKeyBits + kSortDigitBits - 1) / kSortDigitBits) & 1;   // the buffer mot_sort_launch leaves the result in
 enum { kSvRecords = 0, kSvPlay = 1, kSvRuns = 2, kSvOutsideN = 3, kSvVoxels = 4 };   // the plan's ints
 
-// the cell of a record (include/mot.h, CELL OF A RECORD): the all-ones key when it takes no part
-__device__ __forceinline__ unsigned long long sv_key(const float4& q, const SceneVoxelArgs& a) {
-  const float lim = 3.4028234663852886e38f;
-  if (!(fabsf(q.x) <= lim && fabsf(q.y) <= lim && fabsf(q.z) <= lim)) return kSvOutside;   // (NaN fails the compare)
-  const float tx = q.x * a.inv_x, ty = q.y * a.inv_y, tz = q.z * a.inv_z;
-  if (!(tx >= -1048576.f && tx < 1048576.f && ty >= -1048576.f && ty < 1048576.f && tz >= -2048.f && tz < 2048.f)) return kSvOutside;
-  const int ix = (int)floorf(tx), iy = (int)floorf(ty), iz = (int)floorf(tz);
-  return ((unsigned long long)(unsigned)(iz + 2048) << 42) | ((unsigned long long)(unsigned)(iy + 1048576) << 21) | (unsigned long long)(unsigned)(ix + 1048576);
-}
 __device__ __forceinline__ int sv_play(const SceneVoxelBuffers& v) { return sort_count(v.plan + kSvPlay, v.cap); }
 
 // thread t owns sorted positions base + 8 t .. base + 8 t + 7 of the tile: bit q of the result = position q is a run head; *outs: its all-ones keys

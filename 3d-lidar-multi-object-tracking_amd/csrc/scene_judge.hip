@@ -42,32 +42,7 @@ __global__ void MOT_SG_BOUNDS(kSceneBlock)
 scene_judge_scan_kernel(SceneSplatInput in, SceneJudgeBuffers j, int b0, mot_scene_segment* __restrict__ segments) {
   __shared__ int s_part[kSjWaves];
   __shared__ int s_total[MOT_SCENE_CLASSES];
-  const int kb = blockIdx.x, b = b0 + kb, tid = threadIdx.x;
-  const int chunks = sj_chunks(in, j, b);
-  int* __restrict__ rows = j.rows + (long)b * j.max_chunks * kSceneJudgeRow;
-  sj_scan_chunks(rows, chunks, s_part, s_total, tid);
-  __syncthreads();
-  int first_of[MOT_SCENE_CLASSES];
-  int run = 0;
-#pragma unroll
-  for (int c = 0; c < MOT_SCENE_CLASSES; c++) {
-    const bool picked = (j.class_mask >> c) & 1;
-    first_of[c] = picked ? run : -1;
-    if (picked) run += s_total[c];
-  }
-  if (tid < MOT_SCENE_CLASSES) {
-    int* o = reinterpret_cast<int*>(segments + (long)kb * MOT_SCENE_CLASSES + tid);
-    int first = -1;
-#pragma unroll
-    for (int c = 0; c < MOT_SCENE_CLASSES; c++) first = tid == c ? first_of[c] : first;
-    o[0] = first; o[1] = s_total[tid];
-  }
-  // every thread adds the segment starts to the places it wrote itself (chunk ch is thread ch % 256's)
-  for (int ch = tid; ch < chunks; ch += kSceneBlock) {
-#pragma unroll
-    for (int c = 0; c < MOT_SCENE_CLASSES; c++)
-      if (first_of[c] > 0) rows[(long)ch * kSceneJudgeRow + MOT_SCENE_CLASSES + c] += first_of[c];
-  }
+  sj_scan_body(in, j, b0 + blockIdx.x, segments + (long)blockIdx.x * MOT_SCENE_CLASSES, s_part, s_total);
 }
 
 // ------------------------------------------------------------------------------------------ J3

@@ -21,6 +21,8 @@
 //                                  are the same additions, so the cut does not show in the bytes
 //   M6  voxel_merge_kept_kernel    per tile of 2048 runs: the kept and the saturated ones, counted; and behind M3 a second launch of the SAME kernel ranks them:
 //                                  voxel[r] = the run's place among the kept voxels, -1 for a sparse run
+//   M7  voxel_merge_index_kernel   mot_index_voxel_maps_dev alone, in M5's second place: per kept run below the capacity the run's KEY and its saturated W — the
+//                                  index of the maps' occupied cells that map_judge.hip searches (29 + 1 launches; 29 with a capacity of 0)
 //
 // 1 + 21 + 1 + 2 + 1 + 2 + 2 = 30 launches whatever the data and n_maps are (29 without an output block). No global atomics, no workgroup waits on another (no
 // look-back): the order between the launches is the only synchronisation; every count and place is a sum of integers over a fixed set, every fp64 sum has a fixed
@@ -266,6 +268,64 @@ __global__ void MOT_SORT_BOUNDS(kSortBlock) voxel_merge_kept_kernel(SceneVoxelBu
   if (rank) vm_kept_body<true>(v, s_part); else vm_kept_body<false>(v, s_part);
 }
 
+// ------------------------------------------------------------------------------------------ M7 (mot_index_voxel_maps_dev)
+// The merge without the centroid: behind M6's ranks, per kept run below the capacity the run's key ITSELF — the sorted key at the run's start, not re-derived from a
+// centroid — and W again, saturated. M5's cut (a run of at most short_max inputs by its thread, the longer ones of a wave's 64 runs by the wave); W is a sum of
+// integers, so neither the cut nor the order shows. A kernel of its own: M5 keeps its registers and its LDS (tools/kernel_resources.py).
+__global__ void MOT_SORT_BOUNDS(kSortBlock)
+voxel_merge_index_kernel(VoxelMergeMaps m, SceneVoxelBuffers v, unsigned long long* __restrict__ keys, int* __restrict__ counts, long capacity) {
+  __shared__ int s_pre[kVoxelMergeMaps + 1];
+  __shared__ long long s_w[kSortWaves][64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int n = sv_play(v);
+  int R = v.plan[kSvRuns]; R = R < 0 ? 0 : (R > n ? n : R);
+  int valid = n - v.plan[kSvOutsideN]; valid = valid < 0 ? 0 : (valid > n ? n : valid);   // the sorted positions that hold a cell
+  vm_prefix_from_plan(v, n, s_pre);
+  const int* __restrict__ start = reinterpret_cast<const int*>(v.key[kSvSorted ^ 1]);
+  const int* __restrict__ voxel = start + v.cap;
+  const unsigned long long* __restrict__ sorted = v.key[kSvSorted];
+  const unsigned* __restrict__ src = v.val[kSvSorted];
+  const int short_max = m.short_max < 0 ? 0 : (m.short_max > 64 ? 64 : m.short_max);
+  for (long base = (long)blockIdx.x * kSortBlock; base < R; base += (long)gridDim.x * kSortBlock) {   // (uniform over the workgroup)
+    const long r = base + tid;
+    int s = 0, e = 0, at = 0;
+    if (r < R) {
+      s = start[r]; e = r + 1 < R ? start[r + 1] : valid;
+      s = s < 0 ? 0 : s; e = e > valid ? valid : e;
+      at = voxel[r];
+      if (at < 0 || at >= capacity) e = s;   // (a sparse run, or no room: nothing to do)
+    }
+    const int len = e - s;
+    if (len > 0 && len <= short_max) {   // the thread's own run
+      long long W = 0;
+      for (int p = s; p < e; p++) {
+        float4 q;
+        if (vm_input(m, s_pre, src[p], n, &q)) W += __float_as_int(q.w);
+      }
+      keys[at] = sorted[s]; counts[at] = vm_stored(W);
+    }
+    unsigned long long longs = __ballot(len > short_max);
+    while (longs) {   // the wave's long runs, one after another (uniform over the wave)
+      const int l = __ffsll(longs) - 1;
+      longs &= longs - 1;
+      const int sl = __shfl(s, l), el = __shfl(e, l), atl = __shfl(at, l);
+      long long w = 0;
+      for (long p = (long)sl + lane; p < el; p += 64) {
+        float4 q;
+        if (vm_input(m, s_pre, src[p], n, &q)) w += __float_as_int(q.w);
+      }
+      s_w[wave][lane] = w;
+      MOT_WAVE_SYNC();
+      if (lane == 0) {
+        long long W = 0;
+        for (int k = 0; k < 64; k++) W += s_w[wave][k];
+        keys[atl] = sorted[sl]; counts[atl] = vm_stored(W);
+      }
+      MOT_WAVE_SYNC();   // (s_w is read: the next round may write it)
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------ host
 static unsigned vm_blocks(int cap) {
   const long blocks = ((long)cap + kSortBlock - 1) / kSortBlock;
@@ -287,4 +347,8 @@ void mot_launch_voxel_merge_count(const VoxelMergeMaps& m, const SceneVoxelBuffe
 void mot_launch_voxel_merge_write(const VoxelMergeMaps& m, const SceneVoxelBuffers& v, int min_points, mot_model_voxel* out, long out_capacity, hipStream_t stream) {
   if (!out || out_capacity <= 0) return;
   hipLaunchKernelGGL(voxel_merge_reduce_kernel, dim3(vm_blocks(v.cap)), dim3(kSortBlock), 0, stream, m, v, min_points, 1, out, out_capacity);
+}
+void mot_launch_voxel_merge_index(const VoxelMergeMaps& m, const SceneVoxelBuffers& v, unsigned long long* keys, int* counts, long capacity, hipStream_t stream) {
+  if (!keys || !counts || capacity <= 0) return;
+  hipLaunchKernelGGL(voxel_merge_index_kernel, dim3(vm_blocks(v.cap)), dim3(kSortBlock), 0, stream, m, v, keys, counts, capacity);
 }

@@ -196,3 +196,38 @@ def play_merged_voxel_map(ctx, frames, leaf, min_points: int = 1, dt_us: float =
         acc = ctx.merge_voxel_maps(([acc] if acc is not None else []) + take, leaf, 1 if rest else min_points)
         if not rest:
             return acc, heads
+
+
+def play_against_map(ctx, frames, index, min_count: int = 1, reach: int = 0, dt_us: float = 1.0e5, t0: float = 1.0e9, slot_count: int = 1, upload=None) -> np.ndarray:
+    """Yesterday's map, today's drive: the drive played frame by frame with `Context.frames_dev` on slot 0 and every frame judged against a voxel index
+    (`Context.index_voxel_maps_dev` -> `Context.export_map_points_dev`, counts alone: no records travel). Needs `set_track_links(True)`; the scene grid is not needed.
+
+    frames: a sequence of (cloud, v, yaw), clouds (n, 4) float32. index: the `MotVoxelIndex` an index call filled, its blocks on the device. upload: host array ->
+    (device pointer, an object that keeps the block alive); default: through torch. slot_count: the slots of a call (the context's others get the same frame).
+    Returns counts [len(frames), 5] int64: per frame the elevated points per class MAP_OUTSIDE .. MAP_PRESENT — MAP_ABSENT counts what stands where the map
+    has nothing. One synchronisation, at the end: the segment tables of all frames stay on the device until then."""
+    MAP_CLASSES = 5   # (MOT_MAP_CLASSES of include/mot.h)
+    upload = upload or _torch_upload
+    frames = list(frames)
+    stride = ctx.max_points
+    seg_host = np.zeros((max(len(frames), 1), slot_count, MAP_CLASSES, 2), np.int32)
+    seg_ptr, seg_keep = upload(seg_host)
+    keeps = []
+    for k, (cloud, v, yaw) in enumerate(frames):
+        a = np.asarray(cloud, np.float32).reshape(-1, 4)
+        if len(a) > stride:
+            raise ValueError(f"frame {k}: {len(a)} points, the context holds {stride}")
+        host = np.zeros((slot_count, stride, 4), np.float32)
+        host[:, : len(a)] = a
+        ptr, keep = upload(host)
+        keeps.append(keep)
+        ctx.frames_dev(ptr, stride * 4, [len(a)] * slot_count, run_tracker=True, timestamps=[t0 + k * dt_us] * slot_count, ego_v=[v] * slot_count, ego_yaw=[yaw] * slot_count)
+        ctx.export_map_points_dev(slot_count, index, 0, 0, seg_ptr + k * seg_host[0].nbytes, min_count=min_count, reach=reach, classes=0)
+    ctx.synchronize()
+    if hasattr(seg_keep, "to_host"):
+        seg = seg_keep.to_host(seg_host.dtype, seg_host.shape)
+    elif hasattr(seg_keep, "cpu"):
+        seg = seg_keep.cpu().numpy()
+    else:
+        seg = np.asarray(seg_keep).reshape(seg_host.shape)
+    return seg[: len(frames), 0, :, 1].astype(np.int64)

@@ -989,6 +989,79 @@ int mot_merge_voxel_maps_dev(mot_ctx* ctx, const mot_voxel_map_src* maps /* HOST
 int mot_merge_voxel_maps(mot_ctx* ctx, const mot_voxel_map_src* maps /* host array, host blocks */, int n_maps, const mot_voxel_params* voxel,
         mot_model_voxel* out /* may be NULL */, long out_capacity, long* n_voxels, mot_voxel_merge_header* header);
 
+/* ---------------------------------------------------------------- voxel maps indexed, and a frame's points judged against the index (additions within ABI v6)
+ * The reader of the maps above: given the static map of an earlier pass, which points of the live frame lie where the map has something standing, and which lie
+ * where it has nothing — a parked car that was not there yesterday, a barrier. Two calls: a device-resident INDEX of one or several voxel maps, and a JUDGE that
+ * gives every elevated point of a fused step one verdict against it, the points partitioned by verdict in the shape of mot_export_scene_points_dev. Asynchronous on
+ * the context stream, no host round trip from drive to map to the next drive. Nothing is launched or allocated unless these calls are used.
+ *
+ * mot_index_voxel_maps_dev. EXACTLY the merge's meaning (above) without the centroid: INPUTS, CELL OF AN INPUT, LEAF and the cells, W and n_saturated of VOXELS are
+ * those rules word for word, the counts of the maps read on the device and clamped — a count may point at an earlier export's or merge's n_stored, so export ->
+ * merge -> index -> judge never synchronises. The kept cells are the distinct cells in ascending key order whose W >= min_points;
+ *   keys[r]   = the cell's key itself: (i_z + 2^11) << 42 | (i_y + 2^20) << 21 | (i_x + 2^20) — the sorted key of its inputs, not re-derived from a centroid;
+ *   counts[r] = min(W, 2^31 - 1);
+ * the first `capacity` kept cells are stored and nothing is written beyond. *header is a mot_voxel_merge_header with the merge's meaning, field for field (n_stored =
+ * min(n_voxels, capacity): the index's length). The call writes leaf_x/y/z of the descriptor from `voxel` (the judge takes its leaf from there) and reserved = 0.
+ * REFUSALS, each before anything is launched, the caller's blocks and the descriptor untouched: those of mot_merge_voxel_maps_dev with keys / counts / header read
+ * in place of d_out / d_header — MOT_E_ARG for a null index, index->header or voxel; null keys or counts with capacity > 0; a capacity outside [0, 2^31 - 1]; keys
+ * off 8 bytes, counts or header off 4; keys, counts or header overlapping any input block or count word, or each other. MOT_E_HIP when the scratch cannot be had.
+ * Scratch and kernels: the merge's own block and its count launches as they are (csrc/voxel_merge.hip), then ONE write launch — per kept cell below the capacity
+ * the key and the saturated W, a run of at most 64 inputs by one thread, a longer one by a wave. 30 launches whatever the data (29 with a capacity of 0).
+ *
+ * mot_export_map_points_dev. CLASS of an elevated point of the slot's latest fused step, the rules in this order:
+ *   1 MOVING   the grid's KIND rule says DYNAMIC: owner id >= 0 and that track's is_static, as this step left it, is 0 (an id or a track slot out of range counts as
+ *              dynamic). No cell is needed.
+ *   2 OUTSIDE  the point's global record takes no part by the rule CELL OF A RECORD (above): the coordinates are the bits mot_export_track_points_dev writes with
+ *              MOT_FRAME_GLOBAL — the bits a drive's map is made from — and the cell test is the map's own device function with inv_a = 1.0f / index->leaf_a, computed
+ *              once on the host. A non-finite global coordinate is OUTSIDE.
+ *   3 otherwise, with (i_x, i_y, i_z) the point's cell and n = clamp(header->n_stored, 0, capacity), read ON THE DEVICE: the neighbourhood is the cells
+ *     (i_x + d_x, i_y + d_y, i_z + d_z), |d| <= reach, that lie inside the lattice (i_x, i_y in [-2^20, 2^20), i_z in [-2^11, 2^11)); a neighbour outside the
+ *     lattice is in no map — the cell before i_x = -2^20 is NOT the last cell of the row below.
+ *     PRESENT  some neighbourhood cell is among keys[0..n) with counts >= min_count.
+ *     SPARSE   some neighbourhood cell is among keys[0..n), none of them reaches min_count.
+ *     ABSENT   none is. n == 0 makes every such point ABSENT.
+ * An index whose blocks were not written by mot_index_voxel_maps_dev gives unspecified classes, never an access outside the blocks.
+ * OUTPUT: word for word that of mot_export_scene_points_dev with these five classes — d_segments[b * 5 + k] = {first, count} with the TRUE count of every class and
+ * first = -1 outside the mask; the selected classes packed in ascending class order into d_points[b * point_stride ..], records {x, y, z, index} in input order
+ * (MOT_ORDER_ANY included), MOT_FRAME_SENSOR or MOT_FRAME_GLOBAL, truncated at point_stride; d_points == NULL with stride 0 and mask 0: the counts alone; d_classes
+ * optional, truncated at class_stride. mot_get_map_points is mot_get_scene_points' twin: one slot to the host (synchronises), the counts and the table always
+ * delivered, MOT_E_CAPACITY with nothing copied when a buffer that was given is too small. Its index blocks are DEVICE blocks all the same.
+ * VALIDITY: the slot's cloud, boxes and tracker step come from ONE fused call with links on (MOT_E_STATE otherwise, and on sequence slots). The scene grid is NOT
+ * required: the calls work with the grid off, read nothing of it and leave its validity alone. They change no slot, no step counter, no accumulator.
+ * REFUSALS, each before anything is launched, the caller's blocks untouched: MOT_E_STATE as above; MOT_E_ARG for a null index or params; a leaf in the descriptor
+ * that is not finite or outside [1e-2, 1e3]; min_count < 1; reach outside {0, 1}; mask bits >= 5; an unknown frame; a batch outside [1, max_batch]; a negative
+ * stride; null d_points with a stride or a mask; null d_segments; d_points or d_segments off 4 bytes, keys off 8, counts or header off 4; an index capacity outside
+ * [0, 2^31 - 1]; a null header; null keys or counts with capacity > 0; an output block overlapping an index block. MOT_E_HIP when the scratch cannot be had.
+ * Scratch of the calls' own, at the first call, all of it or none (the next call tries again): 1 byte per point of max_points and 40 bytes per 2048 points per slot,
+ * a 48-byte-per-slot argument block and a page-locked ring in front of it; the getter's staging block at ITS first call. Released by mot_destroy alone.
+ * Kernels (csrc/map_judge.hip): classify — per point 16 bytes read, the kind rule's two gathers for an owned point, the transform and the cell, then a binary
+ * search of the keys (reach 0: one lower bound of at most 32 steps and a compare; reach 1: nine, one per (i_z + d_z, i_y + d_y) row, each followed by at most three
+ * consecutive entries: a row's three x-neighbours are adjacent in key order); only the first lane of a run of equal cells inside a wave searches. Then the scene
+ * judge's scan and scatter, the same text. Three launches whatever the data; no global atomics, no workgroup waits on another, the output does not depend on
+ * scheduling. Cost: profiles/map_judge.md (tools/time_map_judge.py).
+ * OUT OF SCOPE: a recorded-drive (sequence-slot) variant; host-block variants of the index call; reach > 1; updating an index in place. */
+typedef struct mot_voxel_index {       /* HOST struct of device pointers; 48 bytes */
+  uint64_t* keys;                      /* [capacity], 8-byte aligned: the occupied cells' keys, strictly ascending */
+  int32_t*  counts;                    /* [capacity], 4-byte aligned: the cell's summed count, saturated at 2^31 - 1 */
+  mot_voxel_merge_header* header;      /* device, 4-byte aligned; header->n_stored is the index's length, read ON THE DEVICE by the judge */
+  long capacity;                       /* [0, 2^31 - 1] */
+  float leaf_x, leaf_y, leaf_z;        /* written by the index call from `voxel`: the judge takes its leaf from here */
+  int32_t reserved;                    /* 0 */
+} mot_voxel_index;
+int mot_index_voxel_maps_dev(mot_ctx* ctx, const mot_voxel_map_src* maps /* HOST array */, int n_maps, const mot_voxel_params* voxel,
+        mot_voxel_index* index /* in: keys, counts, header, capacity; out: leaf */);
+enum { MOT_MAP_OUTSIDE = 0, MOT_MAP_MOVING = 1, MOT_MAP_SPARSE = 2, MOT_MAP_ABSENT = 3, MOT_MAP_PRESENT = 4, MOT_MAP_CLASSES = 5 };
+typedef struct mot_map_judge_params {
+  int32_t min_count;                   /* [1, 2^31 - 1]: a cell counts as standing from this summed count on */
+  int32_t reach;                       /* 0: the point's own cell; 1: its 27 neighbours */
+} mot_map_judge_params;
+int mot_export_map_points_dev(mot_ctx* ctx, int batch, const mot_voxel_index* index, const mot_map_judge_params* params, int class_mask, int frame,
+        mot_track_point* d_points, long point_stride, mot_scene_segment* d_segments /* [batch][5] */,
+        uint8_t* d_classes /* may be NULL */, long class_stride);
+int mot_get_map_points(mot_ctx* ctx, int slot, const mot_voxel_index* index /* device blocks */, const mot_map_judge_params* params, int class_mask, int frame,
+        mot_track_point* points, int point_capacity, int* n_points, mot_scene_segment segments[5],
+        uint8_t* classes /* may be NULL */, int class_capacity, int* n_elevated);
+
 /* on != 0: the fused entry points send their launch sequence (13 kernels with the tracker) as ONE hipGraph launch, captured once per launch geometry
  * (batch, chunks of the largest frame, tracker on / off, outputs); what changes per call without changing the geometry travels in the
  * device-resident argument block. For contexts somebody waits on frame by frame (one or a few streams): the host's part of a frame
